@@ -64,6 +64,8 @@ ALGO_BYTES_PER_GLOBAL_VIEW = 17600 + 300
 # reachability: 38 + 3 floats out, position / key / level in, the env's cache row read or written (npp_reach_kernel.hip)
 ALGO_BYTES_PER_REACH = 340
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s peak
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 0                  # the env rows kept when the outputs exceed the budget
 
 
 def committed_traffic(kernel="step", workload="c0", variant=None):
@@ -98,6 +100,31 @@ def committed_traffic(kernel="step", workload="c0", variant=None):
         except Exception:
             pass
     return best
+
+
+def write_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: write {name: array [N, ...]} (one row per env) as out_dir/<name>.npy, float64 arrays as float64 and every
+    other dtype as float32 (exact for the int8 / int16 / uint8 fields).  If the whole set is larger than `budget` bytes, every array
+    keeps the same fixed, seeded sample of env rows (sorted), and the kept env indices are written as env_index.npy (float64).
+    Returns {"dir", "envs", "envs_kept", "bytes", "arrays": {name: shape}} for the result line."""
+    out = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    n = len(next(iter(out.values())))
+    assert all(len(a) == n for a in out.values()), "every output has one row per env"
+    per_env = sum(a[0].nbytes for a in out.values()) if n else 0
+    room = budget - 256 * (len(out) + 1)   # what the .npy headers leave of the budget
+    rows = None
+    if per_env * n > room:
+        keep = int(room // (per_env + 8))   # + the float64 env index of each kept row
+        if keep < 1:
+            raise ValueError("one env's outputs (%d B) exceed the dump budget (%d B)" % (per_env, budget))
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        out = {k: a[rows] for k, a in out.items()}
+        out["env_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "envs": n, "envs_kept": n if rows is None else len(rows), "bytes": int(sum(a.nbytes for a in out.values())),
+            "arrays": {k: list(a.shape) for k, a in out.items()}}
 
 
 def cpu_baseline(levels, seconds_target=12.0):
@@ -174,6 +201,11 @@ def parse_args(argv=None):
     ap.add_argument("--rank-timeout", type=float, default=1500.0,
                     help="seconds after which `bench.py --gpus N` gives up on its rank processes")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when this process starts the ranks itself")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps of the headline workload, write what its last timed step computed (the output block "
+                         "fields a caller of NppBatch.step and of the timed observation kernels reads; rank 0's envs) as DIR/<name>.npy in "
+                         "float32 / float64, at most 64 MB in all (a fixed, seeded sample of env rows beyond that, indices in env_index.npy).  "
+                         "The inputs are seeded, so runs with the same arguments can be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -271,9 +303,10 @@ STEP_NOTE = ("issue-cadence-bound fp64 scalar chains (about 7k dependent flops p
              "traffic_source (a process cannot run PMC passes on itself)")
 
 
-def run_workload(ctx, workload, K, W, P, player_frame=False, full_obs=False, gather_obs=False, secondaries=False):
+def run_workload(ctx, workload, K, W, P, player_frame=False, full_obs=False, gather_obs=False, secondaries=False, dump_dir=None):
     """Time K npp_step launches (+ the observation kernels asked for) of one workload after P + W untimed ones.  Returns the
-    block of figures for that workload (rank 0) -- `value` is the whole-job rate over all ranks."""
+    block of figures for that workload (rank 0) -- `value` is the whole-job rate over all ranks.  dump_dir: write the outputs of
+    the last timed launch there (write_outputs) before anything else steps the batch."""
     import torch
 
     from nclone_amd import levels as level_sets
@@ -348,6 +381,14 @@ def run_workload(ctx, workload, K, W, P, player_frame=False, full_obs=False, gat
     for k in range(P + W):
         one(k)
     dt, step_us, render_us = timed(P + W)
+    dumped = None
+    if dump_dir is not None and rank == 0:
+        # the fields the timed launches wrote (terminal_state is not: they run with want_terminal=False)
+        names = ["game_state", "entity_pos", "reward", "frames", "action_mask", "flags"]
+        names += [k for k in ("spatial_context", "switch_states", "player_frame", "global_view", "reachability_features", "mine_sdf_features")
+                  if k in outputs]
+        torch.cuda.synchronize()
+        dumped = write_outputs({k: b.out.t[k].cpu().numpy() for k in names}, dump_dir)
     done_frac = float((b.flags & 3).ne(0).float().mean().item())
     # build variant of the G = 16 step kernels picked by npp_step's autotuner during the pre-roll (include/npp_amd.h: npp_set_step_variant)
     sv = b.step_variant()
@@ -553,6 +594,8 @@ def run_workload(ctx, workload, K, W, P, player_frame=False, full_obs=False, gat
         blk["async_subbatches"] = async_rep
     if many_rep is not None:
         blk["open_loop_rollout"] = many_rep
+    if dumped is not None:
+        blk["dump_outputs"] = dumped
     blk["_levels"] = levels
     return blk
 
@@ -602,7 +645,7 @@ def main():
     K, W, P = args.steps, args.warmup, args.preroll
     single = args.workload is not None
     head = run_workload(ctx, args.workload or "c0", K, W, P, player_frame=args.player_frame, full_obs=args.full_obs,
-                        gather_obs=args.gather_obs, secondaries=True)
+                        gather_obs=args.gather_obs, secondaries=True, dump_dir=args.dump_outputs)
     others = {}
     Ko = args.other_steps
     if not single and Ko > 0 and not (args.player_frame or args.full_obs or args.gather_obs):
