@@ -312,6 +312,29 @@ int npp_get_launch_geometry(npp_handle h, int *lanes_per_env, int *waves_per_blo
  * only of those with moving entities -- and npp_load_levels refuses a plan that does not cover one of its levels. */
 int npp_plan_zoo_block(const double *blob, const int64_t *offsets, int n_levels, int *doors, int *movers, int *words);
 
+/* Frame stacking (the reference's FrameStackWrapper, nclone/gym_environment/frame_stack_wrapper.py; device rings in
+ * npp_stack.hip).  Replaces the wrapper's deques (frame_stack_wrapper.py:123-129) with one ring per stacked key and env:
+ * 2 K slots, the entry at ring position q stored in slots q and q + K, so every window of K entries is contiguous.
+ * npp_set_frame_stack: visual_k / state_k entries of player_frame / game_state (1..12, the range checked at
+ *   frame_stack_wrapper.py:116-121; 0 = that key is not stacked), padding 0 "zero" or 1 "repeat" (frame_stack_wrapper.py:183-188).
+ *   (Re)allocates zeroed rings; invalid arguments return NPP_ERR_INVALID.  Synchronises the handle's stream.
+ * npp_frame_stack_render: player_frame of every env straight into the ring slots of the entry the next push completes
+ *   (npp_render_player_frame with a ring stride; the observation overlap applies the same way).
+ * npp_frame_stack_push: completes one entry -- the observation() append of frame_stack_wrapper.py:334-338 -- from d_game_state
+ *   [N,41] (and the frame rendered before), and re-pads every env that was reset: reset_all, or (d_flags[e] & reset_bits) != 0
+ *   (the in-kernel auto-reset).  Re-padding writes the K - 1 older entries of the window (reset() / _reset_to_checkpoint_from_wrapper,
+ *   frame_stack_wrapper.py:190-264).  d_terminal_stack [N,state_k,41] (may be NULL; needs state stacking and d_terminal_state):
+ *   per env the stack it shows after this push, except that a reset env gets the last K - 1 entries of its previous window
+ *   followed by d_terminal_state[e].  Launch it after npp_join: it reads the outputs of the observation kernels.
+ * npp_frame_stack_view: which 0 = player_frame ring (u8 elements), 1 = game_state ring (f32 elements): *base, and the element
+ *   offset of env 0's oldest entry and the element stride between envs of the current window (its K entries of 7056 or 41
+ *   elements are contiguous, oldest first).  Valid until the next push. */
+int npp_set_frame_stack(npp_handle h, int visual_k, int state_k, int padding);
+int npp_frame_stack_render(npp_handle h);
+int npp_frame_stack_push(npp_handle h, const float *d_game_state, const float *d_terminal_state, const uint8_t *d_flags,
+                         int reset_bits, int reset_all, float *d_terminal_stack);
+int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, int64_t *batch_stride);
+
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);
 

@@ -30,6 +30,7 @@ EXPORTS = [
     "npp_set_launch_geometry", "npp_get_launch_geometry", "npp_snapshot", "npp_restore", "npp_entity_checksum", "npp_compile_level_zoo", "npp_render_global_view", "npp_switch_states", "npp_set_entity_pos", "npp_step_many", "npp_render_frame", "npp_plan_zoo_block", "npp_reset_ex",
     "npp_reachability", "npp_reachability_ex", "npp_reach_compile", "npp_reach_features_host", "npp_reach_compile_miss", "npp_reach_rollout_host", "npp_set_dynamic_truncation", "npp_level_truncation_limit",
     "npp_set_obs_overlap", "npp_set_obs_overlap_parts", "npp_join",
+    "npp_set_frame_stack", "npp_frame_stack_render", "npp_frame_stack_push", "npp_frame_stack_view",
 ]
 
 
@@ -119,6 +120,10 @@ def lib():
     L.npp_level_truncation_limit.argtypes = [C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.npp_snapshot.argtypes = [H]
     L.npp_restore.argtypes = [H, C.POINTER(C.c_uint8)]
+    L.npp_set_frame_stack.argtypes = [H, C.c_int, C.c_int, C.c_int]
+    L.npp_frame_stack_render.argtypes = [H]
+    L.npp_frame_stack_push.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.npp_frame_stack_view.argtypes = [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

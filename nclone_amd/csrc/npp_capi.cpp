@@ -105,6 +105,11 @@ struct npp_handle_s {
     float *d_rcache = nullptr, *s_rcache = nullptr;     // [n][REACH_DIM + 1]
     int s_reach = 0;                                    // the snapshot slot holds a reachability cache
     ReachMissDev rmiss = {nullptr, nullptr, nullptr, nullptr};   // per-env dictionary of the miss branch (levels with ReachHdr::miss_exit only)
+    // frame stacking (npp_set_frame_stack / npp_frame_stack_push, npp_stack.hip): one ring of 2 K slots per env and stacked key
+    int fs_vk = 0, fs_sk = 0, fs_repeat = 0;   // stack sizes (0 = off) and padding
+    int fs_vhead = 0, fs_shead = 0;            // ring position of the newest entry
+    uint8_t *d_fs_frames = nullptr;            // [n][2 fs_vk][84 * 84]
+    float *d_fs_state = nullptr;               // [n][2 fs_sk][41]
     LevelHdr *d_hdr = nullptr;
     int n_words_max = 1;
     uint32_t hot_max = 0;      // largest staged-level size over the loaded set
@@ -587,6 +592,7 @@ int npp_destroy(npp_handle h) {
         for (int p = 0; p < 2; p++)
             if (h->side_ev[k][p]) hipEventDestroy(h->side_ev[k][p]);
     hipFree(h->d_phase);
+    hipFree(h->d_fs_frames); hipFree(h->d_fs_state);
     free_reach(h);
     hipFree(h->s_f64); hipFree(h->s_u32); hipFree(h->s_ent); hipFree(h->s_sc); hipFree(h->d_zoo); hipFree(h->s_zoo);
     delete h;
@@ -1168,8 +1174,11 @@ int npp_observe(npp_handle h, const npp_step_out *out) {
     return NPP_OK;
 }
 
-int npp_render_player_frame(npp_handle h, uint8_t *d_out) {
-    if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_render_player_frame: bad arguments");
+}  // extern "C"
+
+namespace {
+// player_frame of every env into d_out + env * stride (and, with mirror != 0, also mirror bytes further on)
+int render_player_frame(npp_handle h, uint8_t *d_out, uint32_t stride, uint32_t mirror) {
     if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_player_frame: no levels loaded");
     ON_DEVICE(h);
     bool tables = !h->d_canvas;   // (observation overlap) something the second stream has to wait for was put on the caller's stream
@@ -1191,7 +1200,89 @@ int npp_render_player_frame(npp_handle h, uint8_t *d_out) {
         a.wg_cost = h->d_pf_cost;
     }
     const int centered = (h->flags & NPP_FLAG_FRAME_CENTERED) ? 1 : 0;
-    return obs_launch(h, a, 1, tables, [&](const KernelArgs &ka, hipStream_t st) { return launch_render(ka, d_out, centered, st); });
+    return obs_launch(h, a, 1, tables,
+                      [&](const KernelArgs &ka, hipStream_t st) { return launch_render(ka, d_out, centered, st, stride, mirror); });
+}
+}  // namespace
+
+extern "C" {
+
+int npp_render_player_frame(npp_handle h, uint8_t *d_out) {
+    if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_render_player_frame: bad arguments");
+    return render_player_frame(h, d_out, 84 * 84, 0);
+}
+
+int npp_set_frame_stack(npp_handle h, int visual_k, int state_k, int padding) {
+    if (!h || visual_k < 0 || visual_k > 12 || state_k < 0 || state_k > 12 || padding < 0 || padding > 1)
+        return fail(h, NPP_ERR_INVALID, "npp_set_frame_stack: stack sizes must be 0 (off) or 1..12 and padding 0 (zero) or 1 (repeat)");
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the old rings may still be read by queued work
+    hipFree(h->d_fs_frames); hipFree(h->d_fs_state);
+    h->d_fs_frames = nullptr; h->d_fs_state = nullptr;
+    h->fs_vk = h->fs_sk = 0;
+    const size_t N = (size_t)h->n;
+    if (visual_k) {
+        const size_t b = N * 2 * visual_k * 84 * 84;
+        HIP_TRY(h, hipMalloc((void **)&h->d_fs_frames, b));
+        HIP_TRY(h, hipMemsetAsync(h->d_fs_frames, 0, b, h->stream));
+    }
+    if (state_k) {
+        const size_t b = N * 2 * state_k * NPP_GAME_STATE_DIM * sizeof(float);
+        HIP_TRY(h, hipMalloc((void **)&h->d_fs_state, b));
+        HIP_TRY(h, hipMemsetAsync(h->d_fs_state, 0, b, h->stream));
+    }
+    h->fs_vk = visual_k; h->fs_sk = state_k; h->fs_repeat = padding;
+    h->fs_vhead = visual_k ? visual_k - 1 : 0;   // the first push completes position 0
+    h->fs_shead = state_k ? state_k - 1 : 0;
+    return NPP_OK;
+}
+
+int npp_frame_stack_render(npp_handle h) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->fs_vk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_render: visual stacking is off (npp_set_frame_stack)");
+    const int K = h->fs_vk, q = (h->fs_vhead + 1) % K;
+    const uint32_t slot = 84 * 84, stride = (uint32_t)(2 * K) * slot;
+    // position q lives in slots q and q + K; slot 0 is never inside a window, so position 0 is written once
+    uint8_t *dst = h->d_fs_frames + (size_t)(q ? q : K) * slot;
+    return render_player_frame(h, dst, stride, q ? (uint32_t)K * slot : 0u);
+}
+
+int npp_frame_stack_push(npp_handle h, const float *d_game_state, const float *d_terminal_state, const uint8_t *d_flags,
+                         int reset_bits, int reset_all, float *d_terminal_stack) {
+    if (!h || !d_game_state || (!reset_all && reset_bits && !d_flags) || (d_terminal_stack && !d_terminal_state))
+        return fail(h, NPP_ERR_INVALID, "npp_frame_stack_push: bad arguments");
+    if (!h->fs_vk && !h->fs_sk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_push: frame stacking is off (npp_set_frame_stack)");
+    if (d_terminal_stack && !h->fs_sk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_push: a terminal stack needs state stacking");
+    ON_DEVICE_JOINED(h);
+    if (h->fs_vk) h->fs_vhead = (h->fs_vhead + 1) % h->fs_vk;
+    if (h->fs_sk) h->fs_shead = (h->fs_shead + 1) % h->fs_sk;
+    StackArgs a;
+    a.n = h->n;
+    a.visual_k = h->fs_vk; a.state_k = h->fs_sk;
+    a.vhead = h->fs_vhead; a.shead = h->fs_shead;
+    a.repeat = h->fs_repeat;
+    a.reset_bits = d_flags ? reset_bits : 0;
+    a.reset_all = reset_all ? 1 : 0;
+    a.flags = d_flags;
+    a.game_state = d_game_state;
+    a.terminal_state = d_terminal_state;
+    a.frames = h->d_fs_frames;
+    a.state = h->d_fs_state;
+    a.terminal_stack = d_terminal_stack;
+    HIP_TRY(h, launch_stack_push(a, h->stream));
+    return NPP_OK;
+}
+
+int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, int64_t *batch_stride) {
+    if (!h || (which != 0 && which != 1) || !base || !offset || !batch_stride) return fail(h, NPP_ERR_INVALID, "npp_frame_stack_view: bad arguments");
+    const int K = which == 0 ? h->fs_vk : h->fs_sk;
+    if (!K) return fail(h, NPP_ERR_STATE, "npp_frame_stack_view: that stack is off (npp_set_frame_stack)");
+    const int64_t E = which == 0 ? 84 * 84 : NPP_GAME_STATE_DIM;
+    const int head = which == 0 ? h->fs_vhead : h->fs_shead;
+    *base = which == 0 ? (void *)h->d_fs_frames : (void *)h->d_fs_state;
+    *offset = (int64_t)(head + 1) * E;
+    *batch_stride = (int64_t)2 * K * E;
+    return NPP_OK;
 }
 
 int npp_set_entity_pos(npp_handle h, int env, int kind, double x, double y) {

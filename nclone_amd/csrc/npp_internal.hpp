@@ -158,7 +158,23 @@ hipError_t launch_reset(const KernelArgs &a, hipStream_t s);
 // per-env copy of every state plane from `src` into the live state (a.reset_mask selects envs; NULL = all)
 hipError_t launch_restore(const KernelArgs &a, const double *src_f64, const uint32_t *src_u32, const uint32_t *src_ent,
                           const float *src_sc, const double *src_zoo, hipStream_t s);
-hipError_t launch_render(const KernelArgs &a, uint8_t *d_out, int centered, hipStream_t s);
+// stride: bytes between the frames of consecutive envs; mirror: non-zero = each frame is also written `mirror` bytes further on
+hipError_t launch_render(const KernelArgs &a, uint8_t *d_out, int centered, hipStream_t s, uint32_t stride = 84 * 84, uint32_t mirror = 0);
+// npp_stack.hip: one frame-stack push (see npp_frame_stack_push in include/npp_amd.h)
+struct StackArgs {
+    int n;
+    int visual_k, state_k;        // 0 = that ring is off
+    int vhead, shead;             // ring position of the entry this push completes (its slots are head and head + K)
+    int repeat;                   // padding: 0 zeros, 1 copies of the newest entry
+    int reset_bits, reset_all;    // env e is re-padded when reset_all or (flags[e] & reset_bits)
+    const uint8_t *flags;
+    const float *game_state;      // [n][41] this step's entry
+    const float *terminal_state;  // [n][41] (reset envs) the state at the terminal step
+    uint8_t *frames;              // [n][2 visual_k][84 * 84]
+    float *state;                 // [n][2 state_k][41]
+    float *terminal_stack;        // [n][state_k][41] or null
+};
+hipError_t launch_stack_push(const StackArgs &a, hipStream_t s);
 // max_records: the largest number of draw records (closed-door strokes + entities + movers) of a loaded level; sizes the LDS
 // xscr: the per-env scratch of the split cell pass (GV_XSTRIDE bytes per env); null keeps the whole cell pass inside the first kernel
 constexpr size_t GV_XSTRIDE = 14336;

@@ -608,7 +608,7 @@ __device__ inline uint32_t span_plain(const FrameLds &L, const Window &wd, int r
 // aligned dwords S0..S5 (its 24-byte gray row) and N0 (the first dword of the next cell's row): row, cell, tile id and the
 // drawable test are paid once per six dwords instead of once per dword.  Strip k of a row owns dwords 6 k - m .. 6 k - m + 5,
 // m = (col0 % 24) / 4 (those whose first pixel lies in the cell); five strips cover the 21 dwords.
-__device__ inline void pass1_strips(FrameLds &L, const Window &wd, uint32_t *dst) {
+__device__ inline void pass1_strips(FrameLds &L, const Window &wd, uint32_t *dst, uint32_t mdw) {
     constexpr int DW_PER_ROW = FW / 4;
     const uint32_t sh = (uint32_t)wd.col0 & 3u;
     const int cxb = wd.col0 / 24;
@@ -617,7 +617,10 @@ __device__ inline void pass1_strips(FrameLds &L, const Window &wd, uint32_t *dst
         const int r = item / 5, k = item - r * 5;
         const int fr = r - wd.top;
         if (fr < 0 || fr >= wd.h) {   // a padding row (cv2.copyMakeBorder(..., value=0)): its five lanes clear it
-            for (int j = k; j < DW_PER_ROW; j += 5) dst[r * DW_PER_ROW + j] = 0;
+            for (int j = k; j < DW_PER_ROW; j += 5) {
+                dst[r * DW_PER_ROW + j] = 0;
+                if (mdw) dst[r * DW_PER_ROW + j + mdw] = 0;
+            }
             continue;
         }
         const int j0 = 6 * k - m;
@@ -652,7 +655,11 @@ __device__ inline void pass1_strips(FrameLds &L, const Window &wd, uint32_t *dst
             if (j < 0 || j >= DW_PER_ROW) continue;
             const int q = r * DW_PER_ROW + j;
             if ((slow >> i) & 1u) L.queue[atomicAdd(&L.nq, 1)] = (unsigned short)q;
-            else dst[q] = __builtin_amdgcn_alignbyte(S[i + 1], S[i], sh);
+            else {
+                const uint32_t v = __builtin_amdgcn_alignbyte(S[i + 1], S[i], sh);
+                dst[q] = v;
+                if (mdw) dst[q + mdw] = v;
+            }
         }
     }
 }
@@ -686,7 +693,11 @@ __device__ inline uint32_t pixel_full(const FrameLds &L, const Window &wd, const
 #ifndef NPP_RENDER_OCC
 #define NPP_RENDER_OCC 5
 #endif
-__global__ __launch_bounds__(256, NPP_RENDER_OCC) void npp_render_kernel(KernelArgs a, uint8_t *out, int centered) {
+// `stride`: bytes from one env's frame to the next (FW * FH for a plain [N, 84, 84] output; the frame-stack ring of
+// npp_stack.hip passes 2 K * FW * FH).  `mirror`: when non-zero, every dword is also written `mirror` bytes further on (the ring's
+// second copy of the slot); 0 for the plain output.
+__global__ __launch_bounds__(256, NPP_RENDER_OCC) void npp_render_kernel(KernelArgs a, uint8_t *out, int centered, uint32_t stride,
+                                                                        uint32_t mirror) {
     __shared__ FrameLds L;
     if ((int)blockIdx.x >= a.n) return;
     // heavy-first: the envs whose frame took longest last time (many drawables in the window) are dispatched first
@@ -701,13 +712,17 @@ __global__ __launch_bounds__(256, NPP_RENDER_OCC) void npp_render_kernel(KernelA
     const FrameHdr fh = {H.off_draw_recs, H.n_door, H.n_ent + H.n_mov, H.has_zoo, H.off_tiles, H.obs_switch, H.obs_door};
     const double px = a.f64[(size_t)F_X * a.n + env], py = a.f64[(size_t)F_Y * a.n + env];
     const Window wd = frame_window(px, py, centered);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(out + (size_t)env * FW * FH);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(out + (size_t)env * stride);
     constexpr int DW_PER_ROW = FW / 4;   // 21
+    const uint32_t mdw = mirror / 4u;    // (uniform) the mirror copy, in dwords
 #ifdef NPP_RENDER_STAMPS
     const unsigned long long t1 = wd.h ? __builtin_amdgcn_s_memtime() : __builtin_amdgcn_s_memtime();
 #endif
     if (wd.h == 0 || wd.w == 0) {        // the window lies outside the canvas (axis swap with player_x > 642): all padding
-        for (int q = threadIdx.x; q < DW_PER_ROW * FH; q += blockDim.x) dst[q] = 0;
+        for (int q = threadIdx.x; q < DW_PER_ROW * FH; q += blockDim.x) {
+            dst[q] = 0;
+            if (mdw) dst[q + mdw] = 0;
+        }
         if (a.wg_cost && threadIdx.x == 0) a.wg_cost[env] = (uint32_t)(__builtin_amdgcn_s_memtime() - pf_t0);
         return;
     }
@@ -737,14 +752,17 @@ __global__ __launch_bounds__(256, NPP_RENDER_OCC) void npp_render_kernel(KernelA
     const unsigned long long t3 = __builtin_amdgcn_s_memtime();
 #endif
     if (wd.w == FW) {
-        pass1_strips(L, wd, dst);   // pass 1
+        pass1_strips(L, wd, dst, mdw);   // pass 1
     } else {   // a window narrower than the frame (player_y < 42 under the axis swap): generic 4-pixel spans with padding columns
         for (int q = threadIdx.x; q < PF_SPANS; q += blockDim.x) {
             const int r = q / DW_PER_ROW, c0 = (q - r * DW_PER_ROW) * 4;
             bool slow;
             const uint32_t v = span_plain(L, wd, r, c0, slow);
             if (slow) L.queue[atomicAdd(&L.nq, 1)] = (unsigned short)q;
-            else dst[q] = v;
+            else {
+                dst[q] = v;
+                if (mdw) dst[q + mdw] = v;
+            }
         }
     }
     __syncthreads();
@@ -758,7 +776,10 @@ __global__ __launch_bounds__(256, NPP_RENDER_OCC) void npp_render_kernel(KernelA
         uint32_t v = pixel_full(L, wd, g_gray_cnt, r, c) << (8 * j);
         v |= __shfl_xor(v, 1, 64);
         v |= __shfl_xor(v, 2, 64);
-        if (j == 0) dst[q] = v;
+        if (j == 0) {
+            dst[q] = v;
+            if (mdw) dst[q + mdw] = v;
+        }
     }
     if (a.wg_cost && threadIdx.x == 0) a.wg_cost[env] = (uint32_t)(__builtin_amdgcn_s_memtime() - pf_t0);   // wavefront 0's view of the frame
 #ifdef NPP_RENDER_STAMPS
@@ -1711,8 +1732,8 @@ hipError_t launch_switch_states(const KernelArgs &a, float *d_out, hipStream_t s
     return hipGetLastError();
 }
 
-hipError_t launch_render(const KernelArgs &a, uint8_t *d_out, int centered, hipStream_t s) {
-    hipLaunchKernelGGL(npp_render_kernel, dim3(a.n), dim3(256), 0, s, a, d_out, centered);
+hipError_t launch_render(const KernelArgs &a, uint8_t *d_out, int centered, hipStream_t s, uint32_t stride, uint32_t mirror) {
+    hipLaunchKernelGGL(npp_render_kernel, dim3(a.n), dim3(256), 0, s, a, d_out, centered, stride, mirror);
     return hipGetLastError();
 }
 

@@ -67,6 +67,16 @@ _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_fr
              "mine_sdf_features", "reach_status")
 
 
+def _device_tensor(ptr, numel, dtype, device):
+    """A torch tensor over `numel` elements of device memory that the native handle owns (no copy, no ownership)."""
+    typestr = {torch.uint8: "|u1", torch.float32: "<f4"}[dtype]
+
+    class _Holder:
+        __cuda_array_interface__ = {"shape": (int(numel),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+    return torch.as_tensor(_Holder(), device=device)
+
+
 class OutputBlock:
     """All enabled outputs of one handle in ONE contiguous device allocation (each field 256-byte aligned), plus two pinned
     host mirrors.  One block means: one RCCL all_gather moves the whole packed observation of a rank (config 4), and one
@@ -290,7 +300,8 @@ class NppBatch:
     def step_many(self, actions, frame_skip=4):
         """actions: uint8 CUDA tensor [K, N].  K Gymnasium steps in one launch (open-loop sequences: checkpoint replay, fixed
         plans).  Returns (flags u8 [K, N], reward f32 [K, N], frames i16 [K, N]); observations of the last step land in
-        self.game_state etc.; with auto-reset, envs that terminate mid-sequence restart on the spot."""
+        self.game_state etc.; with auto-reset, envs that terminate mid-sequence restart on the spot.  Nothing is pushed onto
+        the frame stacks (NppVecEnvironment re-pads them from the observation after a checkpoint replay)."""
         assert actions.dtype == torch.uint8 and actions.is_cuda and actions.dim() == 2 and actions.shape[1] == self.n
         K = int(actions.shape[0])
         with self._ctx():   # allocations, the launch and the copies below are all ordered on the handle's stream
@@ -385,6 +396,55 @@ class NppBatch:
             m = np.ascontiguousarray(mask, dtype=np.uint8)
             assert len(m) == self.n
             nat.check(self.h, self.lib.npp_restore(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    # ---- frame stacking (include/npp_amd.h npp_set_frame_stack; the reference's FrameStackWrapper) ----------------
+    def set_frame_stack(self, visual_k=0, state_k=0, padding="zero"):
+        """Stack the last visual_k player_frames / state_k game_states of every env in rings of the handle (0 = off, else
+        1..12; padding "zero" or "repeat").  The rings start zeroed; frame_stack_push(reset_all=True) pads them properly."""
+        if padding not in ("zero", "repeat"):
+            raise ValueError("padding_type must be 'zero' or 'repeat'")
+        nat.check(self.h, self.lib.npp_set_frame_stack(self.h, int(visual_k), int(state_k), 1 if padding == "repeat" else 0))
+        self.stack_k = (int(visual_k), int(state_k))
+        self._stack_ring = [None, None]
+
+    def render_player_frame_stacked(self):
+        """player_frame of every env into the frame ring (the entry the next frame_stack_push completes)."""
+        nat.check(self.h, self.lib.npp_frame_stack_render(self.h))
+
+    def frame_stack_push(self, reset_bits=0, reset_all=False, terminal_stack=None):
+        """Append this step's entry (game_state from the block, the frame rendered before) to the rings and re-pad every env
+        that was reset: all of them (reset_all), or those whose flags & reset_bits is set.  terminal_stack: optional f32
+        CUDA tensor [N, state_k, 41] that receives each env's stack as of its terminal step (= the live stack if it was not
+        reset).  Call after join() (observation overlap)."""
+        t = self.out.t
+        if terminal_stack is not None:
+            assert terminal_stack.dtype == torch.float32 and terminal_stack.is_cuda and terminal_stack.is_contiguous()
+            assert terminal_stack.shape == (self.n, self.stack_k[1], 41)
+        nat.check(self.h, self.lib.npp_frame_stack_push(
+            self.h, C.c_void_p(t["game_state"].data_ptr()), C.c_void_p(t["terminal_state"].data_ptr()),
+            C.c_void_p(t["flags"].data_ptr()), int(reset_bits), 1 if reset_all else 0,
+            C.c_void_p(terminal_stack.data_ptr()) if terminal_stack is not None else None))
+
+    def frame_stack_views(self):
+        """(player_frame [N, visual_k, 84, 84, 1] u8, game_state [N, state_k, 41] f32) CUDA views of the current windows
+        (None where that key is not stacked): no copy; each env's K entries are contiguous, oldest first, envs are
+        2 K entries apart.  The rings are rewritten in place, so a view shows the window of the latest push."""
+        out = []
+        for which, (shape, dt, esz) in enumerate((((84, 84, 1), torch.uint8, 1), ((41,), torch.float32, 4))):
+            k = self.stack_k[which]
+            if not k:
+                out.append(None)
+                continue
+            base, off, stride = C.c_void_p(), C.c_int64(), C.c_int64()
+            nat.check(self.h, self.lib.npp_frame_stack_view(self.h, which, C.byref(base), C.byref(off), C.byref(stride)))
+            ring = self._stack_ring[which]
+            if ring is None or ring[0] != base.value:   # a torch tensor over the ring memory (owned by the handle)
+                ring = (base.value, _device_tensor(base.value, self.n * stride.value, dt, self.device))
+                self._stack_ring[which] = ring
+            e = int(np.prod(shape))
+            out.append(torch.as_strided(ring[1], (self.n, k) + shape, (stride.value, e) + tuple(
+                int(np.prod(shape[i + 1:])) for i in range(len(shape))), off.value))
+        return tuple(out)
 
     def to_host(self, names=None):
         """{name: numpy array} of the enabled outputs through ONE async device-to-host copy of the output block into pinned

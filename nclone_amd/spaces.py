@@ -52,9 +52,22 @@ def action_space():
     return Discrete(6)
 
 
-def observation_space(visual=False, spatial_context=False, switch_states=False, reachability=False):
+def check_frame_stack(visual_stack_size=4, state_stack_size=4, padding_type="zero"):
+    """The reference's argument checks, messages included (frame_stack_wrapper.py:116-121); both sizes are checked whether or
+    not that key is stacked, as there."""
+    if visual_stack_size < 1 or visual_stack_size > 12:
+        raise ValueError("visual_stack_size must be between 1 and 12")
+    if state_stack_size < 1 or state_stack_size > 12:
+        raise ValueError("state_stack_size must be between 1 and 12")
+    if padding_type not in ["zero", "repeat"]:
+        raise ValueError("padding_type must be 'zero' or 'repeat'")
+
+
+def observation_space(visual=False, spatial_context=False, switch_states=False, reachability=False, visual_stack=0, state_stack=0):
+    """visual_stack / state_stack: K > 0 stacks player_frame to (K, 84, 84, 1) / game_state to (K, 41) with the bounds of the
+    reference's stacked space (frame_stack_wrapper.py:139-181); global_view and the other keys pass through."""
     spaces = {
-        "game_state": Box(-1.0, 1.0, (41,), np.float32),
+        "game_state": Box(-1.0, 1.0, (state_stack, 41) if state_stack else (41,), np.float32),
         "action_mask": Box(0, 1, (6,), np.int8),
         "entity_positions": Box(0.0, 1.0, (6,), np.float32),
     }
@@ -63,7 +76,7 @@ def observation_space(visual=False, spatial_context=False, switch_states=False, 
     if switch_states:
         spaces["switch_states"] = Box(0.0, 1.0, (25,), np.float32)
     if visual:
-        spaces["player_frame"] = Box(0, 255, (84, 84, 1), np.uint8)
+        spaces["player_frame"] = Box(0, 255, (visual_stack, 84, 84, 1) if visual_stack else (84, 84, 1), np.uint8)
         spaces["global_view"] = Box(0, 255, (176, 100, 1), np.uint8)   # RENDERED_VIEW_HEIGHT x WIDTH (constants.py:18-19)
     if reachability:   # npp_environment.py observation space: reachability_features (38), mine_sdf_features (3)
         spaces["reachability_features"] = Box(0.0, 1.0, (38,), np.float32)   # the reference declares [0, 1] (npp_environment.py:236)

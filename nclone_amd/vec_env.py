@@ -47,23 +47,44 @@ class NppVecEnvironment:
                 npp_environment.py:1238-1256) or a number of frames for every env (10000 = the reference's fallback)
     The step's `reward` carries only the sparse terminal constants -- reward parity: NONE (the reference's PBRS reward
     calculator is out of scope); compute the reward from the observations / info flags.
+
+    Frame stacking (the reference's EnvironmentConfig.frame_stack + FrameStackWrapper, frame_stack_wrapper.py):
+    enable_visual_frame_stacking / visual_stack_size, enable_state_stacking / state_stack_size, frame_stack_padding_type
+    ("zero" or "repeat") -- the reference config's names (config.py:22-60).  With it, obs["player_frame"] is [N, K, 84, 84, 1]
+    and obs["game_state"] [N, K, 41], oldest first; every other key is unchanged.  The stack of an env is re-padded (K - 1
+    padding entries, then the new observation) at reset(), at reset(options={"checkpoint": ...}) from the restored / replayed
+    observation, and when the kernel auto-resets it.  Visual stacking needs enable_visual_observations (otherwise it is
+    ignored, as in the reference).  The flags are taken as given, as create_evaluation_env passes them: the reference's
+    create_training_env omits enable_visual_stacking, so the wrapper's default (on) applies there -- pass it explicitly.
+    Sizes outside 1..12 and other paddings raise ValueError with the reference's messages.  Augmentation is not provided.
+    With state stacking, info["terminal_game_state_stack"] [N, K, 41] is, for every env reset in this step, the stack it
+    would have shown at its terminal step (the previous window's last K - 1 entries, then terminal_state), else the live stack.
+    output="torch": the stacked tensors are views of device rings (no copy): each env's K entries are contiguous, but envs are
+    2 K entries apart, and the rings are rewritten by the next step.  output="numpy": contiguous host arrays.
     """
 
     metadata = {"render_modes": []}
 
     def __init__(self, levels, num_envs, level_ids=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", output="torch", autoreset=True, enable_spatial_context=False,
-                 enable_switch_states=False, fast_reset=True, stream=None, enable_reachability=False, obs_overlap=0):
+                 enable_switch_states=False, fast_reset=True, stream=None, enable_reachability=False, obs_overlap=0,
+                 enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
+                 frame_stack_padding_type="zero"):
         assert output in ("torch", "numpy")
+        spaces.check_frame_stack(visual_stack_size, state_stack_size, frame_stack_padding_type)
         self.num_envs = int(num_envs)
         self.frame_skip = int(frame_skip)
         self.output = output
         self.enable_visual_observations = bool(enable_visual_observations)
+        # stack sizes, 0 = not stacked (visual stacking applies only when player_frame is observed, frame_stack_wrapper.py:190)
+        self._vk = int(visual_stack_size) if enable_visual_frame_stacking and self.enable_visual_observations else 0
+        self._sk = int(state_stack_size) if enable_state_stacking else 0
         self.single_action_space = spaces.action_space()
         self.single_observation_space = spaces.observation_space(self.enable_visual_observations,
                                                                  spatial_context=bool(enable_spatial_context),
                                                                  switch_states=bool(enable_switch_states),
-                                                                 reachability=bool(enable_reachability))
+                                                                 reachability=bool(enable_reachability),
+                                                                 visual_stack=self._vk, state_stack=self._sk)
         self.action_space = self.single_action_space
         self.observation_space = self.single_observation_space
         outputs = ["positions"]
@@ -71,8 +92,8 @@ class NppVecEnvironment:
             outputs.append("spatial_context")
         if enable_switch_states:
             outputs.append("switch_states")
-        if self.enable_visual_observations:
-            outputs += ["player_frame", "global_view"]
+        if self.enable_visual_observations:   # (a stacked player_frame lives in the handle's ring, not in the output block)
+            outputs += ["global_view"] if self._vk else ["player_frame", "global_view"]
         if enable_reachability:   # reachability_features + mine_sdf_features (npp_environment.py observation keys)
             outputs += ["reachability_features", "mine_sdf_features"]
         # same-level resets are Simulator.fast_reset in the reference's env (npp_environment.py:541-557): the default here
@@ -95,10 +116,18 @@ class NppVecEnvironment:
             self._actions = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
         self._reset_bits = 11 if autoreset else 0
         self._obs_names = ["game_state", "action_mask", "entity_pos", "positions", "flags"] + outputs[1:]
+        self._term_stack = None
+        if self._vk or self._sk:
+            self._b.set_frame_stack(self._vk, self._sk, frame_stack_padding_type)
+            if self._sk:
+                with self._b._ctx():
+                    self._term_stack = torch.zeros((self.num_envs, self._sk, 41), dtype=torch.float32, device=self._b.device)
+            self._host_stack = {}   # name -> [pinned buffer, pinned buffer, next]: host copies alternate like the output block's
 
     # -- helpers ------------------------------------------------------------------------------------------------
-    def _produce(self):
-        """Launch the secondary observation kernels (frames, switch_states) on the handle's stream."""
+    def _produce(self, reset_all=False):
+        """Launch the secondary observation kernels (frames, switch_states) on the handle's stream, then (frame stacking)
+        push this observation onto the stacks: re-padding every env when reset_all, else the envs the kernel auto-reset."""
         b = self._b
         fused = "switch_states" in b.out.t and "reachability_features" in b.out.t   # one launch writes both
         if "switch_states" in b.out.t and not fused:
@@ -106,9 +135,42 @@ class NppVecEnvironment:
         if "player_frame" in b.out.t:
             b.render_player_frame()
             b.render_global_view()
+        elif self._vk:
+            b.render_player_frame_stacked()
+            b.render_global_view()
         if "reachability_features" in b.out.t:
             b.reachability(with_switch_states=fused)
         b.join()   # (obs_overlap) the handle's stream waits for the kernels that went to the second stream
+        if self._vk or self._sk:
+            b.frame_stack_push(self._reset_bits, reset_all, None if reset_all else self._term_stack)
+
+    def _stacked(self, src, with_terminal=False):
+        """src with the stacked windows in place of player_frame / game_state (+ terminal_game_state_stack).  Device views for
+        output="torch"; for output="numpy" the copies into pinned memory are only enqueued here -- the caller's to_host()
+        synchronises the stream."""
+        if not (self._vk or self._sk):
+            return src
+        pf, gs = self._b.frame_stack_views()
+        stk = {}
+        if pf is not None:
+            stk["player_frame"] = pf
+        if gs is not None:
+            stk["game_state"] = gs
+            if with_terminal:
+                stk["terminal_game_state_stack"] = self._term_stack
+        if self.output == "numpy":
+            with self._b._ctx():
+                for k, t in stk.items():
+                    slot = self._host_stack.get(k)
+                    if slot is None:
+                        slot = self._host_stack[k] = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for _ in range(2)] + [0]
+                    host = slot[slot[2]]
+                    slot[2] ^= 1
+                    host.copy_(t, non_blocking=True)
+                    stk[k] = host.numpy()
+        out = dict(src)
+        out.update(stk)
+        return out
 
     def _obs(self, src):
         """src: {name: tensor-or-array} (device tensors, or the host views of ONE staged copy)."""
@@ -172,10 +234,13 @@ class NppVecEnvironment:
                 else:
                     info = {"checkpoint_replay": False, "replay_frames": 0}
         self._b.observe()
-        self._produce()
+        self._produce(reset_all=True)
         if self.output == "torch":
-            return self._obs(self._b.out.t), info
-        return self._obs(self._b.to_host(self._obs_names)), info
+            return self._obs(self._stacked(self._b.out.t)), info
+        stk = self._stacked({})
+        src = self._b.to_host(self._obs_names)
+        src.update(stk)
+        return self._obs(src), info
 
     def snapshot(self):
         """Save the state of every env on the device (one slot); reset(options={"checkpoint": "snapshot"}) restores it."""
@@ -202,9 +267,11 @@ class NppVecEnvironment:
         output="numpy": ONE async copy of the output block into pinned memory + one synchronisation."""
         b = self._b
         if self.output == "torch":
-            src = b.out.t
+            src = self._stacked(b.out.t, with_terminal=True)
         else:
+            stk = self._stacked({}, with_terminal=True)   # (copies enqueued before to_host's synchronisation)
             src = b.to_host(self._obs_names + ["reward", "frames", "terminal_state"])
+            src.update(stk)
         flags = src["flags"]
         info = {
             "player_won": (flags & 1) != 0,
@@ -215,6 +282,8 @@ class NppVecEnvironment:
             "terminal_observation": src["terminal_state"],
             "frame_skip_stats": {"skip_value": self.frame_skip},
         }
+        if "terminal_game_state_stack" in src:
+            info["terminal_game_state_stack"] = src["terminal_game_state_stack"]
         return self._obs(src), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
@@ -233,11 +302,13 @@ class NppVecEnvironment:
 class NppEnvironment:
     """Single-environment adapter with the reference's exact call signatures (base_environment.py:483,
     npp_environment.py:504).  One GPU lane group does the work of one Python simulator; use NppVecEnvironment for
-    throughput."""
+    throughput.  Frame stacking takes NppVecEnvironment's arguments; stacked keys come without the batch dimension
+    (player_frame (K, 84, 84, 1), game_state (K, 41))."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
-                 enable_reachability=False):
+                 enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
+                 state_stack_size=4, frame_stack_padding_type="zero"):
         if map_data is None:
             if custom_map_path is None:
                 raise ValueError("NppEnvironment needs map_data or custom_map_path")
@@ -247,7 +318,10 @@ class NppEnvironment:
                                     enable_visual_observations=enable_visual_observations,
                                     truncation_limit=truncation_limit, output="numpy", autoreset=False,
                                     fast_reset=fast_reset, enable_spatial_context=enable_spatial_context,
-                                    enable_switch_states=enable_switch_states, enable_reachability=enable_reachability)
+                                    enable_switch_states=enable_switch_states, enable_reachability=enable_reachability,
+                                    enable_visual_frame_stacking=enable_visual_frame_stacking, visual_stack_size=visual_stack_size,
+                                    enable_state_stacking=enable_state_stacking, state_stack_size=state_stack_size,
+                                    frame_stack_padding_type=frame_stack_padding_type)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
