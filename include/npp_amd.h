@@ -297,7 +297,9 @@ int npp_entity_checksum(npp_handle h, int env0, int count, double *out);
 /* Go-Explore style checkpoints (state_checkpoint.py / action_replayer.py in the reference restore a state by
  * reset + replaying the action sequence and validating |dpos| < 0.01 px).  Here a checkpoint is a raw copy of the
  * SoA state of ALL envs kept on the device (one slot per handle): npp_snapshot stores it, npp_restore puts it back for
- * the envs whose mask byte is non-zero (NULL = all).  The env -> level assignment must not have changed in between. */
+ * the envs whose mask byte is non-zero (NULL = all).  The env -> level assignment must not have changed in between (draws of the
+ * level pool are part of the state: the snapshot holds every env's level, draw count and truncation limit, and once a pool has been
+ * on since npp_load_levels npp_restore puts them back together with the state). */
 int npp_snapshot(npp_handle h);
 int npp_restore(npp_handle h, const uint8_t *env_mask);
 
@@ -334,6 +336,43 @@ int npp_frame_stack_render(npp_handle h);
 int npp_frame_stack_push(npp_handle h, const float *d_game_state, const float *d_terminal_state, const uint8_t *d_flags,
                          int reset_bits, int reset_all, float *d_terminal_stack);
 int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, int64_t *batch_stride);
+
+/* Level pool: a new level for every episode (EnvMapLoader.load_map, env_map_loader.py:111-208, which draws a category by weight
+ * (_select_category, :210-234; set_curriculum_weights, :312) and a map inside it; npp_environment.py:516-557 fast-resets only when
+ * the same map comes up again).  The pool is the loaded level set plus one weight per level.
+ * npp_set_level_pool: weights f64[n_levels] (n_levels == npp_num_levels), all finite and >= 0, not all zero; weights == NULL turns the
+ *   pool off (the default: every env keeps its level, byte-identical to a handle that never had a pool).  May be called again between
+ *   steps (curriculum updates): the next draw uses the new weights.  NaN, negative or infinite weights, an all-zero vector and a wrong
+ *   length return NPP_ERR_INVALID.  A call with the pool's current seed keeps the per-env draw counts (a curriculum update); turning
+ *   the pool on or changing the seed restarts them at 0.  Refused while an entity is repositioned
+ *   (npp_set_entity_pos), which is refused in turn while the pool is on.  npp_load_levels turns the pool off.
+ * With the pool on, npp_step with NPP_FLAG_AUTORESET draws for every env whose flags show won, dead or truncated, after the step
+ *   kernel (and after joining an observation overlap): an env that drew ANOTHER level is assigned it exactly as by npp_assign_levels
+ *   (Simulator.reset with fresh entities, reachability cache row and per-episode dictionary dropped, dynamic truncation limit of the
+ *   new level) and its observation rows of `out` (game_state, action_mask, entity_pos, spatial_context, positions) are rewritten with
+ *   the new level's spawn observation; flags, reward, frames and terminal_state keep describing the episode that ended.  An env that
+ *   drew its own level keeps the step kernel's auto-reset (fast_reset under NPP_FLAG_FAST_RESET).  Observation kernels called after
+ *   npp_step see the new levels.  npp_step_many and npp_tick never draw (their in-kernel resets stay on the current level).
+ * npp_draw_levels: every env whose mask byte is non-zero (NULL = all) draws now, with the same consequences for envs that change
+ *   level; the others are not touched (NppVecEnvironment.reset draws this way before its reset).  NPP_ERR_STATE without a pool.
+ * The draw of env e with per-env draw count c (u32, starts at 0, +1 per draw; independent of the 13-bit episode counter):
+ *     mix(z)  = z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+ *     u       = mix(mix(((uint64_t)e << 32) | c) ^ seed)                      (splitmix64 rounds, arithmetic mod 2^64)
+ *     t       = (double)(u >> 11) * 2^-53 * cdf[n - 1]                        (cdf[l] = w[0] + ... + w[l], summed in f64 in index order)
+ *     level   = the number of l with cdf[l] <= t, or the last level of non-zero weight if that is n
+ *   so level l comes up with probability w[l] / sum(w), weight-0 levels never, and the draw depends on nothing but (seed, e, c):
+ *   not on launch geometry, build variant, observation overlap or stream.  The reference's own draws (Python `random`) are not
+ *   reproduced.  The draw counts and levels are part of npp_snapshot / npp_restore.
+ * npp_get_env_levels: i32[n_envs], the level every env plays now (synchronises).
+ * npp_env_level_view: *d_levels = the device array i32[n_envs] behind it (valid while the handle lives; the draws rewrite it in
+ *   stream order, so a consumer on the handle's stream sees the levels of the step it follows).
+ * npp_level_pool_draw_host (host-only): the same draw for `count` (env, count) pairs, with the same weight checks. */
+int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64_t seed);
+int npp_draw_levels(npp_handle h, const uint8_t *env_mask);
+int npp_get_env_levels(npp_handle h, int32_t *host_out);
+int npp_env_level_view(npp_handle h, const int32_t **d_levels);
+int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed, const int32_t *envs, const uint32_t *counts, int count,
+                             int32_t *out);
 
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);

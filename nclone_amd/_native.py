@@ -31,6 +31,7 @@ EXPORTS = [
     "npp_reachability", "npp_reachability_ex", "npp_reach_compile", "npp_reach_features_host", "npp_reach_compile_miss", "npp_reach_rollout_host", "npp_set_dynamic_truncation", "npp_level_truncation_limit",
     "npp_set_obs_overlap", "npp_set_obs_overlap_parts", "npp_join",
     "npp_set_frame_stack", "npp_frame_stack_render", "npp_frame_stack_push", "npp_frame_stack_view",
+    "npp_set_level_pool", "npp_draw_levels", "npp_get_env_levels", "npp_env_level_view", "npp_level_pool_draw_host",
 ]
 
 
@@ -124,6 +125,12 @@ def lib():
     L.npp_frame_stack_render.argtypes = [H]
     L.npp_frame_stack_push.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.npp_frame_stack_view.argtypes = [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.npp_set_level_pool.argtypes = [H, C.POINTER(C.c_double), C.c_int, C.c_uint64]
+    L.npp_draw_levels.argtypes = [H, C.POINTER(C.c_uint8)]
+    L.npp_get_env_levels.argtypes = [H, C.POINTER(C.c_int32)]
+    L.npp_env_level_view.argtypes = [H, C.POINTER(C.c_void_p)]
+    L.npp_level_pool_draw_host.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int,
+                                           C.POINTER(C.c_int32)]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

@@ -85,8 +85,10 @@ class NppAsyncVecEnvironment:
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
-                 output="numpy", autoreset=True, fast_reset=True):
+                 output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None):
         assert output in ("torch", "numpy")
+        if level_weights is not None or level_seed is not None:
+            raise NotImplementedError("NppAsyncVecEnvironment has no level pool (level_weights): use NppVecEnvironment")
         self.num_envs, self.frame_skip, self.output = int(num_envs), int(frame_skip), output
         self.ab = AsyncBatches(num_envs, n_streams, device=device, autoreset=autoreset, outputs=("positions",),
                                fast_reset=fast_reset)

@@ -110,6 +110,21 @@ struct npp_handle_s {
     int fs_vhead = 0, fs_shead = 0;            // ring position of the newest entry
     uint8_t *d_fs_frames = nullptr;            // [n][2 fs_vk][84 * 84]
     float *d_fs_state = nullptr;               // [n][2 fs_sk][41]
+    // level pool (npp_set_level_pool, npp_pool.hip): with it on, the device changes env_level / d_trunc after a step, and the host
+    // mirrors env_level / trunc are read back lazily (pull_levels) where a host path needs them
+    bool pool_on = false;
+    bool pool_ever = false;     // a pool was on since npp_load_levels: levels change without npp_assign_levels, snapshots carry them
+    bool pool_dirty = false;    // the device may have drawn since env_level / trunc were read back
+    uint64_t pool_seed = 0;
+    int pool_last = 0;          // the last level of non-zero weight
+    std::vector<double> pool_w;
+    double *d_pool_cdf = nullptr;        // [n_levels]
+    uint32_t *d_pool_count = nullptr;    // [n] draw counts
+    uint8_t *d_pool_flags = nullptr;     // [n] step flags when the caller asked for none
+    uint8_t *d_pool_changed = nullptr;   // [n] envs that drew another level (device reset / observe mask)
+    int32_t *d_level_trunc = nullptr;    // [n_levels] dynamic truncation limit per level (pool + dynamic truncation)
+    int32_t *s_level = nullptr, *s_trunc = nullptr;   // snapshot of env_level / d_trunc / d_pool_count
+    uint32_t *s_count = nullptr;
     LevelHdr *d_hdr = nullptr;
     int n_words_max = 1;
     uint32_t hot_max = 0;      // largest staged-level size over the loaded set
@@ -293,7 +308,10 @@ struct DeviceGuard {
 // Launch geometry (DESIGN.md "lanes per environment"): G lanes cooperate on one env.  The chip has 256 CUs x 4 SIMDs;
 // the path is a latency-bound fp64 dependency chain, so the grid is sized to put about two wavefronts on every SIMD
 // (one hides the other's latency) and the spare lanes of each wavefront are spent on segment-level parallelism.
+int pull_levels(npp_handle h);
+
 void plan_geometry(npp_handle h, bool keep_tuning = false) {
+    (void)pull_levels(h);   // (a failure leaves the mirror as it was and is reported by the next call that syncs)
     const int zoo_before = h->zoo_active;
     int g = h->lanes_per_env;
     if (const char *ev = std::getenv("NPP_LANES_PER_ENV")) g = std::atoi(ev);
@@ -314,6 +332,8 @@ void plan_geometry(npp_handle h, bool keep_tuning = false) {
     h->zoo_active = h->n_ovr > 0 ? 1 : 0;   // repositioned switches / doors are handled by the zoo kernel's merged walk
     if (h->d_zoo)
         for (int e = 0; e < h->n && !h->zoo_active; e++) h->zoo_active = h->levels[h->env_level[e]].has_zoo ? 1 : 0;
+    if (h->pool_on)   // (level pool) any level an env may draw
+        for (size_t l = 0; l < h->pool_w.size() && !h->zoo_active; l++) h->zoo_active = h->pool_w[l] > 0.0 && h->levels[l].has_zoo ? 1 : 0;
     const int zw = h->zoo_active ? h->zoo_words : 0;
     // LDS plan: staged level + entity words + observation staging (+ zoo blocks) must fit the per-workgroup budget
     for (;;) {
@@ -340,7 +360,7 @@ void plan_geometry(npp_handle h, bool keep_tuning = false) {
     }
     // can every workgroup stage ONE level?  (the host owns the env -> level assignment)
     int epb = (64 / g) * wpb;
-    int ok = !h->hdrs.empty();
+    int ok = !h->hdrs.empty() && !h->pool_on;   // (level pool: levels change on the device, workgroups no longer share one)
     for (int b0 = 0; b0 < h->n && ok; b0 += epb) {
         int lvl = h->env_level[b0];
         if (h->hdrs[lvl].hot_bytes > h->lds_hot_cap) ok = 0;
@@ -496,16 +516,40 @@ int ensure_reach(npp_handle h) {
     return rc;
 }
 
+// level pool: read the device's env_level / d_trunc back into the host mirrors (synchronises; only after a draw)
+int pull_levels(npp_handle h) {
+    if (!h->pool_dirty) return NPP_OK;
+    HIP_TRY(h, join_streams(h));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(h->env_level.data(), h->d_env_level, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(h->trunc.data(), h->d_trunc, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost));
+    h->pool_dirty = false;
+    return NPP_OK;
+}
+
+void level_trunc_table(npp_handle h) {
+    if (h->level_trunc.size() == h->levels.size()) return;
+    h->level_trunc.resize(h->levels.size());
+    for (size_t i = 0; i < h->levels.size(); i++) {
+        ReachBuilt R;
+        build_reach(h->levels[i], R);
+        h->level_trunc[i] = truncation_limit_for_area(R.spawn_area);
+    }
+}
+
+// level pool + dynamic truncation: the per-level limits on the device, for the draw kernel
+int upload_level_trunc(npp_handle h) {
+    level_trunc_table(h);
+    if (!h->d_level_trunc) HIP_TRY(h, hipMalloc((void **)&h->d_level_trunc, sizeof(int32_t) * h->levels.size()));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(h->d_level_trunc, h->level_trunc.data(), sizeof(int32_t) * h->levels.size(), hipMemcpyHostToDevice));
+    return NPP_OK;
+}
+
 // envs selected by mask (NULL = all) take their level's dynamic limit
 int apply_dynamic_truncation(npp_handle h, const uint8_t *mask) {
-    if (h->level_trunc.size() != h->levels.size()) {
-        h->level_trunc.resize(h->levels.size());
-        for (size_t i = 0; i < h->levels.size(); i++) {
-            ReachBuilt R;
-            build_reach(h->levels[i], R);
-            h->level_trunc[i] = truncation_limit_for_area(R.spawn_area);
-        }
-    }
+    if (int rc = pull_levels(h)) return rc;
+    level_trunc_table(h);
     for (int e = 0; e < h->n; e++)
         if (!mask || mask[e]) h->trunc[e] = h->level_trunc[h->env_level[e]];
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -529,6 +573,45 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
     }
     HIP_TRY(h, launch_reset(a, h->stream));
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));  // env_mask is caller memory: finish the copy
+    return NPP_OK;
+}
+
+// Level pool: the envs with (flags[e] & bits) draw a level (npp_pool.hip); those that drew another one are reset as after
+// npp_assign_levels -- fresh Simulator.reset, reachability cache row and per-episode dictionary dropped -- by the existing kernels
+// under the draw's device mask, and, when `out` is given, their observation rows are rewritten by a masked observe launch.
+// The caller has joined the streams.
+int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_out *out) {
+    PoolArgs p;
+    p.n = h->n;
+    p.flags = d_flags;
+    p.bits = bits;
+    p.cdf = h->d_pool_cdf;
+    p.n_levels = (int)h->levels.size();
+    p.last = h->pool_last;
+    p.seed = h->pool_seed;
+    p.count = h->d_pool_count;
+    p.env_level = h->d_env_level;
+    p.trunc = h->d_trunc;
+    p.level_trunc = h->dyn_trunc ? h->d_level_trunc : nullptr;
+    p.changed = h->d_pool_changed;
+    HIP_TRY(h, launch_pool_draw(p, h->stream));
+    h->pool_dirty = true;
+    KernelArgs a = base_args(h);
+    a.reset_mask = h->d_pool_changed;
+    a.reset_fresh = 1;
+    a.fast_reset = 0;   // (base_args carries the auto-reset's NPP_FLAG_FAST_RESET) a new level is a Simulator.reset
+    HIP_TRY(h, launch_reset(a, h->stream));
+    if (h->d_rkey) HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, h->d_rkey, h->d_rcache, h->rmiss, h->stream));
+    if (out) {
+        KernelArgs o = base_args(h);
+        o.n_ticks = 0;
+        o.mode = 0;
+        o.autoreset = 0;
+        fill_out(o, out);
+        o.out.flags = nullptr; o.out.reward = nullptr; o.out.frames = nullptr; o.out.terminal_state = nullptr; o.out.work = nullptr;
+        o.obs_mask = h->d_pool_changed;
+        HIP_TRY(h, launch_step(o, h->stream));
+    }
     return NPP_OK;
 }
 
@@ -558,7 +641,9 @@ int npp_create(int n_envs, int device_id, unsigned flags, npp_handle *out) {
     hipError_t e4 = hipMalloc((void **)&h->d_trunc, sizeof(int32_t) * N);
     hipError_t e5 = hipMalloc((void **)&h->d_mask, N);
     hipError_t e6 = hipMalloc((void **)&h->d_sc_cache, sizeof(float) * 48 * N);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess || e6 != hipSuccess) {
+    hipError_t e7 = hipMalloc((void **)&h->d_pool_count, sizeof(uint32_t) * N);
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess || e6 != hipSuccess ||
+        e7 != hipSuccess) {
         npp_destroy(h);
         return fail(nullptr, NPP_ERR_HIP, "npp_create: hipMalloc failed");
     }
@@ -566,6 +651,7 @@ int npp_create(int n_envs, int device_id, unsigned flags, npp_handle *out) {
     h->trunc.assign(N, 10000);  // MAX_TIME_IN_FRAMES fallback (gym_environment/constants.py:8)
     hipMemcpy(h->d_trunc, h->trunc.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice);
     hipMemset(h->d_env_level, 0, sizeof(int32_t) * N);
+    hipMemset(h->d_pool_count, 0, sizeof(uint32_t) * N);
     *out = h;
     return NPP_OK;
 }
@@ -593,6 +679,8 @@ int npp_destroy(npp_handle h) {
             if (h->side_ev[k][p]) hipEventDestroy(h->side_ev[k][p]);
     hipFree(h->d_phase);
     hipFree(h->d_fs_frames); hipFree(h->d_fs_state);
+    hipFree(h->d_pool_cdf); hipFree(h->d_pool_count); hipFree(h->d_pool_flags); hipFree(h->d_pool_changed); hipFree(h->d_level_trunc);
+    hipFree(h->s_level); hipFree(h->s_count); hipFree(h->s_trunc);
     free_reach(h);
     hipFree(h->s_f64); hipFree(h->s_u32); hipFree(h->s_ent); hipFree(h->s_sc); hipFree(h->d_zoo); hipFree(h->s_zoo);
     delete h;
@@ -629,6 +717,9 @@ int npp_snapshot(npp_handle h) {
         HIP_TRY(h, hipMalloc((void **)&h->s_f64, sizeof(double) * NF64 * N));
         HIP_TRY(h, hipMalloc((void **)&h->s_u32, sizeof(uint32_t) * NU32 * N));
         HIP_TRY(h, hipMalloc((void **)&h->s_sc, sizeof(float) * 48 * N));
+        HIP_TRY(h, hipMalloc((void **)&h->s_level, sizeof(int32_t) * N));
+        HIP_TRY(h, hipMalloc((void **)&h->s_count, sizeof(uint32_t) * N));
+        HIP_TRY(h, hipMalloc((void **)&h->s_trunc, sizeof(int32_t) * N));
     }
     if (h->s_words != h->n_words_max) {
         hipFree(h->s_ent);
@@ -640,6 +731,10 @@ int npp_snapshot(npp_handle h) {
     HIP_TRY(h, hipMemcpyAsync(h->s_u32, h->d_u32, sizeof(uint32_t) * NU32 * N, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->s_ent, h->d_ent, sizeof(uint32_t) * (size_t)h->n_words_max * N, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->s_sc, h->d_sc_cache, sizeof(float) * 48 * N, hipMemcpyDeviceToDevice, h->stream));
+    // (level pool) each env's level, draw count and truncation limit go with its state
+    HIP_TRY(h, hipMemcpyAsync(h->s_level, h->d_env_level, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->s_count, h->d_pool_count, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->s_trunc, h->d_trunc, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, h->stream));
     if (h->d_zoo) {
         if (!h->s_zoo) HIP_TRY(h, hipMalloc((void **)&h->s_zoo, sizeof(double) * (size_t)h->zoo_words * N));
         HIP_TRY(h, hipMemcpyAsync(h->s_zoo, h->d_zoo, sizeof(double) * (size_t)h->zoo_words * N, hipMemcpyDeviceToDevice, h->stream));
@@ -672,6 +767,11 @@ int npp_restore(npp_handle h, const uint8_t *env_mask) {
     HIP_TRY(h, launch_restore(a, h->s_f64, h->s_u32, h->s_ent, h->s_sc, h->d_zoo ? h->s_zoo : nullptr, h->stream));
     if (h->d_rkey)   // no cache in the snapshot (taken before the first npp_reachability): the restored envs start without one
         HIP_TRY(h, launch_reach_restore(a, h->s_reach ? h->s_rkey : nullptr, h->s_rcache, h->d_rkey, h->d_rcache, h->rmiss, h->stream));
+    if (h->pool_ever) {   // the pool changed levels since npp_load_levels: the snapshot's levels come back with the state
+        HIP_TRY(h, launch_pool_restore(h->n, a.reset_mask, h->s_level, h->s_count, h->s_trunc, h->d_env_level, h->d_pool_count, h->d_trunc,
+                                       h->stream));
+        h->pool_dirty = true;
+    }
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));
     // the restored zoo blocks carry the repositioning flags / coordinates of the snapshot (head words 3..7): the host's
     // view of them (which decides whether the zoo kernels run) is restored with them
@@ -681,6 +781,8 @@ int npp_restore(npp_handle h, const uint8_t *env_mask) {
         h->n_ovr = 0;
         for (int e = 0; e < h->n; e++) h->n_ovr += h->ovr[e] != 0;
         plan_geometry(h, true);   // restoring a checkpoint every few hundred steps must not keep the autotuner in its warm-up
+    } else if (h->pool_ever) {
+        plan_geometry(h, true);
     }
     return NPP_OK;
 }
@@ -808,6 +910,12 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     hipFree(h->d_ent); h->d_ent = nullptr;
     hipFree(h->d_zoo); h->d_zoo = nullptr;
     hipFree(h->s_zoo); h->s_zoo = nullptr;
+    // a new level set turns the level pool off (its weights were per level of the old set); draw counts restart
+    hipFree(h->d_pool_cdf); h->d_pool_cdf = nullptr;
+    hipFree(h->d_level_trunc); h->d_level_trunc = nullptr;
+    h->pool_on = h->pool_ever = h->pool_dirty = false;
+    h->pool_w.clear();
+    HIP_TRY(h, hipMemset(h->d_pool_count, 0, sizeof(uint32_t) * (size_t)h->n));
     (void)any_zoo;
     zoo_block_plan(lv, zoo_doors, zoo_movers);
     for (int i = 0; i < n_levels; i++)   // round-1 fault: a block sized over zoo levels only was overrun
@@ -848,6 +956,7 @@ int npp_assign_levels(npp_handle h, const int32_t *env_ids, const int32_t *level
     if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_assign_levels: no levels loaded");
     if (!env_ids && n != h->n) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: env_ids == NULL needs n == n_envs");
     ON_DEVICE_JOINED(h);
+    if (int rc = pull_levels(h)) return rc;   // (level pool) the whole mirror is uploaded below
     std::vector<uint8_t> mask(h->n, 0);
     for (int i = 0; i < n; i++) {   // validate everything before touching the assignment: an error must leave host and device in step
         int e = env_ids ? env_ids[i] : i;
@@ -902,7 +1011,73 @@ int npp_set_dynamic_truncation(npp_handle h, int enable) {
     h->dyn_trunc = enable != 0;
     if (!h->dyn_trunc || h->levels.empty()) return NPP_OK;
     ON_DEVICE_JOINED(h);
+    if (h->pool_on)
+        if (int rc = upload_level_trunc(h)) return rc;
     return apply_dynamic_truncation(h, nullptr);
+}
+
+int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64_t seed) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!weights) {   // off: every env keeps the level it plays now
+        if (!h->pool_on) return NPP_OK;
+        ON_DEVICE_JOINED(h);
+        if (int rc = pull_levels(h)) return rc;
+        h->pool_on = false;
+        plan_geometry(h);
+        return NPP_OK;
+    }
+    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: no levels loaded");
+    std::vector<double> cdf;
+    int last = 0;
+    std::string err;
+    if (!pool_cdf(weights, n_levels, (int)h->levels.size(), cdf, last, err)) return fail(h, NPP_ERR_INVALID, "npp_set_level_pool: " + err);
+    if (h->n_ovr) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: an exit switch / door is repositioned (npp_set_entity_pos)");
+    ON_DEVICE_JOINED(h);
+    const size_t N = (size_t)h->n;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the previous CDF may still be read by queued draws
+    if (!h->d_pool_cdf) HIP_TRY(h, hipMalloc((void **)&h->d_pool_cdf, sizeof(double) * cdf.size()));
+    if (!h->d_pool_changed) {
+        HIP_TRY(h, hipMalloc((void **)&h->d_pool_changed, N));
+        HIP_TRY(h, hipMalloc((void **)&h->d_pool_flags, N));
+        HIP_TRY(h, hipMemset(h->d_pool_flags, 0, N));
+    }
+    HIP_TRY(h, hipMemcpy(h->d_pool_cdf, cdf.data(), sizeof(double) * cdf.size(), hipMemcpyHostToDevice));
+    if (!h->pool_on || seed != h->pool_seed) HIP_TRY(h, hipMemset(h->d_pool_count, 0, sizeof(uint32_t) * N));   // a new stream of draws
+    if (h->dyn_trunc)
+        if (int rc = upload_level_trunc(h)) return rc;
+    const bool was_on = h->pool_on;
+    h->pool_w.assign(weights, weights + n_levels);
+    h->pool_seed = seed;
+    h->pool_last = last;
+    h->pool_on = h->pool_ever = true;
+    // the step-variant autotuner decides once for the pool: a weight update keeps its decision unless it switches the zoo kernels
+    plan_geometry(h, was_on);
+    return NPP_OK;
+}
+
+int npp_draw_levels(npp_handle h, const uint8_t *env_mask) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->pool_on) return fail(h, NPP_ERR_STATE, "npp_draw_levels: the level pool is off (npp_set_level_pool)");
+    ON_DEVICE_JOINED(h);
+    if (env_mask) HIP_TRY(h, hipMemcpyAsync(h->d_mask, env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(h->d_mask, 1, (size_t)h->n, h->stream));
+    if (int rc = pool_redraw(h, h->d_mask, 0xff, nullptr)) return rc;
+    if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));   // env_mask is caller memory: finish the copy
+    return NPP_OK;
+}
+
+int npp_env_level_view(npp_handle h, const int32_t **d_levels) {
+    if (!h || !d_levels) return fail(h, NPP_ERR_INVALID, "npp_env_level_view: bad arguments");
+    *d_levels = h->d_env_level;
+    return NPP_OK;
+}
+
+int npp_get_env_levels(npp_handle h, int32_t *host_out) {
+    if (!h || !host_out) return fail(h, NPP_ERR_INVALID, "npp_get_env_levels: bad arguments");
+    ON_DEVICE_JOINED(h);
+    if (int rc = pull_levels(h)) return rc;
+    std::memcpy(host_out, h->env_level.data(), sizeof(int32_t) * (size_t)h->n);
+    return NPP_OK;
 }
 
 
@@ -1036,9 +1211,10 @@ int npp_get_step_variant(npp_handle h, int *variant, int *tuned) {
     return NPP_OK;
 }
 
-int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
-    if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
+}  // extern "C"
+
+namespace {
+int step_impl(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
     ON_DEVICE_JOINED(h);
     KernelArgs a = base_args(h);
     a.inputs = d_actions;
@@ -1131,6 +1307,23 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
     if (pair >= 0) hipEventRecord(h->tune_ev[2 * (size_t)pair + 1], h->stream);
     HIP_TRY(h, le);
     return NPP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
+    if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
+    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
+    if (!h->pool_on || !(h->flags & NPP_FLAG_AUTORESET)) return step_impl(h, d_actions, frame_skip, out);
+    // level pool: the step as without it, then (joined) the draw for the envs whose episode ended -- read from the step's flags
+    npp_step_out o;
+    std::memset(&o, 0, sizeof(o));
+    if (out) o = *out;
+    if (!o.d_flags) o.d_flags = h->d_pool_flags;
+    if (int rc = step_impl(h, d_actions, frame_skip, &o)) return rc;
+    ON_DEVICE_JOINED(h);
+    return pool_redraw(h, o.d_flags, NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED, &o);
 }
 
 int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame_skip, const npp_step_out *out) {
@@ -1288,6 +1481,11 @@ int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, 
 int npp_set_entity_pos(npp_handle h, int env, int kind, double x, double y) {
     if (!h || env < 0 || env >= h->n || (kind != 0 && kind != 1)) return fail(h, NPP_ERR_INVALID, "npp_set_entity_pos: bad arguments");
     if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: no levels loaded");
+    if (h->pool_on) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the level pool is on (npp_set_level_pool)");
+    {
+        ON_DEVICE_JOINED(h);
+        if (int rc = pull_levels(h)) return rc;
+    }
     const CompiledLevel &L = h->levels[h->env_level[env]];
     if (L.obs_switch < 0) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the env's level has no exit switch / door");
     ON_DEVICE_JOINED(h);
@@ -1372,6 +1570,7 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
     if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_state: no levels loaded");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = pull_levels(h)) return rc;
     size_t N = (size_t)h->n;
     std::vector<double> f((size_t)NF64 * count);
     std::vector<uint32_t> u((size_t)NU32 * count);
@@ -1420,6 +1619,7 @@ int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out) 
     if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_entities: no levels loaded");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = pull_levels(h)) return rc;
     const CompiledLevel &L = h->levels[h->env_level[env]];
     std::vector<uint32_t> w(h->n_words_max);
     for (int k = 0; k < h->n_words_max; k++)
@@ -1439,6 +1639,7 @@ int npp_entity_checksum(npp_handle h, int env0, int count, double *out) {
     if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_entity_checksum: no levels loaded");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = pull_levels(h)) return rc;
     size_t N = (size_t)h->n;
     std::vector<uint32_t> w((size_t)h->n_words_max * count);
     for (int k = 0; k < h->n_words_max; k++)

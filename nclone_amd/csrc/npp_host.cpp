@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../../include/npp_amd.h"
+#include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
 
 using namespace npp;
@@ -25,6 +26,17 @@ int fail(std::nullptr_t, int code, const std::string &msg) {
 }  // namespace
 
 extern "C" {
+
+int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed, const int32_t *envs, const uint32_t *counts, int count,
+                             int32_t *out) {
+    if (count < 0 || (count > 0 && (!envs || !counts || !out))) return fail(nullptr, NPP_ERR_INVALID, "npp_level_pool_draw_host: bad arguments");
+    std::vector<double> cdf;
+    int last = 0;
+    std::string err;
+    if (!pool_cdf(weights, n_levels, n_levels, cdf, last, err)) return fail(nullptr, NPP_ERR_INVALID, err);
+    for (int i = 0; i < count; i++) out[i] = pool_pick(cdf.data(), n_levels, last, seed, (uint32_t)envs[i], counts[i]);
+    return NPP_OK;
+}
 
 int npp_compile_level_segments(const double *map, int64_t n, int16_t *out, int max_rows, int *n_out, uint32_t *unsupported_mask) {
     if (!map || !out || !n_out) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_segments: bad arguments");

@@ -37,4 +37,34 @@ inline int32_t truncation_limit_for_area(int surface_area) {
 }
 
 
+// the level pool's CDF (include/npp_amd.h npp_set_level_pool): cdf[l] = w[0] + ... + w[l] summed in f64 in index order, last = the
+// last level of non-zero weight; false (and `err`) for a wrong length, a NaN, negative or infinite weight or an all-zero vector
+inline bool pool_cdf(const double *w, int n, int n_levels, std::vector<double> &cdf, int &last, std::string &err) {
+    if (!w || n != n_levels || n <= 0) {
+        err = "level pool: " + std::to_string(n) + " weights for " + std::to_string(n_levels) + " loaded levels";
+        return false;
+    }
+    cdf.assign((size_t)n, 0.0);
+    double s = 0.0;
+    last = -1;
+    for (int l = 0; l < n; l++) {
+        if (!(w[l] >= 0.0) || std::isinf(w[l])) {
+            err = "level pool: weight " + std::to_string(l) + " is " + std::to_string(w[l]) + " (weights must be finite and >= 0)";
+            return false;
+        }
+        s += w[l];
+        cdf[(size_t)l] = s;
+        if (w[l] > 0.0) last = l;
+    }
+    if (last < 0) {
+        err = "level pool: every weight is zero";
+        return false;
+    }
+    if (std::isinf(s)) {
+        err = "level pool: the weights sum to infinity";
+        return false;
+    }
+    return true;
+}
+
 }  // namespace npp

@@ -92,6 +92,8 @@ struct KernelArgs {
     const uint8_t *tile_canvas;   // u8 [n_levels][600][1056]: tile-layer coverage counts (render kernels only; built lazily)
     const uint8_t *inputs;  // actions [n] (mode 0) or replay bytes [n_ticks][n] (mode 1)
     const uint8_t *reset_mask;  // reset kernel only; NULL = all
+    const uint8_t *obs_mask;    // observe launches (n_ticks == 0) only: the envs whose rows are written (a device mask); NULL = all.
+                                // Workgroups without a masked env return at once; the rows of the other envs are left alone
     int n;
     int n_ticks;          // frame_skip (mode 0) or tick count (mode 1); 0 = observe only
     int n_steps;          // mode 0: Gymnasium steps per launch (npp_step_many); 0 / 1 = one
@@ -175,6 +177,24 @@ struct StackArgs {
     float *terminal_stack;        // [n][state_k][41] or null
 };
 hipError_t launch_stack_push(const StackArgs &a, hipStream_t s);
+// npp_pool.hip: the level pool's draw (see npp_set_level_pool in include/npp_amd.h)
+struct PoolArgs {
+    int n;
+    const uint8_t *flags;         // env e draws when flags[e] & bits
+    int bits;
+    const double *cdf;            // [n_levels] cumulative weights
+    int n_levels, last;           // last: the last level of non-zero weight
+    uint64_t seed;
+    uint32_t *count;              // [n] draw counts
+    int32_t *env_level;           // [n]
+    int32_t *trunc;               // [n] truncation limits
+    const int32_t *level_trunc;   // [n_levels] dynamic truncation limit per level; null = dynamic truncation off
+    uint8_t *changed;             // [n] out: 1 = the env drew another level than it played (every other byte 0)
+};
+hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s);
+// envs selected by mask (null = all): level, draw count and truncation limit <- the snapshot's
+hipError_t launch_pool_restore(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count, const int32_t *s_trunc,
+                               int32_t *level, uint32_t *count, int32_t *trunc, hipStream_t s);
 // max_records: the largest number of draw records (closed-door strokes + entities + movers) of a loaded level; sizes the LDS
 // xscr: the per-env scratch of the split cell pass (GV_XSTRIDE bytes per env); null keeps the whole cell pass inside the first kernel
 constexpr size_t GV_XSTRIDE = 14336;

@@ -1636,8 +1636,12 @@ DEV void run(const KernelArgs &a, unsigned char *smem) {
     const unsigned long long wg_t0 = a.wg_cost ? __builtin_amdgcn_s_memtime() : 0ull;
     const int env0 = blk * epb;
     const int env = env0 + eib;
-    const bool valid = env < a.n;
-    const int e = valid ? env : a.n - 1;
+    const bool in_range = env < a.n;
+    // masked observe (the level pool's redraw): an env outside the mask runs along without writing anything, and a workgroup
+    // without a masked env leaves at once
+    const bool valid = in_range && (!a.obs_mask || a.obs_mask[env] != 0);
+    if (a.obs_mask && !__syncthreads_or(valid)) return;
+    const int e = in_range ? env : a.n - 1;
     const int n_valid = (a.n - env0) < epb ? (a.n - env0) : epb;
 
     uint32_t *ew = reinterpret_cast<uint32_t *>(smem + (LDS_LEVEL ? a.lds_hot_cap : 0u));
@@ -1813,9 +1817,9 @@ DEV void run(const KernelArgs &a, unsigned char *smem) {
         if (gdst) {
             if (r == 0) write_game_state(n, a.trunc_limit[e], reinterpret_cast<float *>(stage) + eib * 41);
             __syncthreads();
-            if (pass == 1) {
+            if (pass == 1 && !a.obs_mask) {
                 block_store_rows(stage, reinterpret_cast<uint32_t *>(gdst + (size_t)env0 * 41), 41, n_valid);
-            } else if (do_reset && writer) {
+            } else if ((pass == 1 || do_reset) && writer) {
                 const uint32_t *row = stage + eib * 41;
                 uint32_t *dst = reinterpret_cast<uint32_t *>(gdst + (size_t)env * 41);
                 for (int k = 0; k < 41; k++) dst[k] = row[k];
@@ -1831,7 +1835,13 @@ DEV void run(const KernelArgs &a, unsigned char *smem) {
             row[4] = (float)((ZOO ? lv.door_x : H.door_x) / 1056.0); row[5] = (float)((ZOO ? lv.door_y : H.door_y) / 600.0);
         }
         __syncthreads();
-        block_store_rows(stage, reinterpret_cast<uint32_t *>(a.out.entity_pos + (size_t)env0 * 6), 6, n_valid);
+        if (!a.obs_mask) {
+            block_store_rows(stage, reinterpret_cast<uint32_t *>(a.out.entity_pos + (size_t)env0 * 6), 6, n_valid);
+        } else if (writer) {
+            const uint32_t *row = stage + eib * 6;
+            uint32_t *dst = reinterpret_cast<uint32_t *>(a.out.entity_pos + (size_t)env * 6);
+            for (int k = 0; k < 6; k++) dst[k] = row[k];
+        }
         __syncthreads();
     }
     if (a.out.positions && writer) {   // pass-through scalars player_x/y, switch_x/y, exit_door_x/y (unrounded)

@@ -69,7 +69,7 @@ _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_fr
 
 def _device_tensor(ptr, numel, dtype, device):
     """A torch tensor over `numel` elements of device memory that the native handle owns (no copy, no ownership)."""
-    typestr = {torch.uint8: "|u1", torch.float32: "<f4"}[dtype]
+    typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4"}[dtype]
 
     class _Holder:
         __cuda_array_interface__ = {"shape": (int(numel),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
@@ -241,6 +241,46 @@ class NppBatch:
         """The reference env's per-level limit: int(clip(sqrt(reachable surface area) * 500, 1200, 10000)) frames
         (truncation_calculator.py:19-57), re-applied at every level (re)assignment."""
         nat.check(self.h, self.lib.npp_set_dynamic_truncation(self.h, 1 if enable else 0))
+
+    # ---- level pool (include/npp_amd.h npp_set_level_pool; the reference's per-episode map draw) -------------------
+    def set_level_pool(self, weights, seed=0):
+        """Draw a new level for every episode: level l with probability weights[l] / sum(weights) (one non-negative weight per
+        loaded level).  weights=None turns the pool off.  A call with the pool's current seed keeps the per-env draw counts (a
+        curriculum update); another seed restarts them.  Bad weights raise ValueError with the native message."""
+        if weights is None:
+            nat.check(self.h, self.lib.npp_set_level_pool(self.h, None, 0, 0))
+            self._pool_weights = None
+            return
+        w = np.array(weights, dtype=np.float64).ravel()
+        code = self.lib.npp_set_level_pool(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), len(w), int(seed) & (2**64 - 1))
+        if code == nat.NPP_ERR_INVALID:
+            raise ValueError(self.lib.npp_last_error(self.h).decode())
+        nat.check(self.h, code)
+        self._pool_weights = w
+
+    def draw_levels(self, mask=None):
+        """Every env (or those with a non-zero mask byte) draws a level from the pool now; an env that draws another level is
+        assigned it as by assign_levels (reset on it), the others are left alone."""
+        if mask is None:
+            nat.check(self.h, self.lib.npp_draw_levels(self.h, None))
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            assert len(m) == self.n
+            nat.check(self.h, self.lib.npp_draw_levels(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def env_level_view(self):
+        """int32 CUDA tensor [N] over the handle's env -> level array (no copy): the draws rewrite it in stream order."""
+        if getattr(self, "_level_view", None) is None:
+            p = C.c_void_p()
+            nat.check(self.h, self.lib.npp_env_level_view(self.h, C.byref(p)))
+            self._level_view = _device_tensor(p.value, self.n, torch.int32, self.device)
+        return self._level_view
+
+    def env_levels(self):
+        """int32 [N]: the level every env plays now (synchronises the handle's stream)."""
+        out = np.zeros(self.n, dtype=np.int32)
+        nat.check(self.h, self.lib.npp_get_env_levels(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
 
     def set_launch_geometry(self, lanes_per_env=0, waves_per_block=0):
         nat.check(self.h, self.lib.npp_set_launch_geometry(self.h, int(lanes_per_env), int(waves_per_block)))
@@ -520,6 +560,24 @@ def level_truncation_limit(map_data):
     lim, area = C.c_int32(0), C.c_int32(0)
     nat.check(None, L.npp_level_truncation_limit(m.ctypes.data_as(C.POINTER(C.c_double)), len(m), C.byref(lim), C.byref(area)))
     return lim.value, area.value
+
+
+def level_pool_draw(weights, seed, envs, counts):
+    """Host-only: the levels the pool draws for envs[i] at draw count counts[i] (include/npp_amd.h npp_set_level_pool has the
+    formula).  Bad weights raise ValueError with the native message."""
+    L = nat.lib()
+    w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+    e = np.ascontiguousarray(envs, dtype=np.int32).ravel()
+    c = np.ascontiguousarray(counts, dtype=np.uint32).ravel()
+    assert len(e) == len(c)
+    out = np.zeros(len(e), dtype=np.int32)
+    code = L.npp_level_pool_draw_host(w.ctypes.data_as(C.POINTER(C.c_double)), len(w), int(seed) & (2**64 - 1),
+                                      e.ctypes.data_as(C.POINTER(C.c_int32)), c.ctypes.data_as(C.POINTER(C.c_uint32)), len(e),
+                                      out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if code == nat.NPP_ERR_INVALID:
+        raise ValueError(L.npp_last_error(None).decode())
+    nat.check(None, code)
+    return out
 
 
 def compile_level_zoo(map_data):

@@ -31,6 +31,27 @@ def calculate_truncation_limit(surface_area, reachable_mine_count=0):
     return int(np.clip(v, 1200, MAX_TIME_IN_FRAMES))
 
 
+def level_category(tag):
+    """The category a level tag of nclone_amd.levels names: the tag without its last ":"-separated field ("maze:tiny:100001" ->
+    "maze:tiny", "replay:17" -> "replay")."""
+    return tag.rsplit(":", 1)[0] if ":" in tag else tag
+
+
+def expand_category_weights(category_weights, level_categories):
+    """Per-level pool weights from per-category ones, as the reference's map loader draws: a category with probability
+    proportional to its weight (env_map_loader.py:210-234), then a level of it uniformly.  category_weights: {category: weight};
+    level_categories: the category of every loaded level (e.g. [level_category(t) for t in tags]).  Categories without a weight
+    get 0; a weighted category without any level raises ValueError."""
+    cats = list(level_categories)
+    count = {}
+    for c in cats:
+        count[c] = count.get(c, 0) + 1
+    for c, w in category_weights.items():
+        if w and c not in count:
+            raise ValueError("category %r has weight %r but no loaded level" % (c, w))
+    return np.array([float(category_weights.get(c, 0.0)) / count[c] for c in cats], dtype=np.float64)
+
+
 def controls_to_input_byte(hor, jump):
     """(hor, jump) -> replay input byte (bit0 jump, bit1 right, bit2 left; replay/replay_executor.py:61-84)."""
     return (1 if jump else 0) | (2 if hor > 0 else 0) | (4 if hor < 0 else 0)
@@ -61,6 +82,15 @@ class NppVecEnvironment:
     would have shown at its terminal step (the previous window's last K - 1 entries, then terminal_state), else the live stack.
     output="torch": the stacked tensors are views of device rings (no copy): each env's K entries are contiguous, but envs are
     2 K entries apart, and the rings are rewritten by the next step.  output="numpy": contiguous host arrays.
+
+    Level pool (the reference's per-episode map draw, env_map_loader.py:111-208): level_weights, one non-negative
+    weight per level, makes every env draw its next level -- level l with probability w[l] / sum(w) -- whenever its episode ends in
+    step() (with autoreset) and in reset() (not in the checkpoint resets, which keep the level they restore).  An env that draws
+    another level returns that level's spawn observation; one that draws its own level resets as without the pool.  The draws are a
+    counter-based hash of (level_seed, env index, draw count), so a run is reproducible from level_seed; they do not reproduce the
+    reference's Python `random` stream.  reset(seed=s) reseeds the pool with s.  set_level_weights() changes the weights between
+    steps (curriculum); expand_category_weights() turns per-category weights into per-level ones.  level_weights=None (default):
+    every env keeps the level level_ids gives it, as before.  info["level_id"] (both modes): the level each env plays after the step.
     """
 
     metadata = {"render_modes": []}
@@ -69,7 +99,7 @@ class NppVecEnvironment:
                  truncation_limit="dynamic", output="torch", autoreset=True, enable_spatial_context=False,
                  enable_switch_states=False, fast_reset=True, stream=None, enable_reachability=False, obs_overlap=0,
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
-                 frame_stack_padding_type="zero"):
+                 frame_stack_padding_type="zero", level_weights=None, level_seed=None):
         assert output in ("torch", "numpy")
         spaces.check_frame_stack(visual_stack_size, state_stack_size, frame_stack_padding_type)
         self.num_envs = int(num_envs)
@@ -111,6 +141,16 @@ class NppVecEnvironment:
             self._b.set_truncation_limit(truncation_limit)
         if obs_overlap:   # speed knob (same bits): observation kernels of the cheap envs beside the step's expensive tail
             self._b.set_obs_overlap(int(obs_overlap))
+        self._pool = level_weights is not None
+        self._level_seed = None
+        if self._pool:
+            self._level_seed = int(level_seed) if level_seed is not None else int(np.random.SeedSequence().entropy) & (2**64 - 1)
+            self._b.set_level_pool(level_weights, self._level_seed)
+            self._level_ids = None
+        else:
+            with self._b._ctx():   # the fixed assignment, for info["level_id"]
+                self._level_ids_np = self._b.env_levels()
+                self._level_ids = torch.from_numpy(self._level_ids_np).to(self._b.device)
         self._rng = np.random.default_rng()
         with self._b._ctx():
             self._actions = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
@@ -206,6 +246,11 @@ class NppVecEnvironment:
                  Other keys of the reference (skip_map_load, new_level, map_name) concern its map loader and are ignored."""
         if seed is not None:
             self._rng = np.random.default_rng(seed)
+            if self._pool:   # the pool's draws restart from the seed (off and on again: the draw counts restart at 0)
+                self._level_seed = int(seed) & (2**64 - 1)
+                w = self._level_weights_now
+                self._b.set_level_pool(None)
+                self._b.set_level_pool(w, self._level_seed)
         ckpt = (options or {}).get("checkpoint")
         info = {}
         if isinstance(ckpt, str):
@@ -214,6 +259,8 @@ class NppVecEnvironment:
             self._b.restore()
             info = {"checkpoint_replay": False, "restored_snapshot": True}
         else:
+            if self._pool and ckpt is None:   # every env draws its level (the checkpoint replay keeps the one it replays on)
+                self._b.draw_levels()
             self._b.reset()
             if ckpt is not None:
                 seq = ckpt.get("action_sequence") if isinstance(ckpt, dict) else getattr(ckpt, "action_sequence", ckpt)
@@ -241,6 +288,24 @@ class NppVecEnvironment:
         src = self._b.to_host(self._obs_names)
         src.update(stk)
         return self._obs(src), info
+
+    @property
+    def _level_weights_now(self):
+        return self._b._pool_weights
+
+    def set_level_weights(self, weights):
+        """New pool weights (one per level), used from the next draw on; the draw counts and the seed are kept."""
+        if not self._pool:
+            raise RuntimeError("set_level_weights: this env was created without level_weights (no level pool)")
+        self._b.set_level_pool(weights, self._level_seed)
+
+    def _level_id(self, numpy):
+        if self._pool:
+            if numpy:
+                return self._b.env_levels()
+            with self._b._ctx():
+                return self._b.env_level_view().clone()
+        return self._level_ids_np.copy() if numpy else self._level_ids
 
     def snapshot(self):
         """Save the state of every env on the device (one slot); reset(options={"checkpoint": "snapshot"}) restores it."""
@@ -284,6 +349,7 @@ class NppVecEnvironment:
         }
         if "terminal_game_state_stack" in src:
             info["terminal_game_state_stack"] = src["terminal_game_state_stack"]
+        info["level_id"] = self._level_id(self.output == "numpy")
         return self._obs(src), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
