@@ -17,126 +17,223 @@
 
 using namespace npp;
 
-struct npp_handle_s {
-    int n = 0;
-    int device = 0;
-    unsigned flags = 0;
-    hipStream_t stream = nullptr;
-    double *d_f64 = nullptr;
-    uint32_t *d_u32 = nullptr;
-    uint32_t *d_ent = nullptr;
-    float *d_sc_cache = nullptr;
-    double *d_zoo = nullptr;   // per-env zoo blocks (always allocated with the levels; at least the 8-word head)
-    std::vector<uint8_t> ovr;  // per env: ZOO_OVR_* flags set through npp_set_entity_pos
-    int n_ovr = 0;
-    std::vector<uint8_t> s_ovr;   // the same at npp_snapshot (the zoo block's head words 3..7 travel with the snapshot)
-    double *s_zoo = nullptr;
-    int zoo_words = 0, zoo_doors = 0, zoo_movers = 0;
-    int zoo_active = 0;        // some env is assigned a level with zoo entities
-    // snapshot slot (npp_snapshot / npp_restore)
-    double *s_f64 = nullptr;
-    uint32_t *s_u32 = nullptr;
-    uint32_t *s_ent = nullptr;
-    float *s_sc = nullptr;
-    int s_words = 0;
-    unsigned long long assign_gen = 0, s_gen = ~0ull;
-    int32_t *d_env_level = nullptr;
-    int32_t *d_trunc = nullptr;
-    std::vector<int32_t> trunc;            // host mirror of d_trunc
-    bool dyn_trunc = false;                // npp_set_dynamic_truncation: per-level limit from the reachable surface area
-    std::vector<int32_t> level_trunc;      // [n_levels] that limit (empty = not computed for the loaded set)
-    uint8_t *d_mask = nullptr;
-    unsigned char *d_blob = nullptr;
-    uint8_t *d_canvas = nullptr;   // tile-layer coverage canvas of every level (render paths; built on first use)
-    float *d_gv_h = nullptr;       // global_view: per-level picture / horizontal sums / view of the level right after a reset
-    uint8_t *d_gv_v = nullptr, *d_gv_p = nullptr;
-    unsigned char *d_gv_x = nullptr;   // global_view: per-env scratch of the split cell pass
-    uint32_t *d_gv_order = nullptr, *d_gv_cost = nullptr;   // global_view: heavy-first launch order and the per-env cost it is built from
-    long gv_launches = 0;
-    uint32_t *d_pf_order = nullptr, *d_pf_cost = nullptr;   // npp_render_player_frame: heavy-first env order and the per-env cost behind it
-    long pf_launches = 0;
-    uint32_t *d_wg_order = nullptr, *d_wg_cost = nullptr;   // npp_step: heavy-first workgroup order and the per-block cost behind it
-    int wg_blocks = 0;
-    long step_launches = 0;
-    // autotuner of the step-kernel build variant (npp_kernels.hip: VariantK): windows of TUNE_WINDOW launches per variant, timed
-    // with one pair of HIP events each (never synchronised: the decision is taken once the last event has completed)
-    int variant_pin = -1;            // -1 = autotune
-    int variant = 0;                 // what npp_step launches now
-    int tune_state = 0;              // 0 = warm-up, 1 .. TUNE_ROUNDS * 3 = measuring windows, > that = waiting for events / decided
-    int tune_count = 0;              // launches inside the current state
-    bool tuned = false;
-    std::vector<hipEvent_t> tune_ev;   // one (start, end) pair per measured launch: 2 * TUNE_WINDOW * windows
-    // cost-split launch (experiment, NPP_STEP_SPLIT = "percent:variant_heavy:variant_light"): the heaviest workgroups of the
-    // heavy-first order run as their own launch of another build variant on a second stream, joined by events
-    hipStream_t split_stream = nullptr;
-    hipEvent_t split_ev[2] = {nullptr, nullptr};
-    long tune_since = 0;             // launches since the last decision
-    // observation overlap (npp_set_obs_overlap / npp_set_obs_overlap_parts): npp_step cuts its heavy-first workgroup order at
-    // cut_pct[] percent and launches every piece ("part") as a kernel of its own -- part 0, the cheap tail of the order, on the
-    // caller's stream, the others on part_stream[] -- and while live_parts > 1 every observation entry point launches one kernel per
-    // part on the stream of the part it reads, so the observations of the cheap envs are produced while the expensive envs are still
-    // stepping.  join_streams() makes the caller's stream wait for the others.
-    int n_cuts = 0;                  // 0 = off
-    int cut_pct[3] = {0, 0, 0};      // ascending, from the head (most expensive end) of the order
-    int live_parts = 1;              // parts of the last npp_step still to be joined (1 = it was not split)
-    bool phase_dirty = true;         // d_phase does not describe the current order / cuts
-    uint8_t *d_phase = nullptr;      // [n] which part steps the env (npp_phase_kernel, rewritten when the order or the cuts change)
-    hipStream_t part_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // part 0 = the cheap tail of the order, on the caller's stream
-    // the streams behind part_stream[1..] and side[][]: created by calibrate_streams(), which keeps only streams whose kernels were
-    // SEEN to run beside the caller's and beside each other (HIP spreads a process's streams over four hardware queues; two streams
-    // on one queue serialise, and which queue a new stream gets depends on every stream the process has created before)
-    std::vector<hipStream_t> owned;
-    hipStream_t owned_for = nullptr;   // the caller's stream they were chosen against
-    bool owned_valid = false;
-    hipEvent_t cal_ev[2] = {nullptr, nullptr};
-    hipEvent_t part_ev[4] = {nullptr, nullptr, nullptr, nullptr};        // join
-    hipEvent_t ov_ev[2] = {nullptr, nullptr};                           // fork / tables on the caller's stream ready
-    // ... and with two parts (four hardware queues feed a process) the observation kernels need not wait for each other either: the
-    // kinds (bit 0 global_view, 1 player_frame, 2 reachability, 3 switch_states) named in side_mask run on a side stream forked off
-    // the stream that stepped the part -- side[0][p] for global_view, side[1][p] shared by the other three
-    unsigned side_mask = 0;
-    hipStream_t side[2][2] = {};
-    hipEvent_t side_ev[2][2] = {};   // fork, then reused for the join
-    bool side_busy[2][2] = {};
-    // reachability observation (npp_reachability; built on first use): per-level tables + per-env cache
-    ReachHdr *d_rhdr = nullptr;
-    unsigned char *d_rblob = nullptr;
-    uint32_t *d_rkey = nullptr, *s_rkey = nullptr;      // (ninja cell, exit_switch_activated) of the cached vector, 0 = none
-    float *d_rcache = nullptr, *s_rcache = nullptr;     // [n][REACH_DIM + 1]
-    int s_reach = 0;                                    // the snapshot slot holds a reachability cache
-    ReachMissDev rmiss = {nullptr, nullptr, nullptr, nullptr};   // per-env dictionary of the miss branch (levels with ReachHdr::miss_exit only)
-    // frame stacking (npp_set_frame_stack / npp_frame_stack_push, npp_stack.hip): one ring of 2 K slots per env and stacked key
-    int fs_vk = 0, fs_sk = 0, fs_repeat = 0;   // stack sizes (0 = off) and padding
-    int fs_vhead = 0, fs_shead = 0;            // ring position of the newest entry
-    uint8_t *d_fs_frames = nullptr;            // [n][2 fs_vk][84 * 84]
-    float *d_fs_state = nullptr;               // [n][2 fs_sk][41]
-    // level pool (npp_set_level_pool, npp_pool.hip): with it on, the device changes env_level / d_trunc after a step, and the host
-    // mirrors env_level / trunc are read back lazily (pull_levels) where a host path needs them
-    bool pool_on = false;
-    bool pool_ever = false;     // a pool was on since npp_load_levels: levels change without npp_assign_levels, snapshots carry them
-    bool pool_dirty = false;    // the device may have drawn since env_level / trunc were read back
-    uint64_t pool_seed = 0;
-    int pool_last = 0;          // the last level of non-zero weight
-    std::vector<double> pool_w;
-    double *d_pool_cdf = nullptr;        // [n_levels]
-    uint32_t *d_pool_count = nullptr;    // [n] draw counts
-    uint8_t *d_pool_flags = nullptr;     // [n] step flags when the caller asked for none
-    uint8_t *d_pool_changed = nullptr;   // [n] envs that drew another level (device reset / observe mask)
-    int32_t *d_level_trunc = nullptr;    // [n_levels] dynamic truncation limit per level (pool + dynamic truncation)
-    int32_t *s_level = nullptr, *s_trunc = nullptr;   // snapshot of env_level / d_trunc / d_pool_count
-    uint32_t *s_count = nullptr;
-    LevelHdr *d_hdr = nullptr;
-    int n_words_max = 1;
-    uint32_t hot_max = 0;      // largest staged-level size over the loaded set
-    uint32_t lds_hot_cap = 0;  // LDS bytes reserved for a staged level under the current launch geometry
-    int lanes_per_env = 0;     // 0 = choose from n_envs
-    int waves_per_block = 0;
-    int geo_g = 1, geo_wpb = 1;
-    int lds_level = 0;         // all workgroups level-uniform and staged levels fit
+namespace {
+
+// Owners of the handle's device resources: released when they are dropped or reassigned, never by hand.  Kernel arguments stay
+// plain pointers (.get()); the caller's stream is borrowed and never wrapped.
+template <class T> class DevBuf {   // n elements of T in device memory
+    T *p_ = nullptr;
+    size_t n_ = 0;
+
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { reset(); std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t n, size_t pad = 0) {   // `pad` bytes past the end: for kernels that read rows as aligned dword groups
+        reset();
+        const hipError_t e = hipMalloc((void **)&p_, n * sizeof(T) + pad);
+        if (e == hipSuccess) n_ = n; else p_ = nullptr;
+        return e;
+    }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+    T *get() const { return p_; }
+    size_t size() const { return n_; }
+    size_t bytes() const { return n_ * sizeof(T); }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+
+template <class T, hipError_t (*Create)(T *, unsigned), hipError_t (*Destroy)(T)> class HipObject {   // a HIP event or stream
+    T o_ = nullptr;
+
+  public:
+    HipObject() = default;
+    HipObject(HipObject &&o) noexcept { *this = std::move(o); }
+    HipObject &operator=(HipObject &&o) noexcept { reset(); std::swap(o_, o.o_); return *this; }
+    ~HipObject() { reset(); }
+    hipError_t create(unsigned flags) {
+        reset();
+        const hipError_t e = Create(&o_, flags);
+        if (e != hipSuccess) o_ = nullptr;
+        return e;
+    }
+    void reset() { if (o_) (void)Destroy(o_); o_ = nullptr; }
+    T get() const { return o_; }
+    explicit operator bool() const { return o_ != nullptr; }
+};
+using Event = HipObject<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using Stream = HipObject<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;   // one the handle created
+
+// live per-env state (npp_create)
+struct EnvState {
+    DevBuf<double> f64;             // [NF64][n]
+    DevBuf<uint32_t> u32;           // [NU32][n]
+    DevBuf<int32_t> level, trunc;   // level and truncation limit (host mirrors: npp_handle_s::env_level / trunc)
+    DevBuf<uint8_t> mask;           // a caller's env mask, copied for a launch
+    DevBuf<float> sc;               // [48][n] spatial-context cache
+    DevBuf<uint32_t> count;         // level pool draw counts
+};
+
+// global_view's per-level tables: picture / horizontal sums / view of the level right after a reset
+struct GvTables {
+    DevBuf<float> h;
+    DevBuf<uint8_t> v, p;
+};
+
+// reachability observation (npp_reachability): per-level tables + per-env cache
+struct Reach {
+    DevBuf<ReachHdr> hdr;
+    DevBuf<unsigned char> blob;
+    DevBuf<uint32_t> key;   // (ninja cell, exit_switch_activated) of the cached vector, 0 = none
+    DevBuf<float> cache;    // [n][REACH_DIM + 1]
+    // per-env dictionary of the miss branch (levels with ReachHdr::miss_exit only)
+    DevBuf<uint32_t> stamp, epoch, last_episode;
+    DevBuf<double> raw;
+    ReachMissDev miss() const { return {stamp.get(), raw.get(), epoch.get(), last_episode.get()}; }
+};
+
+// The loaded level set and everything derived from it: replaced whole by npp_load_levels
+struct LevelSet {
     std::vector<CompiledLevel> levels;
     std::vector<LevelHdr> hdrs;
-    std::vector<int32_t> env_level;
+    int n_words_max = 1;
+    uint32_t hot_max = 0;   // largest staged-level size over the set
+    int zoo_words = 0, zoo_doors = 0, zoo_movers = 0;
+    DevBuf<unsigned char> blob;   // staged levels
+    DevBuf<LevelHdr> hdr;
+    DevBuf<uint32_t> ent;         // [n_words_max][n] entity words
+    DevBuf<double> zoo;           // [n][zoo_words] per-env zoo blocks (at least the 8-word head)
+    // built on first use
+    DevBuf<uint8_t> canvas;       // tile-layer coverage canvas of every level (render paths)
+    GvTables gv;
+    Reach reach;
+    std::vector<int32_t> level_trunc;   // [n_levels] dynamic truncation limit (empty = not computed)
+    DevBuf<int32_t> d_level_trunc;      // the same on the device (level pool + dynamic truncation)
+    DevBuf<double> pool_cdf;            // [n_levels] (level pool)
+};
+
+// The snapshot slot (npp_snapshot / npp_restore): one mirror per live buffer, sized like it
+struct Snapshot {
+    DevBuf<double> f64;
+    DevBuf<uint32_t> u32, ent;
+    DevBuf<float> sc;
+    DevBuf<int32_t> level, trunc;   // (level pool) each env's level, draw count and truncation limit go with its state
+    DevBuf<uint32_t> count;
+    DevBuf<double> zoo;             // the zoo block's head words 3..7 carry the repositioning of npp_set_entity_pos
+    DevBuf<uint32_t> rkey;          // the cached reachability vector is part of what the next observation returns
+    DevBuf<float> rcache;
+    bool reach = false;             // the slot holds a reachability cache
+    std::vector<uint8_t> ovr;       // npp_handle_s::ovr at npp_snapshot
+    unsigned long long gen = ~0ull;   // npp_handle_s::assign_gen at npp_snapshot
+};
+
+// heavy-first launch orders and the costs they are built from (sized by n: kept across npp_load_levels)
+struct Orders {
+    DevBuf<uint32_t> wg_order, wg_cost;   // npp_step: workgroup order and per-block costs
+    int wg_blocks = 0;
+    long step_launches = 0;
+    DevBuf<uint32_t> pf_order, pf_cost;   // npp_render_player_frame: env order and per-env costs
+    long pf_launches = 0;
+    DevBuf<uint32_t> gv_order, gv_cost;   // global_view: env order and per-env costs
+    long gv_launches = 0;
+    DevBuf<unsigned char> gv_x;           // (NPP_GV_SPLIT builds) global_view's per-env scratch of the split cell pass
+};
+
+// autotuner of the step-kernel build variant (npp_kernels.hip: VariantK): windows of TUNE_WINDOW launches per variant, timed
+// with one pair of HIP events each (never synchronised: the decision is taken once the last event has completed)
+struct Tuner {
+    int pin = -1;        // -1 = autotune
+    int variant = 0;     // what npp_step launches now
+    int state = 0;       // 0 = warm-up, 1 .. TUNE_ROUNDS * 3 = measuring windows, > that = waiting for events / decided
+    int count = 0;       // launches inside the current state
+    bool tuned = false;
+    long since = 0;      // launches since the last decision
+    std::vector<Event> ev;   // one (start, end) pair per measured launch: 2 * TUNE_WINDOW * windows
+    // a new level set / assignment / geometry / stream: the warm-up also lets the heavy-first order settle
+    void restart() { state = 0; count = 0; tuned = pin >= 0; variant = pin >= 0 ? pin : 0; }
+};
+
+// observation overlap (npp_set_obs_overlap / npp_set_obs_overlap_parts): npp_step cuts its heavy-first workgroup order at
+// cut_pct[] percent and launches every piece ("part") as a kernel of its own -- part 0, the cheap tail of the order, on the
+// caller's stream, the others on part_stream[] -- and while live_parts > 1 every observation entry point launches one kernel per
+// part on the stream of the part it reads, so the observations of the cheap envs are produced while the expensive envs are still
+// stepping.  join_streams() makes the caller's stream wait for the others.
+struct Overlap {
+    int n_cuts = 0;               // 0 = off
+    int cut_pct[3] = {0, 0, 0};   // ascending, from the head (most expensive end) of the order
+    int live_parts = 1;           // parts of the last npp_step still to be joined (1 = it was not split)
+    bool phase_dirty = true;      // phase does not describe the current order / cuts
+    DevBuf<uint8_t> phase;        // [n] which part steps the env (npp_phase_kernel, rewritten when the order or the cuts change)
+    hipStream_t part_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // part 0 = the cheap tail of the order, on the caller's stream
+    // the streams behind part_stream[1..] and side[]: created by calibrate_streams(), which keeps only streams whose kernels were
+    // SEEN to run beside the caller's and beside each other (HIP spreads a process's streams over four hardware queues; two streams
+    // on one queue serialise, and which queue a new stream gets depends on every stream the process has created before)
+    std::vector<Stream> owned;
+    hipStream_t owned_for = nullptr;   // the caller's stream they were chosen against
+    bool owned_valid = false;
+    Event cal_ev[2];
+    Event part_ev[4];   // join
+    Event ov_ev[2];     // fork / tables on the caller's stream ready
+    // ... and with two parts player_frame need not wait for the other observation kernels either: it runs on side[p], forked off
+    // the stream that stepped part p.  Measured (doors, full Dict, two parts cut at 40 %): no side stream 471 us per step,
+    // global_view aside 485, player_frame aside 436, both 555 -- HIP feeds a process through four hardware queues, so more
+    // streams than that share queues and serialise again
+    hipStream_t side[2] = {nullptr, nullptr};
+    Event side_ev[2];   // fork, then reused for the join
+    bool side_busy[2] = {false, false};
+};
+
+// frame stacking (npp_set_frame_stack / npp_frame_stack_push, npp_stack.hip): one ring of 2 K slots per env and stacked key
+struct FrameStack {
+    int vk = 0, sk = 0, repeat = 0;   // stack sizes (0 = off) and padding
+    int vhead = 0, shead = 0;         // ring position of the newest entry
+    DevBuf<uint8_t> frames;           // [n][2 vk][84 * 84]
+    DevBuf<float> state;              // [n][2 sk][41]
+};
+
+// level pool (npp_set_level_pool, npp_pool.hip): with it on, the device changes env_level / trunc after a step, and the host
+// mirrors are read back lazily (pull_levels) where a host path needs them
+struct Pool {
+    bool on = false;
+    bool ever = false;    // a pool was on since npp_load_levels: levels change without npp_assign_levels, snapshots carry them
+    bool dirty = false;   // the device may have drawn since env_level / trunc were read back
+    uint64_t seed = 0;
+    int last = 0;         // the last level of non-zero weight
+    std::vector<double> w;
+    DevBuf<uint8_t> flags;     // [n] step flags when the caller asked for none
+    DevBuf<uint8_t> changed;   // [n] envs that drew another level (device reset / observe mask)
+};
+
+// the launch plan (plan_geometry)
+struct Plan {
+    int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
+    uint32_t lds_hot_cap = 0;   // LDS bytes reserved for a staged level
+    int zoo_active = 0;         // some env may play a level with zoo entities (or has one repositioned)
+    int lds_level = 0;          // all workgroups level-uniform and staged levels fit
+};
+
+}  // namespace
+
+struct npp_handle_s {
+    int n = 0, device = 0;
+    unsigned flags = 0;
+    hipStream_t stream = nullptr;   // the caller's
     std::string err;
+    std::vector<int32_t> env_level, trunc;   // host mirrors of env.level / env.trunc
+    bool dyn_trunc = false;           // npp_set_dynamic_truncation: per-level limit from the reachable surface area
+    std::vector<uint8_t> ovr;         // per env: ZOO_OVR_* flags set through npp_set_entity_pos
+    int n_ovr = 0;
+    unsigned long long assign_gen = 0;
+    int lanes_per_env = 0, waves_per_block = 0;   // npp_set_launch_geometry (0 = choose)
+    Plan plan;
+    EnvState env;
+    LevelSet ls;
+    Snapshot snap;
+    Orders ord;
+    Tuner tune;
+    Overlap ov;
+    FrameStack fs;
+    Pool pool;
 };
 
 
@@ -159,38 +256,39 @@ uint32_t align_up(uint32_t v, uint32_t a) { return (v + a - 1) / a * a; }
 
 // observation overlap: the caller's stream waits for everything the other streams were given since the last split step
 hipError_t join_streams(npp_handle h) {
+    Overlap &ov = h->ov;
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 2; k++)
-        for (int p = 0; p < 2; p++)
-            if (h->side_busy[k][p]) {
-                h->side_busy[k][p] = false;
-                if (e == hipSuccess) e = hipEventRecord(h->side_ev[k][p], h->side[k][p]);
-                if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->side_ev[k][p], 0);
-            }
-    for (int p = 0; p < h->live_parts && h->live_parts > 1; p++) {
-        if (h->part_stream[p] == h->stream) continue;
-        if (e == hipSuccess) e = hipEventRecord(h->part_ev[p], h->part_stream[p]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->part_ev[p], 0);
+    for (int p = 0; p < 2; p++)
+        if (ov.side_busy[p]) {
+            ov.side_busy[p] = false;
+            if (e == hipSuccess) e = hipEventRecord(ov.side_ev[p].get(), ov.side[p]);
+            if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ov.side_ev[p].get(), 0);
+        }
+    for (int p = 0; p < ov.live_parts && ov.live_parts > 1; p++) {
+        if (ov.part_stream[p] == h->stream) continue;
+        if (e == hipSuccess) e = hipEventRecord(ov.part_ev[p].get(), ov.part_stream[p]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ov.part_ev[p].get(), 0);
     }
-    h->live_parts = 1;
+    ov.live_parts = 1;
     return e;
 }
-// the stream observation kernel `kind` of part `part` is launched on: the part's own stream, or (two parts only) a side stream
-// forked off it here.  `tables`: the caller's stream holds work the kernel needs (order tables) -- other streams wait for that.
-hipError_t obs_stream(npp_handle h, int kind, int part, bool tables, hipStream_t *out) {
-    hipStream_t src = h->part_stream[part];
+// the stream an observation kernel of part `part` is launched on: the part's own stream, or (player_frame, two parts only) a side
+// stream forked off it here.  `tables`: the caller's stream holds work the kernel needs (order tables) -- other streams wait for that.
+hipError_t obs_stream(npp_handle h, bool player_frame, int part, bool tables, hipStream_t *out) {
+    Overlap &ov = h->ov;
+    hipStream_t dst = ov.part_stream[part];
     hipError_t e = hipSuccess;
-    const bool aside = h->n_cuts == 1 && (h->side_mask >> kind & 1) != 0 && h->side[kind ? 1 : 0][part] != nullptr;
-    kind = kind ? 1 : 0;
-    hipStream_t dst = aside ? h->side[kind][part] : src;
-    if (aside && !h->side_busy[kind][part]) {   // (a second call before the join just queues behind the first)
-        e = hipEventRecord(h->side_ev[kind][part], src);
-        if (e == hipSuccess) e = hipStreamWaitEvent(dst, h->side_ev[kind][part], 0);
-        h->side_busy[kind][part] = true;
+    if (player_frame && ov.n_cuts == 1 && ov.side[part] != nullptr) {
+        if (!ov.side_busy[part]) {   // (a second call before the join just queues behind the first)
+            e = hipEventRecord(ov.side_ev[part].get(), dst);
+            if (e == hipSuccess) e = hipStreamWaitEvent(ov.side[part], ov.side_ev[part].get(), 0);
+            ov.side_busy[part] = true;
+        }
+        dst = ov.side[part];
     }
     if (e == hipSuccess && tables && dst != h->stream) {
-        e = hipEventRecord(h->ov_ev[1], h->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(dst, h->ov_ev[1], 0);
+        e = hipEventRecord(ov.ov_ev[1].get(), h->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(dst, ov.ov_ev[1].get(), 0);
     }
     *out = dst;
     return e;
@@ -200,83 +298,77 @@ hipError_t obs_stream(npp_handle h, int kind, int part, bool tables, hipStream_t
 // does, or a whole kernel later.  (Setup path: synchronises both streams.)
 bool streams_overlap(npp_handle h, hipStream_t a, hipStream_t b, long long ticks, float single_ms) {
     if (hipStreamSynchronize(a) != hipSuccess || hipStreamSynchronize(b) != hipSuccess) return true;
-    bool ok = hipEventRecord(h->cal_ev[0], a) == hipSuccess;
+    bool ok = hipEventRecord(h->ov.cal_ev[0].get(), a) == hipSuccess;
     ok = ok && launch_spin(ticks, a) == hipSuccess && launch_spin(ticks, b) == hipSuccess;
-    ok = ok && hipEventRecord(h->cal_ev[1], b) == hipSuccess;
+    ok = ok && hipEventRecord(h->ov.cal_ev[1].get(), b) == hipSuccess;
     ok = ok && hipStreamSynchronize(a) == hipSuccess && hipStreamSynchronize(b) == hipSuccess;
     float ms = 0.f;
-    if (!ok || hipEventElapsedTime(&ms, h->cal_ev[0], h->cal_ev[1]) != hipSuccess) return true;   // cannot tell: take the stream
+    if (!ok || hipEventElapsedTime(&ms, h->ov.cal_ev[0].get(), h->ov.cal_ev[1].get()) != hipSuccess) return true;   // cannot tell: take the stream
     return ms < 1.6f * single_ms;
 }
 
-// `need` streams of the handle's own that overlap with the caller's stream and with each other (see NppHandle::owned); when fewer
+// `need` streams of the handle's own that overlap with the caller's stream and with each other (see Overlap::owned); when fewer
 // can be found among 12 candidates the rest are streams that do not -- slower, never wrong.
 int calibrate_streams(npp_handle h, int need) {
-    if (h->owned_valid && h->owned_for == h->stream && (int)h->owned.size() >= need) return NPP_OK;
+    Overlap &ov = h->ov;
+    if (ov.owned_valid && ov.owned_for == h->stream && (int)ov.owned.size() >= need) return NPP_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (hipStream_t st : h->owned) hipStreamDestroy(st);
-    h->owned.clear();
-    if (!h->cal_ev[0]) {
-        HIP_TRY(h, hipEventCreate(&h->cal_ev[0]));
-        HIP_TRY(h, hipEventCreate(&h->cal_ev[1]));
+    ov.owned.clear();
+    if (!ov.cal_ev[0]) {
+        HIP_TRY(h, ov.cal_ev[0].create(hipEventDefault));
+        HIP_TRY(h, ov.cal_ev[1].create(hipEventDefault));
     }
     const long long ticks = 3000;   // 30 us of the 100 MHz wall clock
     float single_ms = 0.03f;
     {   // what one such kernel takes between two events on one stream (launch overhead included)
         launch_spin(ticks, h->stream);   // warm: the code object
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipEventRecord(h->cal_ev[0], h->stream));
+        HIP_TRY(h, hipEventRecord(ov.cal_ev[0].get(), h->stream));
         HIP_TRY(h, launch_spin(ticks, h->stream));
-        HIP_TRY(h, hipEventRecord(h->cal_ev[1], h->stream));
+        HIP_TRY(h, hipEventRecord(ov.cal_ev[1].get(), h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, h->cal_ev[0], h->cal_ev[1]) == hipSuccess && ms > 0.f) single_ms = ms;
+        if (hipEventElapsedTime(&ms, ov.cal_ev[0].get(), ov.cal_ev[1].get()) == hipSuccess && ms > 0.f) single_ms = ms;
     }
-    std::vector<hipStream_t> rejected;
-    for (int c = 0; c < 12 && (int)h->owned.size() < need; c++) {
-        hipStream_t st = nullptr;
-        HIP_TRY(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        bool ok = streams_overlap(h, h->stream, st, ticks, single_ms);
-        for (size_t i = 0; ok && i < h->owned.size(); i++) ok = streams_overlap(h, h->owned[i], st, ticks, single_ms);
-        (ok ? h->owned : rejected).push_back(st);   // a rejected stream stays alive until the search ends: it keeps its queue busy
+    std::vector<Stream> rejected;
+    for (int c = 0; c < 12 && (int)ov.owned.size() < need; c++) {
+        Stream st;
+        HIP_TRY(h, st.create(hipStreamNonBlocking));
+        bool ok = streams_overlap(h, h->stream, st.get(), ticks, single_ms);
+        for (size_t i = 0; ok && i < ov.owned.size(); i++) ok = streams_overlap(h, ov.owned[i].get(), st.get(), ticks, single_ms);
+        (ok ? ov.owned : rejected).push_back(std::move(st));   // a rejected stream stays alive until the search ends: it keeps its queue busy
     }
-    while ((int)h->owned.size() < need && !rejected.empty()) { h->owned.push_back(rejected.back()); rejected.pop_back(); }
-    for (hipStream_t st : rejected) hipStreamDestroy(st);
-    while ((int)h->owned.size() < need) {
-        hipStream_t st = nullptr;
-        HIP_TRY(h, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        h->owned.push_back(st);
+    while ((int)ov.owned.size() < need && !rejected.empty()) { ov.owned.push_back(std::move(rejected.back())); rejected.pop_back(); }
+    rejected.clear();
+    while ((int)ov.owned.size() < need) {
+        Stream st;
+        HIP_TRY(h, st.create(hipStreamNonBlocking));
+        ov.owned.push_back(std::move(st));
     }
-    h->owned_for = h->stream;
-    h->owned_valid = true;
-    // hand them out: the parts first, then (two parts only) the side streams in use
+    ov.owned_for = h->stream;
+    ov.owned_valid = true;
+    // hand them out: the parts first, then (two parts only) the side streams
     int k = 0;
     // the cheap tail of the order rides on the caller's stream: that stream also carries the order-table kernels the other
     // streams wait for, and behind the most expensive part they would come a whole step late (measured: 520 us per step
     // instead of 440, doors, full Dict)
-    for (int q = 0; q <= h->n_cuts; q++) h->part_stream[q] = q == 0 ? h->stream : h->owned[k++];
-    for (int i = 0; i < 2; i++)
-        for (int q = 0; q < 2; q++) {
-            const bool used = h->n_cuts == 1 && (i ? (h->side_mask & 14u) : (h->side_mask & 1u));
-            h->side[i][q] = used ? h->owned[k++] : nullptr;
-        }
+    for (int q = 0; q <= ov.n_cuts; q++) ov.part_stream[q] = q == 0 ? h->stream : ov.owned[k++].get();
+    for (int q = 0; q < 2; q++) ov.side[q] = ov.n_cuts == 1 ? ov.owned[k++].get() : nullptr;
     return NPP_OK;
 }
-int streams_needed(npp_handle h) {
-    return h->n_cuts + (h->n_cuts == 1 ? 2 * (((h->side_mask & 14u) ? 1 : 0) + ((h->side_mask & 1u) ? 1 : 0)) : 0);
-}
+int streams_needed(npp_handle h) { return h->ov.n_cuts + (h->ov.n_cuts == 1 ? 2 : 0); }
 
 // One observation kernel: as it is on the caller's stream (overlap off), or once per part of the last split step, the most
 // expensive part first, each launch told which part's envs are its own.
-template <class F> int obs_launch(npp_handle h, KernelArgs a, int kind, bool tables, F &&launch) {
-    if (h->live_parts <= 1) {   // overlap off, or the last step was not split
+template <class F> int obs_launch(npp_handle h, KernelArgs a, bool player_frame, bool tables, F &&launch) {
+    if (h->ov.live_parts <= 1) {   // overlap off, or the last step was not split
         HIP_TRY(h, launch(a, h->stream));
         return NPP_OK;
     }
     hipStream_t st = h->stream;
-    a.phase = h->d_phase;
-    for (int q = h->live_parts - 1; q >= 0; q--) {
-        HIP_TRY(h, obs_stream(h, kind, q, tables, &st));
+    a.phase = h->ov.phase.get();
+    for (int q = h->ov.live_parts - 1; q >= 0; q--) {
+        HIP_TRY(h, obs_stream(h, player_frame, q, tables, &st));
         a.phase_id = q;
         HIP_TRY(h, launch(a, st));
     }
@@ -308,94 +400,99 @@ struct DeviceGuard {
 // Launch geometry (DESIGN.md "lanes per environment"): G lanes cooperate on one env.  The chip has 256 CUs x 4 SIMDs;
 // the path is a latency-bound fp64 dependency chain, so the grid is sized to put about two wavefronts on every SIMD
 // (one hides the other's latency) and the spare lanes of each wavefront are spent on segment-level parallelism.
-int pull_levels(npp_handle h);
-
-void plan_geometry(npp_handle h, bool keep_tuning = false) {
-    (void)pull_levels(h);   // (a failure leaves the mirror as it was and is reported by the next call that syncs)
-    const int zoo_before = h->zoo_active;
-    int g = h->lanes_per_env;
-    if (const char *ev = std::getenv("NPP_LANES_PER_ENV")) g = std::atoi(ev);
+// The plan for n envs playing `level` of set L; `any_ovr`: some exit switch / door is repositioned; `pool`: the weights of the
+// level pool when it is on.
+Plan make_plan(const LevelSet &L, int n, const std::vector<int32_t> &level, int lanes_per_env, int waves_per_block, bool any_ovr,
+               const std::vector<double> *pool) {
+    Plan p;
+    int g = lanes_per_env;
     if (g <= 0) {
         // measured on MI355X (tools/sweep_geometry.py, tools/big_batch_probe.py): 16 lanes per env up to 16 384 envs, 8 at
         // 32 768, 4 from 65 536 on (95.8 M env-steps/s there; 2 lanes per env is 2.5x slower at any size)
         g = 16;
-        while (g > 4 && (long long)h->n * g / 64 > 4096) g >>= 1;
+        while (g > 4 && (long long)n * g / 64 > 4096) g >>= 1;
     }
     int gg = 1;
     while (gg * 2 <= g && gg < 64) gg *= 2;
     g = gg;
-    int wpb = h->waves_per_block;
-    if (const char *ev = std::getenv("NPP_WAVES_PER_BLOCK")) wpb = std::atoi(ev);
+    int wpb = waves_per_block;
     if (wpb <= 0) wpb = 4;
     if (wpb > 4) wpb = 4;
-    while (wpb > 1 && (64 / g) * wpb > h->n) wpb >>= 1;
-    h->zoo_active = h->n_ovr > 0 ? 1 : 0;   // repositioned switches / doors are handled by the zoo kernel's merged walk
-    if (h->d_zoo)
-        for (int e = 0; e < h->n && !h->zoo_active; e++) h->zoo_active = h->levels[h->env_level[e]].has_zoo ? 1 : 0;
-    if (h->pool_on)   // (level pool) any level an env may draw
-        for (size_t l = 0; l < h->pool_w.size() && !h->zoo_active; l++) h->zoo_active = h->pool_w[l] > 0.0 && h->levels[l].has_zoo ? 1 : 0;
-    const int zw = h->zoo_active ? h->zoo_words : 0;
+    while (wpb > 1 && (64 / g) * wpb > n) wpb >>= 1;
+    p.zoo_active = any_ovr ? 1 : 0;   // repositioned switches / doors are handled by the zoo kernel's merged walk
+    if (!L.levels.empty())
+        for (int e = 0; e < n && !p.zoo_active; e++) p.zoo_active = L.levels[level[e]].has_zoo ? 1 : 0;
+    if (pool)   // (level pool) any level an env may draw
+        for (size_t l = 0; l < pool->size() && !p.zoo_active; l++) p.zoo_active = (*pool)[l] > 0.0 && L.levels[l].has_zoo ? 1 : 0;
+    const int zw = p.zoo_active ? L.zoo_words : 0;
     // LDS plan: staged level + entity words + observation staging (+ zoo blocks) must fit the per-workgroup budget
     for (;;) {
         int epb = (64 / g) * wpb;
-        uint32_t fixed = (uint32_t)lds_bytes(0, h->n_words_max, epb, zw);
+        uint32_t fixed = (uint32_t)lds_bytes(0, L.n_words_max, epb, zw);
         if (fixed > LDS_BUDGET) {
             if (wpb > 1) { wpb >>= 1; continue; }
             if (g < 64) { g *= 2; continue; }   // zoo blocks are big: fewer envs per wavefront
         }
-        uint32_t cap = h->hot_max;
+        uint32_t cap = L.hot_max;
         if (zw && fixed + cap > LDS_BUDGET && wpb > 1) { wpb >>= 1; continue; }   // zoo: staging the level beats a bigger workgroup
         if (fixed + cap > LDS_BUDGET) cap = fixed < LDS_BUDGET ? ((LDS_BUDGET - fixed) / 16) * 16 : 0;
-        h->lds_hot_cap = cap;
+        p.lds_hot_cap = cap;
         break;
     }
-    // a new plan (level set, assignment, geometry, zoo kernels on / off) restarts npp_step's variant autotuner; a plan that comes
-    // out the same (npp_restore of a snapshot with the same overrides) keeps the decision
-    const bool same_plan = keep_tuning && g == h->geo_g && wpb == h->geo_wpb && zoo_before == h->zoo_active;
-    h->geo_g = g;
-    h->geo_wpb = wpb;
-    if (!same_plan) {
-        h->tune_state = 0; h->tune_count = 0; h->tuned = h->variant_pin >= 0;
-        h->variant = h->variant_pin >= 0 ? h->variant_pin : 0;
-    }
+    p.g = g;
+    p.wpb = wpb;
     // can every workgroup stage ONE level?  (the host owns the env -> level assignment)
     int epb = (64 / g) * wpb;
-    int ok = !h->hdrs.empty() && !h->pool_on;   // (level pool: levels change on the device, workgroups no longer share one)
-    for (int b0 = 0; b0 < h->n && ok; b0 += epb) {
-        int lvl = h->env_level[b0];
-        if (h->hdrs[lvl].hot_bytes > h->lds_hot_cap) ok = 0;
-        for (int e = b0 + 1; e < b0 + epb && e < h->n && ok; e++)
-            if (h->env_level[e] != lvl) ok = 0;
+    int ok = !L.hdrs.empty() && !pool;   // (level pool: levels change on the device, workgroups no longer share one)
+    for (int b0 = 0; b0 < n && ok; b0 += epb) {
+        int lvl = level[b0];
+        if (L.hdrs[lvl].hot_bytes > p.lds_hot_cap) ok = 0;
+        for (int e = b0 + 1; e < b0 + epb && e < n && ok; e++)
+            if (level[e] != lvl) ok = 0;
     }
-    h->lds_level = ok;
+    p.lds_level = ok;
+    return p;
+}
+
+int pull_levels(npp_handle h);
+
+void plan_geometry(npp_handle h, bool keep_tuning = false) {
+    (void)pull_levels(h);   // (a failure leaves the mirror as it was and is reported by the next call that syncs)
+    const Plan p = make_plan(h->ls, h->n, h->env_level, h->lanes_per_env, h->waves_per_block, h->n_ovr > 0, h->pool.on ? &h->pool.w : nullptr);
+    // a new plan (level set, assignment, geometry, zoo kernels on / off) restarts npp_step's variant autotuner; a plan that comes
+    // out the same (npp_restore of a snapshot with the same overrides) keeps the decision
+    const bool same_plan = keep_tuning && p.g == h->plan.g && p.wpb == h->plan.wpb && p.zoo_active == h->plan.zoo_active;
+    h->plan = p;
+    if (!same_plan) h->tune.restart();
 }
 
 KernelArgs base_args(npp_handle h) {
+    const LevelSet &L = h->ls;
     KernelArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.f64 = h->d_f64;
-    a.u32 = h->d_u32;
-    a.ent_bits = h->d_ent;
-    a.sc_cache = h->d_sc_cache;
-    a.env_level = h->d_env_level;
-    a.trunc_limit = h->d_trunc;
-    a.hdr = h->d_hdr;
-    a.blob = h->d_blob;
-    a.tile_canvas = h->d_canvas;
+    a.f64 = h->env.f64.get();
+    a.u32 = h->env.u32.get();
+    a.ent_bits = L.ent.get();
+    a.sc_cache = h->env.sc.get();
+    a.env_level = h->env.level.get();
+    a.trunc_limit = h->env.trunc.get();
+    a.hdr = L.hdr.get();
+    a.blob = L.blob.get();
+    a.tile_canvas = L.canvas.get();
     a.n = h->n;
     a.autoreset = (h->flags & NPP_FLAG_AUTORESET) ? 1 : 0;
     a.fast_reset = (h->flags & NPP_FLAG_FAST_RESET) ? 1 : 0;   // in-kernel auto-resets
-    a.n_words_max = h->n_words_max;
-    a.lds_hot_cap = h->lds_hot_cap;
-    a.lanes_per_env = h->geo_g;
-    a.waves_per_block = h->geo_wpb;
-    a.lds_level = h->lds_level;
-    a.zoo = h->d_zoo;
-    a.zoo_words = h->zoo_words;
-    a.zoo_doors = h->zoo_doors;
-    a.zoo_movers = h->zoo_movers;
-    a.zoo_active = h->zoo_active;
-    a.variant = (h->geo_g == 16 && !h->zoo_active) ? h->variant : 0;   // npp_step's autotuner (or the pinned build)
+    a.n_words_max = L.n_words_max;
+    a.lds_hot_cap = h->plan.lds_hot_cap;
+    a.lanes_per_env = h->plan.g;
+    a.waves_per_block = h->plan.wpb;
+    a.lds_level = h->plan.lds_level;
+    a.zoo = L.zoo.get();
+    a.zoo_words = L.zoo_words;
+    a.zoo_doors = L.zoo_doors;
+    a.zoo_movers = L.zoo_movers;
+    a.zoo_active = h->plan.zoo_active;
+    a.variant = (h->plan.g == 16 && !h->plan.zoo_active) ? h->tune.variant : 0;   // npp_step's autotuner (or the pinned build)
     return a;
 }
 
@@ -416,133 +513,107 @@ void fill_out(KernelArgs &a, const npp_step_out *o) {
 // The render kernels read the tile layer from a per-level coverage canvas (npp_render.hip); it is built the first time a
 // frame is asked for, so handles that never render pay neither the memory (633 600 B per level) nor the kernel.
 int ensure_canvas(npp_handle h) {
-    if (h->d_canvas) return NPP_OK;
-    const size_t bytes = (size_t)h->levels.size() * 600 * 1056 + 16;   // + 16: rows are read as aligned dword pairs
-    HIP_TRY(h, hipMalloc((void **)&h->d_canvas, bytes));
+    LevelSet &L = h->ls;
+    if (L.canvas) return NPP_OK;
+    HIP_TRY(h, L.canvas.alloc(L.levels.size() * 600 * 1056, 16));   // + 16: rows are read as aligned dword pairs
     HIP_TRY(h, launch_tile_tables(h->stream));   // idempotent: every handle of a device writes the same bytes
-    HIP_TRY(h, launch_tile_canvas(h->d_hdr, h->d_blob, h->d_canvas, (int)h->levels.size(), h->stream));
-    return NPP_OK;
-}
-
-int ensure_gv_tables(npp_handle h, float **gh) {
-    const size_t nl = h->levels.size();
-    HIP_TRY(h, hipMalloc((void **)&h->d_gv_v, nl * 176 * 100));
-    HIP_TRY(h, hipMalloc((void **)&h->d_gv_p, nl * 600 * 1056 + 16));   // + 16: row slices are read as four aligned dwords
-    HIP_TRY(h, hipMalloc((void **)gh, nl * 600 * 100 * sizeof(float)));
-    KernelArgs a = base_args(h);
-    HIP_TRY(h, launch_gv_static(a, (int)nl, h->d_gv_p, *gh, h->d_gv_v, h->stream));
+    HIP_TRY(h, launch_tile_canvas(L.hdr.get(), L.blob.get(), L.canvas.get(), (int)L.levels.size(), h->stream));
     return NPP_OK;
 }
 
 int ensure_gv(npp_handle h) {
     if (int rc = ensure_canvas(h)) return rc;
-    if (h->d_gv_h) return NPP_OK;
-    float *gh = nullptr;
-    if (int rc = ensure_gv_tables(h, &gh)) {   // nothing half-built stays behind: the next call starts over (d_gv_h is the marker)
-        hipFree(h->d_gv_v); hipFree(h->d_gv_p); hipFree(gh);
-        h->d_gv_v = nullptr; h->d_gv_p = nullptr;
-        return rc;
-    }
-    h->d_gv_h = gh;
-    if (!h->d_gv_order) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_gv_order, (size_t)h->n * sizeof(uint32_t)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_gv_cost, (size_t)h->n * sizeof(uint32_t)));
-        HIP_TRY(h, hipMemsetAsync(h->d_gv_cost, 0, (size_t)h->n * sizeof(uint32_t), h->stream));
-        h->gv_launches = 0;   // the first launch builds an order (any permutation) from the zero costs
+    if (h->ls.gv.h) return NPP_OK;
+    const size_t nl = h->ls.levels.size();
+    GvTables t;   // complete or not at all: a failure leaves nothing behind and the next call starts over
+    HIP_TRY(h, t.v.alloc(nl * 176 * 100));
+    HIP_TRY(h, t.p.alloc(nl * 600 * 1056, 16));   // + 16: row slices are read as four aligned dwords
+    HIP_TRY(h, t.h.alloc(nl * 600 * 100));
+    HIP_TRY(h, launch_gv_static(base_args(h), (int)nl, t.p.get(), t.h.get(), t.v.get(), h->stream));
+    h->ls.gv = std::move(t);
+    Orders &o = h->ord;
+    if (!o.gv_order) {
+        HIP_TRY(h, o.gv_order.alloc(h->n));
+        HIP_TRY(h, o.gv_cost.alloc(h->n));
+        HIP_TRY(h, hipMemsetAsync(o.gv_cost.get(), 0, o.gv_cost.bytes(), h->stream));
+        o.gv_launches = 0;   // the first launch builds an order (any permutation) from the zero costs
     }
 #ifdef NPP_GV_SPLIT
-    if (!h->d_gv_x) {   // (A/B builds of the split cell pass) sized by the number of envs, not by the level set: kept across npp_load_levels
-        HIP_TRY(h, hipMalloc((void **)&h->d_gv_x, (size_t)h->n * GV_XSTRIDE));
+    if (!o.gv_x) {   // (A/B builds of the split cell pass) sized by the number of envs, not by the level set: kept across npp_load_levels
+        HIP_TRY(h, o.gv_x.alloc((size_t)h->n * GV_XSTRIDE));
     }
 #endif
     return NPP_OK;
 }
 
-void free_reach(npp_handle h) {
-    hipFree(h->d_rhdr); hipFree(h->d_rblob); hipFree(h->d_rkey); hipFree(h->d_rcache); hipFree(h->s_rkey); hipFree(h->s_rcache);
-    hipFree(h->rmiss.stamp); hipFree(h->rmiss.raw); hipFree(h->rmiss.epoch); hipFree(h->rmiss.last_episode);
-    h->d_rhdr = nullptr; h->d_rblob = nullptr; h->d_rkey = nullptr; h->d_rcache = nullptr; h->s_rkey = nullptr; h->s_rcache = nullptr;
-    h->rmiss = {nullptr, nullptr, nullptr, nullptr};
-    h->s_reach = 0;
-}
-
 // The reachability tables (npp_reach.cpp) are built the first time the observation is asked for: ~1 ms of host work and
 // ~260 KB of HBM per level, which handles that never ask for it do not pay.
-int ensure_reach_alloc(npp_handle h, const std::vector<ReachHdr> &hdrs, const std::vector<unsigned char> &blob, bool any_miss) {
-    const size_t N = (size_t)h->n, nl = hdrs.size();
-    HIP_TRY(h, hipMalloc((void **)&h->d_rblob, blob.size() + 16));
-    HIP_TRY(h, hipMemcpy(h->d_rblob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc((void **)&h->d_rkey, sizeof(uint32_t) * N));
-    HIP_TRY(h, hipMemset(h->d_rkey, 0, sizeof(uint32_t) * N));
-    HIP_TRY(h, hipMalloc((void **)&h->d_rcache, sizeof(float) * (REACH_DIM + 1) * N));
-    HIP_TRY(h, hipMemset(h->d_rcache, 0, sizeof(float) * (REACH_DIM + 1) * N));
-    if (any_miss) {   // 13.2 KB per env: 108 MB at 8192 envs
-        HIP_TRY(h, hipMalloc((void **)&h->rmiss.stamp, sizeof(uint32_t) * REACH_CELLS * N));
-        HIP_TRY(h, hipMemset(h->rmiss.stamp, 0, sizeof(uint32_t) * REACH_CELLS * N));
-        HIP_TRY(h, hipMalloc((void **)&h->rmiss.raw, sizeof(double) * REACH_CELLS * N));
-        HIP_TRY(h, hipMalloc((void **)&h->rmiss.epoch, sizeof(uint32_t) * N));
-        HIP_TRY(h, hipMemset(h->rmiss.epoch, 0, sizeof(uint32_t) * N));
-        HIP_TRY(h, hipMalloc((void **)&h->rmiss.last_episode, sizeof(uint32_t) * N));
-        HIP_TRY(h, hipMemset(h->rmiss.last_episode, 0xff, sizeof(uint32_t) * N));
-    }
-    ReachHdr *d = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&d, sizeof(ReachHdr) * nl));
-    h->d_rhdr = d;
-    HIP_TRY(h, hipMemcpy(d, hdrs.data(), sizeof(ReachHdr) * nl, hipMemcpyHostToDevice));
-    return NPP_OK;
-}
-
 int ensure_reach(npp_handle h) {
-    if (h->d_rhdr) return NPP_OK;
-    const size_t nl = h->levels.size();
+    if (h->ls.reach.hdr) return NPP_OK;
+    const size_t N = (size_t)h->n, nl = h->ls.levels.size();
     std::vector<ReachHdr> hdrs(nl);
     std::vector<unsigned char> blob;
     bool any_miss = false;
     for (size_t i = 0; i < nl; i++) {
         ReachBuilt R;
-        build_reach(h->levels[i], R);
+        build_reach(h->ls.levels[i], R);
         if (!R.hdr.supported)
             return fail(h, NPP_ERR_UNSUPPORTED, "npp_reachability: level " + std::to_string(i) + ": " + R.note +
                                                     " (outside the restated part of the reference's reachability code, see DESIGN.md)");
         any_miss = any_miss || R.hdr.miss_exit;
         pack_reach(R, hdrs[i], blob);
     }
-    const int rc = ensure_reach_alloc(h, hdrs, blob, any_miss);
-    if (rc != NPP_OK) {   // a failed allocation / copy must not leave half a table set behind (d_rhdr is the "complete" marker)
-        const std::string msg = h->err;
-        free_reach(h);
-        h->err = msg;
+    Reach r;   // complete or not at all: a failed allocation / copy leaves nothing behind
+    HIP_TRY(h, r.blob.alloc(blob.size(), 16));
+    HIP_TRY(h, hipMemcpy(r.blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, r.key.alloc(N));
+    HIP_TRY(h, hipMemset(r.key.get(), 0, r.key.bytes()));
+    HIP_TRY(h, r.cache.alloc((REACH_DIM + 1) * N));
+    HIP_TRY(h, hipMemset(r.cache.get(), 0, r.cache.bytes()));
+    if (any_miss) {   // 13.2 KB per env: 108 MB at 8192 envs
+        HIP_TRY(h, r.stamp.alloc(REACH_CELLS * N));
+        HIP_TRY(h, hipMemset(r.stamp.get(), 0, r.stamp.bytes()));
+        HIP_TRY(h, r.raw.alloc(REACH_CELLS * N));
+        HIP_TRY(h, r.epoch.alloc(N));
+        HIP_TRY(h, hipMemset(r.epoch.get(), 0, r.epoch.bytes()));
+        HIP_TRY(h, r.last_episode.alloc(N));
+        HIP_TRY(h, hipMemset(r.last_episode.get(), 0xff, r.last_episode.bytes()));
     }
-    return rc;
+    HIP_TRY(h, r.hdr.alloc(nl));
+    HIP_TRY(h, hipMemcpy(r.hdr.get(), hdrs.data(), r.hdr.bytes(), hipMemcpyHostToDevice));
+    h->ls.reach = std::move(r);
+    return NPP_OK;
 }
 
-// level pool: read the device's env_level / d_trunc back into the host mirrors (synchronises; only after a draw)
+// level pool: read the device's env_level / trunc back into the host mirrors (synchronises; only after a draw)
 int pull_levels(npp_handle h) {
-    if (!h->pool_dirty) return NPP_OK;
+    if (!h->pool.dirty) return NPP_OK;
     HIP_TRY(h, join_streams(h));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->env_level.data(), h->d_env_level, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(h->trunc.data(), h->d_trunc, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost));
-    h->pool_dirty = false;
+    HIP_TRY(h, hipMemcpy(h->env_level.data(), h->env.level.get(), h->env.level.bytes(), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(h->trunc.data(), h->env.trunc.get(), h->env.trunc.bytes(), hipMemcpyDeviceToHost));
+    h->pool.dirty = false;
     return NPP_OK;
 }
 
 void level_trunc_table(npp_handle h) {
-    if (h->level_trunc.size() == h->levels.size()) return;
-    h->level_trunc.resize(h->levels.size());
-    for (size_t i = 0; i < h->levels.size(); i++) {
+    LevelSet &L = h->ls;
+    if (L.level_trunc.size() == L.levels.size()) return;
+    L.level_trunc.resize(L.levels.size());
+    for (size_t i = 0; i < L.levels.size(); i++) {
         ReachBuilt R;
-        build_reach(h->levels[i], R);
-        h->level_trunc[i] = truncation_limit_for_area(R.spawn_area);
+        build_reach(L.levels[i], R);
+        L.level_trunc[i] = truncation_limit_for_area(R.spawn_area);
     }
 }
 
 // level pool + dynamic truncation: the per-level limits on the device, for the draw kernel
 int upload_level_trunc(npp_handle h) {
+    LevelSet &L = h->ls;
     level_trunc_table(h);
-    if (!h->d_level_trunc) HIP_TRY(h, hipMalloc((void **)&h->d_level_trunc, sizeof(int32_t) * h->levels.size()));
+    if (!L.d_level_trunc) HIP_TRY(h, L.d_level_trunc.alloc(L.levels.size()));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->d_level_trunc, h->level_trunc.data(), sizeof(int32_t) * h->levels.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(L.d_level_trunc.get(), L.level_trunc.data(), L.d_level_trunc.bytes(), hipMemcpyHostToDevice));
     return NPP_OK;
 }
 
@@ -551,9 +622,9 @@ int apply_dynamic_truncation(npp_handle h, const uint8_t *mask) {
     if (int rc = pull_levels(h)) return rc;
     level_trunc_table(h);
     for (int e = 0; e < h->n; e++)
-        if (!mask || mask[e]) h->trunc[e] = h->level_trunc[h->env_level[e]];
+        if (!mask || mask[e]) h->trunc[e] = h->ls.level_trunc[h->env_level[e]];
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->d_trunc, h->trunc.data(), sizeof(int32_t) * (size_t)h->n, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->env.trunc.get(), h->trunc.data(), h->env.trunc.bytes(), hipMemcpyHostToDevice));
     return NPP_OK;
 }
 
@@ -561,15 +632,15 @@ int apply_dynamic_truncation(npp_handle h, const uint8_t *mask) {
 // any later reset is a Simulator.reset(), after which Entity.index no longer starts at 0 (see ZOO_HEAD in npp_internal.hpp)
 int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, int automatic = 0) {
     if (!h) return NPP_ERR_INVALID;
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_reset: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_reset: no levels loaded");
     ON_DEVICE_JOINED(h);
     KernelArgs a = base_args(h);
     a.reset_fresh = fresh;
     a.fast_reset = fresh ? 0 : fast;
     a.reset_auto = automatic;
     if (env_mask) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_mask, env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-        a.reset_mask = h->d_mask;
+        HIP_TRY(h, hipMemcpyAsync(h->env.mask.get(), env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+        a.reset_mask = h->env.mask.get();
     }
     HIP_TRY(h, launch_reset(a, h->stream));
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));  // env_mask is caller memory: finish the copy
@@ -581,27 +652,28 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
 // under the draw's device mask, and, when `out` is given, their observation rows are rewritten by a masked observe launch.
 // The caller has joined the streams.
 int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_out *out) {
+    const LevelSet &L = h->ls;
     PoolArgs p;
     p.n = h->n;
     p.flags = d_flags;
     p.bits = bits;
-    p.cdf = h->d_pool_cdf;
-    p.n_levels = (int)h->levels.size();
-    p.last = h->pool_last;
-    p.seed = h->pool_seed;
-    p.count = h->d_pool_count;
-    p.env_level = h->d_env_level;
-    p.trunc = h->d_trunc;
-    p.level_trunc = h->dyn_trunc ? h->d_level_trunc : nullptr;
-    p.changed = h->d_pool_changed;
+    p.cdf = L.pool_cdf.get();
+    p.n_levels = (int)L.levels.size();
+    p.last = h->pool.last;
+    p.seed = h->pool.seed;
+    p.count = h->env.count.get();
+    p.env_level = h->env.level.get();
+    p.trunc = h->env.trunc.get();
+    p.level_trunc = h->dyn_trunc ? L.d_level_trunc.get() : nullptr;
+    p.changed = h->pool.changed.get();
     HIP_TRY(h, launch_pool_draw(p, h->stream));
-    h->pool_dirty = true;
+    h->pool.dirty = true;
     KernelArgs a = base_args(h);
-    a.reset_mask = h->d_pool_changed;
+    a.reset_mask = h->pool.changed.get();
     a.reset_fresh = 1;
     a.fast_reset = 0;   // (base_args carries the auto-reset's NPP_FLAG_FAST_RESET) a new level is a Simulator.reset
     HIP_TRY(h, launch_reset(a, h->stream));
-    if (h->d_rkey) HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, h->d_rkey, h->d_rcache, h->rmiss, h->stream));
+    if (L.reach.key) HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, L.reach.key.get(), L.reach.cache.get(), L.reach.miss(), h->stream));
     if (out) {
         KernelArgs o = base_args(h);
         o.n_ticks = 0;
@@ -609,10 +681,17 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
         o.autoreset = 0;
         fill_out(o, out);
         o.out.flags = nullptr; o.out.reward = nullptr; o.out.frames = nullptr; o.out.terminal_state = nullptr; o.out.work = nullptr;
-        o.obs_mask = h->d_pool_changed;
+        o.obs_mask = h->pool.changed.get();
         HIP_TRY(h, launch_step(o, h->stream));
     }
     return NPP_OK;
+}
+
+// snapshot: `snap` <- a copy of `live` on the stream, (re)allocated when the live buffer's size differs from the copy's
+template <class T> hipError_t mirror(DevBuf<T> &snap, const DevBuf<T> &live, hipStream_t st) {
+    if (snap.size() != live.size())
+        if (hipError_t e = snap.alloc(live.size())) return e;
+    return hipMemcpyAsync(snap.get(), live.get(), live.bytes(), hipMemcpyDeviceToDevice, st);
 }
 
 }  // namespace
@@ -635,23 +714,17 @@ int npp_create(int n_envs, int device_id, unsigned flags, npp_handle *out) {
     h->device = device_id;
     h->flags = flags;
     size_t N = (size_t)n_envs;
-    hipError_t e1 = hipMalloc((void **)&h->d_f64, sizeof(double) * NF64 * N);
-    hipError_t e2 = hipMalloc((void **)&h->d_u32, sizeof(uint32_t) * NU32 * N);
-    hipError_t e3 = hipMalloc((void **)&h->d_env_level, sizeof(int32_t) * N);
-    hipError_t e4 = hipMalloc((void **)&h->d_trunc, sizeof(int32_t) * N);
-    hipError_t e5 = hipMalloc((void **)&h->d_mask, N);
-    hipError_t e6 = hipMalloc((void **)&h->d_sc_cache, sizeof(float) * 48 * N);
-    hipError_t e7 = hipMalloc((void **)&h->d_pool_count, sizeof(uint32_t) * N);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess || e6 != hipSuccess ||
-        e7 != hipSuccess) {
-        npp_destroy(h);
+    EnvState &s = h->env;
+    if (s.f64.alloc(NF64 * N) != hipSuccess || s.u32.alloc(NU32 * N) != hipSuccess || s.level.alloc(N) != hipSuccess ||
+        s.trunc.alloc(N) != hipSuccess || s.mask.alloc(N) != hipSuccess || s.sc.alloc(48 * N) != hipSuccess || s.count.alloc(N) != hipSuccess) {
+        delete h;
         return fail(nullptr, NPP_ERR_HIP, "npp_create: hipMalloc failed");
     }
     h->env_level.assign(N, 0);
     h->trunc.assign(N, 10000);  // MAX_TIME_IN_FRAMES fallback (gym_environment/constants.py:8)
-    hipMemcpy(h->d_trunc, h->trunc.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice);
-    hipMemset(h->d_env_level, 0, sizeof(int32_t) * N);
-    hipMemset(h->d_pool_count, 0, sizeof(uint32_t) * N);
+    hipMemcpy(s.trunc.get(), h->trunc.data(), s.trunc.bytes(), hipMemcpyHostToDevice);
+    hipMemset(s.level.get(), 0, s.level.bytes());
+    hipMemset(s.count.get(), 0, s.count.bytes());
     *out = h;
     return NPP_OK;
 }
@@ -660,43 +733,17 @@ int npp_destroy(npp_handle h) {
     if (!h) return NPP_OK;
     DeviceGuard dg(h->device);
     hipDeviceSynchronize();
-    hipFree(h->d_f64); hipFree(h->d_u32); hipFree(h->d_ent); hipFree(h->d_env_level); hipFree(h->d_trunc);
-    hipFree(h->d_mask); hipFree(h->d_blob); hipFree(h->d_hdr); hipFree(h->d_sc_cache); hipFree(h->d_canvas);
-    hipFree(h->d_gv_h); hipFree(h->d_gv_v); hipFree(h->d_gv_p);
-    hipFree(h->d_gv_x); hipFree(h->d_gv_order); hipFree(h->d_gv_cost); hipFree(h->d_wg_order); hipFree(h->d_wg_cost); hipFree(h->d_pf_order); hipFree(h->d_pf_cost);
-    for (auto &e : h->tune_ev)
-        if (e) hipEventDestroy(e);
-    if (h->split_stream) { hipStreamDestroy(h->split_stream); hipEventDestroy(h->split_ev[0]); hipEventDestroy(h->split_ev[1]); }
-    for (auto &e : h->ov_ev)
-        if (e) hipEventDestroy(e);
-    for (hipStream_t st : h->owned) hipStreamDestroy(st);
-    for (auto &e : h->cal_ev)
-        if (e) hipEventDestroy(e);
-    for (int q = 0; q < 4; q++)
-        if (h->part_ev[q]) hipEventDestroy(h->part_ev[q]);
-    for (int k = 0; k < 2; k++)
-        for (int p = 0; p < 2; p++)
-            if (h->side_ev[k][p]) hipEventDestroy(h->side_ev[k][p]);
-    hipFree(h->d_phase);
-    hipFree(h->d_fs_frames); hipFree(h->d_fs_state);
-    hipFree(h->d_pool_cdf); hipFree(h->d_pool_count); hipFree(h->d_pool_flags); hipFree(h->d_pool_changed); hipFree(h->d_level_trunc);
-    hipFree(h->s_level); hipFree(h->s_count); hipFree(h->s_trunc);
-    free_reach(h);
-    hipFree(h->s_f64); hipFree(h->s_u32); hipFree(h->s_ent); hipFree(h->s_sc); hipFree(h->d_zoo); hipFree(h->s_zoo);
     delete h;
     return NPP_OK;
 }
 
 int npp_set_stream(npp_handle h, void *hip_stream) {
     if (!h) return NPP_ERR_INVALID;
-    if (h->stream != (hipStream_t)hip_stream) {   // the autotuner's window events live on the old stream: start its cycle over
-        h->tune_state = 0; h->tune_count = 0; h->tuned = h->variant_pin >= 0;
-        h->variant = h->variant_pin >= 0 ? h->variant_pin : 0;
-    }
-    if (h->live_parts > 1 || h->n_cuts) {   // a split step may still be in flight: its other streams join the OLD stream
+    if (h->stream != (hipStream_t)hip_stream) h->tune.restart();   // the autotuner's window events live on the old stream: start its cycle over
+    if (h->ov.live_parts > 1 || h->ov.n_cuts) {   // a split step may still be in flight: its other streams join the OLD stream
         ON_DEVICE_JOINED(h);
     }
-    if (h->stream != (hipStream_t)hip_stream) h->owned_valid = false;   // (observation overlap) streams are chosen again at the next split step
+    if (h->stream != (hipStream_t)hip_stream) h->ov.owned_valid = false;   // (observation overlap) streams are chosen again at the next split step
     h->stream = (hipStream_t)hip_stream;
     return NPP_OK;
 }
@@ -710,78 +757,61 @@ int npp_sync(npp_handle h) {
 
 int npp_snapshot(npp_handle h) {
     if (!h) return NPP_ERR_INVALID;
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_snapshot: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_snapshot: no levels loaded");
     ON_DEVICE_JOINED(h);
-    size_t N = (size_t)h->n;
-    if (!h->s_f64) {
-        HIP_TRY(h, hipMalloc((void **)&h->s_f64, sizeof(double) * NF64 * N));
-        HIP_TRY(h, hipMalloc((void **)&h->s_u32, sizeof(uint32_t) * NU32 * N));
-        HIP_TRY(h, hipMalloc((void **)&h->s_sc, sizeof(float) * 48 * N));
-        HIP_TRY(h, hipMalloc((void **)&h->s_level, sizeof(int32_t) * N));
-        HIP_TRY(h, hipMalloc((void **)&h->s_count, sizeof(uint32_t) * N));
-        HIP_TRY(h, hipMalloc((void **)&h->s_trunc, sizeof(int32_t) * N));
+    Snapshot &s = h->snap;
+    const EnvState &v = h->env;
+    const LevelSet &L = h->ls;
+    HIP_TRY(h, mirror(s.f64, v.f64, h->stream));
+    HIP_TRY(h, mirror(s.u32, v.u32, h->stream));
+    HIP_TRY(h, mirror(s.ent, L.ent, h->stream));
+    HIP_TRY(h, mirror(s.sc, v.sc, h->stream));
+    HIP_TRY(h, mirror(s.level, v.level, h->stream));
+    HIP_TRY(h, mirror(s.count, v.count, h->stream));
+    HIP_TRY(h, mirror(s.trunc, v.trunc, h->stream));
+    if (L.zoo) HIP_TRY(h, mirror(s.zoo, L.zoo, h->stream));
+    s.reach = false;
+    if (L.reach.key) {
+        HIP_TRY(h, mirror(s.rkey, L.reach.key, h->stream));
+        HIP_TRY(h, mirror(s.rcache, L.reach.cache, h->stream));
+        s.reach = true;
     }
-    if (h->s_words != h->n_words_max) {
-        hipFree(h->s_ent);
-        h->s_ent = nullptr;
-        HIP_TRY(h, hipMalloc((void **)&h->s_ent, sizeof(uint32_t) * (size_t)h->n_words_max * N));
-        h->s_words = h->n_words_max;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->s_f64, h->d_f64, sizeof(double) * NF64 * N, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->s_u32, h->d_u32, sizeof(uint32_t) * NU32 * N, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->s_ent, h->d_ent, sizeof(uint32_t) * (size_t)h->n_words_max * N, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->s_sc, h->d_sc_cache, sizeof(float) * 48 * N, hipMemcpyDeviceToDevice, h->stream));
-    // (level pool) each env's level, draw count and truncation limit go with its state
-    HIP_TRY(h, hipMemcpyAsync(h->s_level, h->d_env_level, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->s_count, h->d_pool_count, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->s_trunc, h->d_trunc, sizeof(int32_t) * N, hipMemcpyDeviceToDevice, h->stream));
-    if (h->d_zoo) {
-        if (!h->s_zoo) HIP_TRY(h, hipMalloc((void **)&h->s_zoo, sizeof(double) * (size_t)h->zoo_words * N));
-        HIP_TRY(h, hipMemcpyAsync(h->s_zoo, h->d_zoo, sizeof(double) * (size_t)h->zoo_words * N, hipMemcpyDeviceToDevice, h->stream));
-    }
-    h->s_reach = 0;
-    if (h->d_rkey) {   // the cached reachability vector is part of what the next observation returns
-        if (!h->s_rkey) {
-            HIP_TRY(h, hipMalloc((void **)&h->s_rkey, sizeof(uint32_t) * N));
-            HIP_TRY(h, hipMalloc((void **)&h->s_rcache, sizeof(float) * (REACH_DIM + 1) * N));
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->s_rkey, h->d_rkey, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->s_rcache, h->d_rcache, sizeof(float) * (REACH_DIM + 1) * N, hipMemcpyDeviceToDevice, h->stream));
-        h->s_reach = 1;
-    }
-    h->s_ovr = h->ovr;
-    h->s_gen = h->assign_gen;
+    s.ovr = h->ovr;
+    s.gen = h->assign_gen;
     return NPP_OK;
 }
 
 int npp_restore(npp_handle h, const uint8_t *env_mask) {
     if (!h) return NPP_ERR_INVALID;
-    if (!h->s_f64 || h->s_gen != h->assign_gen)
-        return fail(h, NPP_ERR_STATE, "npp_restore: no snapshot for the current level assignment");
+    const Snapshot &s = h->snap;
+    if (!s.f64 || s.gen != h->assign_gen) return fail(h, NPP_ERR_STATE, "npp_restore: no snapshot for the current level assignment");
     ON_DEVICE_JOINED(h);
+    const LevelSet &L = h->ls;
+    EnvState &v = h->env;
     KernelArgs a = base_args(h);
     if (env_mask) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_mask, env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-        a.reset_mask = h->d_mask;
+        HIP_TRY(h, hipMemcpyAsync(v.mask.get(), env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+        a.reset_mask = v.mask.get();
     }
-    HIP_TRY(h, launch_restore(a, h->s_f64, h->s_u32, h->s_ent, h->s_sc, h->d_zoo ? h->s_zoo : nullptr, h->stream));
-    if (h->d_rkey)   // no cache in the snapshot (taken before the first npp_reachability): the restored envs start without one
-        HIP_TRY(h, launch_reach_restore(a, h->s_reach ? h->s_rkey : nullptr, h->s_rcache, h->d_rkey, h->d_rcache, h->rmiss, h->stream));
-    if (h->pool_ever) {   // the pool changed levels since npp_load_levels: the snapshot's levels come back with the state
-        HIP_TRY(h, launch_pool_restore(h->n, a.reset_mask, h->s_level, h->s_count, h->s_trunc, h->d_env_level, h->d_pool_count, h->d_trunc,
-                                       h->stream));
-        h->pool_dirty = true;
+    HIP_TRY(h, launch_restore(a, s.f64.get(), s.u32.get(), s.ent.get(), s.sc.get(), L.zoo ? s.zoo.get() : nullptr, h->stream));
+    if (L.reach.key)   // no cache in the snapshot (taken before the first npp_reachability): the restored envs start without one
+        HIP_TRY(h, launch_reach_restore(a, s.reach ? s.rkey.get() : nullptr, s.rcache.get(), L.reach.key.get(), L.reach.cache.get(),
+                                        L.reach.miss(), h->stream));
+    if (h->pool.ever) {   // the pool changed levels since npp_load_levels: the snapshot's levels come back with the state
+        HIP_TRY(h, launch_pool_restore(h->n, a.reset_mask, s.level.get(), s.count.get(), s.trunc.get(), v.level.get(), v.count.get(),
+                                       v.trunc.get(), h->stream));
+        h->pool.dirty = true;
     }
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));
     // the restored zoo blocks carry the repositioning flags / coordinates of the snapshot (head words 3..7): the host's
     // view of them (which decides whether the zoo kernels run) is restored with them
-    if (h->s_ovr.size() == h->ovr.size()) {
+    if (s.ovr.size() == h->ovr.size()) {
         for (int e = 0; e < h->n; e++)
-            if (!env_mask || env_mask[e]) h->ovr[e] = h->s_ovr[e];
+            if (!env_mask || env_mask[e]) h->ovr[e] = s.ovr[e];
         h->n_ovr = 0;
         for (int e = 0; e < h->n; e++) h->n_ovr += h->ovr[e] != 0;
         plan_geometry(h, true);   // restoring a checkpoint every few hundred steps must not keep the autotuner in its warm-up
-    } else if (h->pool_ever) {
+    } else if (h->pool.ever) {
         plan_geometry(h, true);
     }
     return NPP_OK;
@@ -799,18 +829,22 @@ int npp_set_launch_geometry(npp_handle h, int lanes_per_env, int waves_per_block
 
 int npp_get_launch_geometry(npp_handle h, int *lanes_per_env, int *waves_per_block) {
     if (!h) return NPP_ERR_INVALID;
-    if (lanes_per_env) *lanes_per_env = h->geo_g;
-    if (waves_per_block) *waves_per_block = h->geo_wpb;
+    if (lanes_per_env) *lanes_per_env = h->plan.g;
+    if (waves_per_block) *waves_per_block = h->plan.wpb;
     return NPP_OK;
 }
 
 int npp_num_envs(npp_handle h) { return h ? h->n : 0; }
-int npp_num_levels(npp_handle h) { return h ? (int)h->levels.size() : 0; }
+int npp_num_levels(npp_handle h) { return h ? (int)h->ls.levels.size() : 0; }
 
 int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, int n_levels) {
     if (!h || !blob || !offsets || n_levels <= 0) return fail(h, NPP_ERR_INVALID, "npp_load_levels: bad arguments");
     ON_DEVICE_JOINED(h);
-    std::vector<CompiledLevel> lv(n_levels);
+    // The new set is built whole in `next` and swapped in only once it is complete and fits: a failed call leaves the previous
+    // set loaded.  Everything that can fail short of a device error comes before the first device write.
+    LevelSet next;
+    std::vector<CompiledLevel> &lv = next.levels;
+    lv.resize(n_levels);
     for (int i = 0; i < n_levels; i++) {
         std::string err;
         if (offsets[i + 1] < offsets[i] || !compile_level(blob + offsets[i], offsets[i + 1] - offsets[i], lv[i], err))
@@ -825,11 +859,8 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     }
     // ---- pack the blob
     std::vector<unsigned char> host;
-    std::vector<LevelHdr> hdrs(n_levels);
-    int words_max = 1;
-    uint32_t hot_max = 0;
-    bool any_zoo = false;
-    int zoo_doors = 0, zoo_movers = 0;
+    std::vector<LevelHdr> &hdrs = next.hdrs;
+    hdrs.resize(n_levels);
     auto append = [&](const void *p, size_t bytes, uint32_t align) -> uint32_t {
         uint32_t off = align_up((uint32_t)host.size(), align);
         host.resize(off + bytes);
@@ -879,10 +910,9 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
             if ((L.mov_meta[m] & 7u) == MK_BALL) { H.ball_first = (uint32_t)m; break; }
         H.db_count = L.db_count;
         for (int k = 0; k < 5; k++) H.locked_slots[k] = L.locked_slots[k];
-        if (L.has_zoo) any_zoo = true;
         // every level's block is initialised by the reset kernel (locked doors have an edge counter too)
-        zoo_doors = std::max(zoo_doors, (int)H.n_zdoor);
-        zoo_movers = std::max(zoo_movers, (int)H.n_mov);
+        next.zoo_doors = std::max(next.zoo_doors, (int)H.n_zdoor);
+        next.zoo_movers = std::max(next.zoo_movers, (int)H.n_mov);
         H.n_seg = (uint32_t)L.segs.size();
         H.n_ent = (uint32_t)L.ent_x.size();
         H.n_words = (uint32_t)L.ent_init_words.size();
@@ -894,58 +924,43 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
             H.sw_x = L.ent_x[L.obs_switch]; H.sw_y = L.ent_y[L.obs_switch];
             H.door_x = L.ent_x[L.obs_door]; H.door_y = L.ent_y[L.obs_door];
         }
-        words_max = std::max(words_max, (int)H.n_words);
+        next.n_words_max = std::max(next.n_words_max, (int)H.n_words);
         H.fits_lds = 1;
-        hot_max = std::max(hot_max, hot_bytes);
+        next.hot_max = std::max(next.hot_max, hot_bytes);
     }
-    // ---- upload (replaces the previous set)
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    hipFree(h->d_blob); h->d_blob = nullptr;
-    hipFree(h->d_canvas); h->d_canvas = nullptr;
-    hipFree(h->d_gv_h); h->d_gv_h = nullptr;
-    hipFree(h->d_gv_v); h->d_gv_v = nullptr;
-    hipFree(h->d_gv_p); h->d_gv_p = nullptr;
-    free_reach(h);
-    hipFree(h->d_hdr); h->d_hdr = nullptr;
-    hipFree(h->d_ent); h->d_ent = nullptr;
-    hipFree(h->d_zoo); h->d_zoo = nullptr;
-    hipFree(h->s_zoo); h->s_zoo = nullptr;
-    // a new level set turns the level pool off (its weights were per level of the old set); draw counts restart
-    hipFree(h->d_pool_cdf); h->d_pool_cdf = nullptr;
-    hipFree(h->d_level_trunc); h->d_level_trunc = nullptr;
-    h->pool_on = h->pool_ever = h->pool_dirty = false;
-    h->pool_w.clear();
-    HIP_TRY(h, hipMemset(h->d_pool_count, 0, sizeof(uint32_t) * (size_t)h->n));
-    (void)any_zoo;
-    zoo_block_plan(lv, zoo_doors, zoo_movers);
+    zoo_block_plan(lv, next.zoo_doors, next.zoo_movers);
     for (int i = 0; i < n_levels; i++)   // round-1 fault: a block sized over zoo levels only was overrun
-        if ((int)hdrs[i].n_zdoor > zoo_doors || (int)hdrs[i].n_mov > zoo_movers)
+        if ((int)hdrs[i].n_zdoor > next.zoo_doors || (int)hdrs[i].n_mov > next.zoo_movers)
             return fail(h, NPP_ERR_STATE, "npp_load_levels: zoo block plan does not cover level " + std::to_string(i));
-    h->zoo_words = zoo_words_for(zoo_doors, zoo_movers);
-    h->zoo_doors = zoo_doors;
-    h->zoo_movers = zoo_movers;
-    HIP_TRY(h, hipMalloc((void **)&h->d_zoo, sizeof(double) * (size_t)h->zoo_words * h->n));
-    HIP_TRY(h, hipMemset(h->d_zoo, 0, sizeof(double) * (size_t)h->zoo_words * h->n));
+    next.zoo_words = zoo_words_for(next.zoo_doors, next.zoo_movers);
+    {   // the plan the call ends with (every env on level 0, nothing repositioned, the pool off) must fit LDS
+        const Plan p = make_plan(next, h->n, std::vector<int32_t>((size_t)h->n, 0), h->lanes_per_env, h->waves_per_block, false, nullptr);
+        if (lds_bytes(p.lds_hot_cap, next.n_words_max, (64 / p.g) * p.wpb, p.zoo_active ? next.zoo_words : 0) > LDS_BUDGET)
+            return fail(h, NPP_ERR_INVALID, "npp_load_levels: entity tables exceed LDS");
+    }
+    const size_t N = (size_t)h->n;
+    HIP_TRY(h, next.zoo.alloc((size_t)next.zoo_words * N));
+    HIP_TRY(h, next.blob.alloc(host.size(), 16));
+    HIP_TRY(h, next.hdr.alloc(n_levels));
+    HIP_TRY(h, next.ent.alloc((size_t)next.n_words_max * N));
+    // ---- upload and swap in (queued work may still read the old set: it is released at the swap)
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemset(h->env.count.get(), 0, h->env.count.bytes()));   // a new level set turns the level pool off; draw counts restart
+    HIP_TRY(h, hipMemset(next.zoo.get(), 0, next.zoo.bytes()));
+    HIP_TRY(h, hipMemcpy(next.blob.get(), host.data(), host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(next.hdr.get(), hdrs.data(), next.hdr.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(next.ent.get(), 0, next.ent.bytes()));
+    h->ls = std::move(next);
+    // the snapshot planes of the old set's per-env buffers go with it (the snapshot no longer matches assign_gen)
+    h->snap.zoo.reset(); h->snap.rkey.reset(); h->snap.rcache.reset(); h->snap.reach = false;
+    h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
+    h->pool.w.clear();
     h->ovr.assign(h->n, 0);
     h->n_ovr = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->d_blob, host.size() + 16));
-    HIP_TRY(h, hipMemcpy(h->d_blob, host.data(), host.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc((void **)&h->d_hdr, sizeof(LevelHdr) * n_levels));
-    HIP_TRY(h, hipMemcpy(h->d_hdr, hdrs.data(), sizeof(LevelHdr) * n_levels, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc((void **)&h->d_ent, sizeof(uint32_t) * (size_t)words_max * h->n));
-    HIP_TRY(h, hipMemset(h->d_ent, 0, sizeof(uint32_t) * (size_t)words_max * h->n));
-    h->levels.swap(lv);
-    h->hdrs.swap(hdrs);
     h->assign_gen++;
-    h->n_words_max = words_max;
-    h->hot_max = hot_max;
     std::fill(h->env_level.begin(), h->env_level.end(), 0);
     plan_geometry(h);
-    if (lds_bytes(h->lds_hot_cap, h->n_words_max, (64 / h->geo_g) * h->geo_wpb, h->zoo_active ? h->zoo_words : 0) > LDS_BUDGET)
-        return fail(h, NPP_ERR_INVALID, "npp_load_levels: entity tables exceed LDS");
-    std::fill(h->env_level.begin(), h->env_level.end(), 0);
-    HIP_TRY(h, hipMemset(h->d_env_level, 0, sizeof(int32_t) * (size_t)h->n));
-    h->level_trunc.clear();
+    HIP_TRY(h, hipMemset(h->env.level.get(), 0, h->env.level.bytes()));
     if (h->dyn_trunc)
         if (int rc = apply_dynamic_truncation(h, nullptr)) return rc;
     return reset_impl(h, nullptr, 1);
@@ -953,14 +968,14 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
 
 int npp_assign_levels(npp_handle h, const int32_t *env_ids, const int32_t *level_ids, int n) {
     if (!h || !level_ids || n <= 0) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_assign_levels: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_assign_levels: no levels loaded");
     if (!env_ids && n != h->n) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: env_ids == NULL needs n == n_envs");
     ON_DEVICE_JOINED(h);
     if (int rc = pull_levels(h)) return rc;   // (level pool) the whole mirror is uploaded below
     std::vector<uint8_t> mask(h->n, 0);
     for (int i = 0; i < n; i++) {   // validate everything before touching the assignment: an error must leave host and device in step
         int e = env_ids ? env_ids[i] : i;
-        if (e < 0 || e >= h->n || level_ids[i] < 0 || level_ids[i] >= (int)h->levels.size())
+        if (e < 0 || e >= h->n || level_ids[i] < 0 || level_ids[i] >= (int)h->ls.levels.size())
             return fail(h, NPP_ERR_INVALID, "npp_assign_levels: index out of range");
     }
     for (int i = 0; i < n; i++) {
@@ -972,12 +987,13 @@ int npp_assign_levels(npp_handle h, const int32_t *env_ids, const int32_t *level
     h->assign_gen++;
     plan_geometry(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->d_env_level, h->env_level.data(), sizeof(int32_t) * (size_t)h->n, hipMemcpyHostToDevice));
-    if (h->d_rkey) {   // a new level: the env's cached reachability vector belongs to the old one
+    HIP_TRY(h, hipMemcpy(h->env.level.get(), h->env_level.data(), h->env.level.bytes(), hipMemcpyHostToDevice));
+    const Reach &r = h->ls.reach;
+    if (r.key) {   // a new level: the env's cached reachability vector belongs to the old one
         KernelArgs a = base_args(h);
-        HIP_TRY(h, hipMemcpy(h->d_mask, mask.data(), (size_t)h->n, hipMemcpyHostToDevice));
-        a.reset_mask = h->d_mask;
-        HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, h->d_rkey, h->d_rcache, h->rmiss, h->stream));
+        HIP_TRY(h, hipMemcpy(h->env.mask.get(), mask.data(), (size_t)h->n, hipMemcpyHostToDevice));
+        a.reset_mask = h->env.mask.get();
+        HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, r.key.get(), r.cache.get(), r.miss(), h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     if (h->dyn_trunc)
@@ -1002,54 +1018,56 @@ int npp_set_truncation_limit(npp_handle h, const int32_t *limits, int32_t all) {
     if (limits) h->trunc.assign(limits, limits + h->n);
     else h->trunc.assign(h->n, all);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->d_trunc, h->trunc.data(), sizeof(int32_t) * (size_t)h->n, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->env.trunc.get(), h->trunc.data(), h->env.trunc.bytes(), hipMemcpyHostToDevice));
     return NPP_OK;
 }
 
 int npp_set_dynamic_truncation(npp_handle h, int enable) {
     if (!h) return NPP_ERR_INVALID;
     h->dyn_trunc = enable != 0;
-    if (!h->dyn_trunc || h->levels.empty()) return NPP_OK;
+    if (!h->dyn_trunc || h->ls.levels.empty()) return NPP_OK;
     ON_DEVICE_JOINED(h);
-    if (h->pool_on)
+    if (h->pool.on)
         if (int rc = upload_level_trunc(h)) return rc;
     return apply_dynamic_truncation(h, nullptr);
 }
 
 int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64_t seed) {
     if (!h) return NPP_ERR_INVALID;
+    Pool &P = h->pool;
     if (!weights) {   // off: every env keeps the level it plays now
-        if (!h->pool_on) return NPP_OK;
+        if (!P.on) return NPP_OK;
         ON_DEVICE_JOINED(h);
         if (int rc = pull_levels(h)) return rc;
-        h->pool_on = false;
+        P.on = false;
         plan_geometry(h);
         return NPP_OK;
     }
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: no levels loaded");
     std::vector<double> cdf;
     int last = 0;
     std::string err;
-    if (!pool_cdf(weights, n_levels, (int)h->levels.size(), cdf, last, err)) return fail(h, NPP_ERR_INVALID, "npp_set_level_pool: " + err);
+    if (!pool_cdf(weights, n_levels, (int)h->ls.levels.size(), cdf, last, err)) return fail(h, NPP_ERR_INVALID, "npp_set_level_pool: " + err);
     if (h->n_ovr) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: an exit switch / door is repositioned (npp_set_entity_pos)");
     ON_DEVICE_JOINED(h);
     const size_t N = (size_t)h->n;
+    DevBuf<double> &d_cdf = h->ls.pool_cdf;
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the previous CDF may still be read by queued draws
-    if (!h->d_pool_cdf) HIP_TRY(h, hipMalloc((void **)&h->d_pool_cdf, sizeof(double) * cdf.size()));
-    if (!h->d_pool_changed) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_pool_changed, N));
-        HIP_TRY(h, hipMalloc((void **)&h->d_pool_flags, N));
-        HIP_TRY(h, hipMemset(h->d_pool_flags, 0, N));
+    if (!d_cdf) HIP_TRY(h, d_cdf.alloc(cdf.size()));
+    if (!P.changed) {
+        HIP_TRY(h, P.changed.alloc(N));
+        HIP_TRY(h, P.flags.alloc(N));
+        HIP_TRY(h, hipMemset(P.flags.get(), 0, N));
     }
-    HIP_TRY(h, hipMemcpy(h->d_pool_cdf, cdf.data(), sizeof(double) * cdf.size(), hipMemcpyHostToDevice));
-    if (!h->pool_on || seed != h->pool_seed) HIP_TRY(h, hipMemset(h->d_pool_count, 0, sizeof(uint32_t) * N));   // a new stream of draws
+    HIP_TRY(h, hipMemcpy(d_cdf.get(), cdf.data(), sizeof(double) * cdf.size(), hipMemcpyHostToDevice));
+    if (!P.on || seed != P.seed) HIP_TRY(h, hipMemset(h->env.count.get(), 0, h->env.count.bytes()));   // a new stream of draws
     if (h->dyn_trunc)
         if (int rc = upload_level_trunc(h)) return rc;
-    const bool was_on = h->pool_on;
-    h->pool_w.assign(weights, weights + n_levels);
-    h->pool_seed = seed;
-    h->pool_last = last;
-    h->pool_on = h->pool_ever = true;
+    const bool was_on = P.on;
+    P.w.assign(weights, weights + n_levels);
+    P.seed = seed;
+    P.last = last;
+    P.on = P.ever = true;
     // the step-variant autotuner decides once for the pool: a weight update keeps its decision unless it switches the zoo kernels
     plan_geometry(h, was_on);
     return NPP_OK;
@@ -1057,18 +1075,19 @@ int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64
 
 int npp_draw_levels(npp_handle h, const uint8_t *env_mask) {
     if (!h) return NPP_ERR_INVALID;
-    if (!h->pool_on) return fail(h, NPP_ERR_STATE, "npp_draw_levels: the level pool is off (npp_set_level_pool)");
+    if (!h->pool.on) return fail(h, NPP_ERR_STATE, "npp_draw_levels: the level pool is off (npp_set_level_pool)");
     ON_DEVICE_JOINED(h);
-    if (env_mask) HIP_TRY(h, hipMemcpyAsync(h->d_mask, env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-    else HIP_TRY(h, hipMemsetAsync(h->d_mask, 1, (size_t)h->n, h->stream));
-    if (int rc = pool_redraw(h, h->d_mask, 0xff, nullptr)) return rc;
+    uint8_t *d_mask = h->env.mask.get();
+    if (env_mask) HIP_TRY(h, hipMemcpyAsync(d_mask, env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(d_mask, 1, (size_t)h->n, h->stream));
+    if (int rc = pool_redraw(h, d_mask, 0xff, nullptr)) return rc;
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));   // env_mask is caller memory: finish the copy
     return NPP_OK;
 }
 
 int npp_env_level_view(npp_handle h, const int32_t **d_levels) {
     if (!h || !d_levels) return fail(h, NPP_ERR_INVALID, "npp_env_level_view: bad arguments");
-    *d_levels = h->d_env_level;
+    *d_levels = h->env.level.get();
     return NPP_OK;
 }
 
@@ -1089,54 +1108,48 @@ namespace {
 // the levels with a crease under the spawn, which favours variant 2 -- a first cut that tuned on launches 48 .. 288 picked it for the
 // mixed set and lost 10 %), then 9 interleaved windows of 48 launches; the decision is re-examined every 16 384 launches
 constexpr int TUNE_WARM = 256, TUNE_WINDOW = 48, TUNE_ROUNDS = 3, TUNE_AGAIN = 16384;
-// restart the tuner (new level set / assignment / geometry): the warm-up also lets the heavy-first order settle
-void tune_reset(npp_handle h) {
-    h->tune_state = 0; h->tune_count = 0; h->tuned = h->variant_pin >= 0;
-    h->variant = h->variant_pin >= 0 ? h->variant_pin : 0;
-}
 // called by npp_step before every launch; returns the variant to launch.  *pair >= 0: a measured launch -- npp_step records
-// tune_ev[2 * pair] right before and tune_ev[2 * pair + 1] right after the step kernel, so that only the kernel itself is timed
+// ev[2 * pair] right before and ev[2 * pair + 1] right after the step kernel, so that only the kernel itself is timed
 // (observation kernels and the caller's own work on the stream, whose cost varies with the state, stay outside: ADVICE r2)
 int tune_next(npp_handle h, int *pair) {
+    Tuner &T = h->tune;
     *pair = -1;
-    if (h->variant_pin >= 0) return h->variant_pin;
-    if (h->geo_g != 16 || h->zoo_active) return 0;   // only the plain G = 16 kernels have variants
-    if (h->tuned) {
+    if (T.pin >= 0) return T.pin;
+    if (h->plan.g != 16 || h->plan.zoo_active) return 0;   // only the plain G = 16 kernels have variants
+    if (T.tuned) {
         static const long again = [] { const char *ev = std::getenv("NPP_TUNE_AGAIN"); return ev ? std::atol(ev) : (long)TUNE_AGAIN; }();   // tests shorten it
-        if (++h->tune_since < again) return h->variant;
-        h->tuned = false; h->tune_state = 0; h->tune_count = TUNE_WARM; h->tune_since = 0;   // measure again, no warm-up needed
+        if (++T.since < again) return T.variant;
+        T.tuned = false; T.state = 0; T.count = TUNE_WARM; T.since = 0;   // measure again, no warm-up needed
     }
     const int n_win = 3 * TUNE_ROUNDS;
-    if (h->tune_state == 0) {   // warm-up on variant 0
-        if (++h->tune_count <= TUNE_WARM) return h->variant;
-        if (h->tune_ev.empty()) {
-            h->tune_ev.assign((size_t)2 * TUNE_WINDOW * n_win, nullptr);
-            for (auto &e : h->tune_ev)
-                if (hipEventCreate(&e) != hipSuccess) {   // no events: stay on variant 0
-                    for (auto &d : h->tune_ev)
-                        if (d) hipEventDestroy(d);
-                    h->tune_ev.clear();
-                    h->tuned = true; h->variant = 0;
+    if (T.state == 0) {   // warm-up on variant 0
+        if (++T.count <= TUNE_WARM) return T.variant;
+        if (T.ev.empty()) {
+            T.ev.resize((size_t)2 * TUNE_WINDOW * n_win);
+            for (Event &e : T.ev)
+                if (e.create(hipEventDefault) != hipSuccess) {   // no events: stay on variant 0
+                    T.ev.clear();
+                    T.tuned = true; T.variant = 0;
                     return 0;
                 }
         }
-        h->tune_state = 1; h->tune_count = 0;
+        T.state = 1; T.count = 0;
     }
-    if (h->tune_state <= n_win) {   // window w measures variant (w - 1) % 3
-        const int w = h->tune_state;
-        *pair = (w - 1) * TUNE_WINDOW + h->tune_count;
-        if (++h->tune_count == TUNE_WINDOW) { h->tune_state++; h->tune_count = 0; }
+    if (T.state <= n_win) {   // window w measures variant (w - 1) % 3
+        const int w = T.state;
+        *pair = (w - 1) * TUNE_WINDOW + T.count;
+        if (++T.count == TUNE_WINDOW) { T.state++; T.count = 0; }
         return (w - 1) % 3;
     }
     // all windows recorded: decide as soon as the last launch has been reached by the GPU (no waiting)
-    if (hipEventQuery(h->tune_ev.back()) == hipSuccess) {
+    if (hipEventQuery(T.ev.back().get()) == hipSuccess) {
         float t[3] = {0.f, 0.f, 0.f};
         bool ok = true;
         for (int w = 0; w < n_win && ok; w++)
             for (int k = 0; k < TUNE_WINDOW && ok; k++) {
                 float ms = 0.f;
                 const size_t p = (size_t)w * TUNE_WINDOW + k;
-                ok = hipEventElapsedTime(&ms, h->tune_ev[2 * p], h->tune_ev[2 * p + 1]) == hipSuccess;
+                ok = hipEventElapsedTime(&ms, T.ev[2 * p].get(), T.ev[2 * p + 1].get()) == hipSuccess;
                 t[w % 3] += ms;
             }
         int best = 0;
@@ -1149,10 +1162,10 @@ int tune_next(npp_handle h, int *pair) {
             const int alt = t[1] <= t[2] ? 1 : 2;
             if (t[alt] <= t[0] * margin) best = alt;
         }
-        h->variant = best; h->tuned = true; h->tune_since = 0;
+        T.variant = best; T.tuned = true; T.since = 0;
         return best;
     }
-    return h->variant;
+    return T.variant;
 }
 }  // namespace
 
@@ -1162,25 +1175,20 @@ int npp_set_obs_overlap_parts(npp_handle h, const int *cuts, int n_cuts) {
         if (cuts[i] <= (i ? cuts[i - 1] : 0) || cuts[i] >= 100)
             return fail(h, NPP_ERR_INVALID, "npp_set_obs_overlap_parts: cuts must be ascending percentages in (0, 100)");
     ON_DEVICE_JOINED(h);
-    if (n_cuts > 0 && !h->d_phase) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_phase, (size_t)h->n));
-        HIP_TRY(h, hipMemsetAsync(h->d_phase, 0, (size_t)h->n, h->stream));
-        for (auto &e : h->ov_ev) HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        // player_frame beside the rest.  Measured (doors, full Dict, two parts cut at 40 %): no side stream 471 us per step,
-        // global_view aside 485, player_frame aside 436, both 555 -- HIP feeds a process through four hardware queues, so more
-        // streams than that share queues and serialise again
-        h->side_mask = 2;
-        if (const char *ev = std::getenv("NPP_OBS_SIDE")) h->side_mask = (unsigned)std::atoi(ev) & 15u;
+    Overlap &ov = h->ov;
+    if (n_cuts > 0 && !ov.phase) {
+        HIP_TRY(h, ov.phase.alloc(h->n));
+        HIP_TRY(h, hipMemsetAsync(ov.phase.get(), 0, ov.phase.bytes(), h->stream));
+        for (Event &e : ov.ov_ev) HIP_TRY(h, e.create(hipEventDisableTiming));
     }
-    for (int q = 0; q < 4; q++)
-        if (!h->part_ev[q]) HIP_TRY(h, hipEventCreateWithFlags(&h->part_ev[q], hipEventDisableTiming));
-    for (int k = 0; k < 2; k++)
-        for (int q = 0; q < 2; q++)
-            if (!h->side_ev[k][q]) HIP_TRY(h, hipEventCreateWithFlags(&h->side_ev[k][q], hipEventDisableTiming));
-    if (n_cuts != h->n_cuts) h->owned_valid = false;
-    h->phase_dirty = true;
-    h->n_cuts = n_cuts;
-    for (int i = 0; i < n_cuts; i++) h->cut_pct[i] = cuts[i];
+    for (Event &e : ov.part_ev)
+        if (!e) HIP_TRY(h, e.create(hipEventDisableTiming));
+    for (Event &e : ov.side_ev)
+        if (!e) HIP_TRY(h, e.create(hipEventDisableTiming));
+    if (n_cuts != ov.n_cuts) ov.owned_valid = false;
+    ov.phase_dirty = true;
+    ov.n_cuts = n_cuts;
+    for (int i = 0; i < n_cuts; i++) ov.cut_pct[i] = cuts[i];
     if (n_cuts > 0)
         if (int rc = calibrate_streams(h, streams_needed(h))) return rc;
     return NPP_OK;
@@ -1199,15 +1207,16 @@ int npp_join(npp_handle h) {
 
 int npp_set_step_variant(npp_handle h, int variant) {
     if (!h || variant < -1 || variant > 2) return fail(h, NPP_ERR_INVALID, "npp_set_step_variant: variant must be -1 (autotune) or 0..2");
-    h->variant_pin = variant;
-    tune_reset(h);
+    h->tune.pin = variant;
+    h->tune.restart();
     return NPP_OK;
 }
 
 int npp_get_step_variant(npp_handle h, int *variant, int *tuned) {
     if (!h) return NPP_ERR_INVALID;
-    if (variant) *variant = (h->geo_g == 16 && !h->zoo_active) ? h->variant : 0;
-    if (tuned) *tuned = (h->tuned || h->variant_pin >= 0 || h->geo_g != 16 || h->zoo_active) ? 1 : 0;
+    const bool plain = h->plan.g == 16 && !h->plan.zoo_active;
+    if (variant) *variant = plain ? h->tune.variant : 0;
+    if (tuned) *tuned = (h->tune.tuned || h->tune.pin >= 0 || !plain) ? 1 : 0;
     return NPP_OK;
 }
 
@@ -1221,90 +1230,74 @@ int step_impl(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_
     a.n_ticks = frame_skip;
     a.mode = 0;
     fill_out(a, out);
+    Orders &o = h->ord;
     {   // heavy-first workgroup order: rebuilt from the per-block costs every 16th launch (and whenever the launch geometry changes)
-        const int epb = (64 / (h->geo_g > 0 ? h->geo_g : 1)) * (h->geo_wpb > 0 ? h->geo_wpb : 1);
+        const int epb = (64 / (h->plan.g > 0 ? h->plan.g : 1)) * (h->plan.wpb > 0 ? h->plan.wpb : 1);
         const int blocks = (h->n + epb - 1) / epb;
-        if (!h->d_wg_order) {
-            HIP_TRY(h, hipMalloc((void **)&h->d_wg_order, (size_t)h->n * sizeof(uint32_t)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_wg_cost, (size_t)h->n * sizeof(uint32_t)));
-            h->wg_blocks = 0;
+        if (!o.wg_order) {
+            HIP_TRY(h, o.wg_order.alloc(h->n));
+            HIP_TRY(h, o.wg_cost.alloc(h->n));
+            o.wg_blocks = 0;
         }
-        const bool fresh = blocks != h->wg_blocks;
-        if (fresh) tune_reset(h);
-        if (fresh || h->step_launches % 16 == 0) {
-            h->phase_dirty = true;   // (observation overlap) the parts are pieces of this order
-            if (fresh) HIP_TRY(h, hipMemsetAsync(h->d_wg_cost, 0, (size_t)h->n * sizeof(uint32_t), h->stream));
-            HIP_TRY(h, launch_cost_order(h->d_wg_cost, h->d_wg_order, blocks, NPP_STEP_FOLD, h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->d_wg_cost, 0, (size_t)blocks * sizeof(uint32_t), h->stream));   // costs are maxima over the next 16 launches
-            h->wg_blocks = blocks;
+        const bool fresh = blocks != o.wg_blocks;
+        if (fresh) h->tune.restart();
+        if (fresh || o.step_launches % 16 == 0) {
+            h->ov.phase_dirty = true;   // (observation overlap) the parts are pieces of this order
+            if (fresh) HIP_TRY(h, hipMemsetAsync(o.wg_cost.get(), 0, o.wg_cost.bytes(), h->stream));
+            HIP_TRY(h, launch_cost_order(o.wg_cost.get(), o.wg_order.get(), blocks, NPP_STEP_FOLD, h->stream));
+            HIP_TRY(h, hipMemsetAsync(o.wg_cost.get(), 0, (size_t)blocks * sizeof(uint32_t), h->stream));   // costs are maxima over the next 16 launches
+            o.wg_blocks = blocks;
         }
-        h->step_launches++;
-        a.wg_order = h->d_wg_order;
-        a.wg_cost = h->d_wg_cost;
-    }
-    {   // cost-split launch (VERDICT r2 #3b; off unless NPP_STEP_SPLIT is set -- measured, no gain: DESIGN.md 4.1)
-        static const char *sp = std::getenv("NPP_STEP_SPLIT");
-        int pct = 0, vh = 0, vl = 1;
-        if (sp && std::sscanf(sp, "%d:%d:%d", &pct, &vh, &vl) == 3 && pct > 0 && pct < 100 && h->geo_g == 16 && !h->zoo_active && a.wg_order) {
-            const int epb = (64 / h->geo_g) * h->geo_wpb, blocks = (h->n + epb - 1) / epb;
-            const int heavy = std::max(1, blocks * pct / 100);
-            if (!h->split_stream) {
-                HIP_TRY(h, hipStreamCreateWithFlags(&h->split_stream, hipStreamNonBlocking));
-                HIP_TRY(h, hipEventCreateWithFlags(&h->split_ev[0], hipEventDisableTiming));
-                HIP_TRY(h, hipEventCreateWithFlags(&h->split_ev[1], hipEventDisableTiming));
-            }
-            HIP_TRY(h, hipEventRecord(h->split_ev[0], h->stream));
-            HIP_TRY(h, hipStreamWaitEvent(h->split_stream, h->split_ev[0], 0));
-            KernelArgs ah = a, al = a;
-            ah.variant = vh; ah.wg_first = 0; ah.wg_count = heavy;
-            al.variant = vl; al.wg_first = heavy; al.wg_count = blocks - heavy;
-            HIP_TRY(h, launch_step(ah, h->split_stream));
-            HIP_TRY(h, launch_step(al, h->stream));
-            HIP_TRY(h, hipEventRecord(h->split_ev[1], h->split_stream));
-            HIP_TRY(h, hipStreamWaitEvent(h->stream, h->split_ev[1], 0));
-            return NPP_OK;
-        }
+        o.step_launches++;
+        a.wg_order = o.wg_order.get();
+        a.wg_cost = o.wg_cost.get();
     }
     int pair = -1;
     a.variant = tune_next(h, &pair);
-    if (h->n_cuts > 0 && h->d_phase && pair < 0 && (h->tuned || h->variant_pin >= 0 || h->geo_g != 16 || h->zoo_active)) {
+    Overlap &ov = h->ov;
+    if (ov.n_cuts > 0 && ov.phase && pair < 0 && (h->tune.tuned || h->tune.pin >= 0 || h->plan.g != 16 || h->plan.zoo_active)) {
         // observation overlap: the pieces of the heavy-first order as launches of their own, the most expensive first; the
         // observation entry points called next launch one kernel per part.  Only with workgroups of whole reachability groups (16
         // envs) and never on a launch the autotuner is timing.
-        const int epb = (64 / h->geo_g) * h->geo_wpb, blocks = (h->n + epb - 1) / epb;
+        const int epb = (64 / h->plan.g) * h->plan.wpb, blocks = (h->n + epb - 1) / epb;
         int edge[5] = {0, 0, 0, 0, 0};   // part q = n_cuts - i covers order entries [edge[i], edge[i + 1])
         bool ok = epb % 16 == 0;
-        for (int i = 0; i < h->n_cuts; i++) {
-            edge[i + 1] = (int)((long long)blocks * h->cut_pct[i] / 100);
+        for (int i = 0; i < ov.n_cuts; i++) {
+            edge[i + 1] = (int)((long long)blocks * ov.cut_pct[i] / 100);
             ok = ok && edge[i + 1] > edge[i];
         }
-        edge[h->n_cuts + 1] = blocks;
-        ok = ok && edge[h->n_cuts + 1] > edge[h->n_cuts];
+        edge[ov.n_cuts + 1] = blocks;
+        ok = ok && edge[ov.n_cuts + 1] > edge[ov.n_cuts];
         if (ok) {
             // the one-wavefront-per-SIMD build holds 310 registers: beside it neither another part nor an observation kernel finds
             // room on the SIMD, which is the point of the split (doors, full Dict: 502 us per step with it, 435-442 with build 0)
             if (a.variant == 2) a.variant = 0;
-            if (!h->owned_valid || h->owned_for != h->stream)   // (first split step after npp_set_stream: one-off, synchronises)
+            if (!ov.owned_valid || ov.owned_for != h->stream)   // (first split step after npp_set_stream: one-off, synchronises)
                 if (int rc = calibrate_streams(h, streams_needed(h))) return rc;
-            if (h->phase_dirty) {   // the env -> part map, on the caller's stream ahead of the fork
-                HIP_TRY(h, launch_phase_assign(h->d_wg_order, blocks, epb, h->n, edge, h->n_cuts + 1, h->d_phase, h->stream));
-                h->phase_dirty = false;
+            if (ov.phase_dirty) {   // the env -> part map, on the caller's stream ahead of the fork
+                HIP_TRY(h, launch_phase_assign(o.wg_order.get(), blocks, epb, h->n, edge, ov.n_cuts + 1, ov.phase.get(), h->stream));
+                ov.phase_dirty = false;
             }
-            HIP_TRY(h, hipEventRecord(h->ov_ev[0], h->stream));
-            h->live_parts = h->n_cuts + 1;
-            for (int i = 0; i <= h->n_cuts; i++) {
-                const int q = h->n_cuts - i;
+            HIP_TRY(h, hipEventRecord(ov.ov_ev[0].get(), h->stream));
+            hipError_t e = hipSuccess;
+            for (int i = 0; i <= ov.n_cuts && e == hipSuccess; i++) {
+                const int q = ov.n_cuts - i;
                 KernelArgs ap = a;
                 ap.wg_first = edge[i]; ap.wg_count = edge[i + 1] - edge[i];
-                if (h->part_stream[q] != h->stream) HIP_TRY(h, hipStreamWaitEvent(h->part_stream[q], h->ov_ev[0], 0));
-                HIP_TRY(h, launch_step(ap, h->part_stream[q]));
+                if (ov.part_stream[q] != h->stream) e = hipStreamWaitEvent(ov.part_stream[q], ov.ov_ev[0].get(), 0);
+                if (e == hipSuccess) e = launch_step(ap, ov.part_stream[q]);
+            }
+            ov.live_parts = ov.n_cuts + 1;   // (only now: a part that failed to launch leaves the others to be joined right here)
+            if (e != hipSuccess) {
+                (void)join_streams(h);
+                return fail(h, NPP_ERR_HIP, std::string("npp_step: part launch: ") + hipGetErrorString(e));
             }
             return NPP_OK;
         }
     }
-    if (pair >= 0) hipEventRecord(h->tune_ev[2 * (size_t)pair], h->stream);
+    if (pair >= 0) hipEventRecord(h->tune.ev[2 * (size_t)pair].get(), h->stream);
     const hipError_t le = launch_step(a, h->stream);
-    if (pair >= 0) hipEventRecord(h->tune_ev[2 * (size_t)pair + 1], h->stream);
+    if (pair >= 0) hipEventRecord(h->tune.ev[2 * (size_t)pair + 1].get(), h->stream);
     HIP_TRY(h, le);
     return NPP_OK;
 }
@@ -1314,13 +1307,13 @@ extern "C" {
 
 int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
-    if (!h->pool_on || !(h->flags & NPP_FLAG_AUTORESET)) return step_impl(h, d_actions, frame_skip, out);
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
+    if (!h->pool.on || !(h->flags & NPP_FLAG_AUTORESET)) return step_impl(h, d_actions, frame_skip, out);
     // level pool: the step as without it, then (joined) the draw for the envs whose episode ended -- read from the step's flags
     npp_step_out o;
     std::memset(&o, 0, sizeof(o));
     if (out) o = *out;
-    if (!o.d_flags) o.d_flags = h->d_pool_flags;
+    if (!o.d_flags) o.d_flags = h->pool.flags.get();
     if (int rc = step_impl(h, d_actions, frame_skip, &o)) return rc;
     ON_DEVICE_JOINED(h);
     return pool_redraw(h, o.d_flags, NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED, &o);
@@ -1328,7 +1321,7 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
 
 int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0 || n_steps <= 0) return fail(h, NPP_ERR_INVALID, "npp_step_many: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step_many: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step_many: no levels loaded");
     ON_DEVICE_JOINED(h);
     KernelArgs a = base_args(h);
     a.inputs = d_actions;
@@ -1343,7 +1336,7 @@ int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame
 
 int npp_tick(npp_handle h, const uint8_t *d_inputs, int n_ticks) {
     if (!h || !d_inputs || n_ticks <= 0) return fail(h, NPP_ERR_INVALID, "npp_tick: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_tick: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_tick: no levels loaded");
     ON_DEVICE_JOINED(h);
     KernelArgs a = base_args(h);
     a.inputs = d_inputs;
@@ -1356,7 +1349,7 @@ int npp_tick(npp_handle h, const uint8_t *d_inputs, int n_ticks) {
 
 int npp_observe(npp_handle h, const npp_step_out *out) {
     if (!h || !out) return fail(h, NPP_ERR_INVALID, "npp_observe: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_observe: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_observe: no levels loaded");
     ON_DEVICE_JOINED(h);
     KernelArgs a = base_args(h);
     a.n_ticks = 0;
@@ -1372,28 +1365,29 @@ int npp_observe(npp_handle h, const npp_step_out *out) {
 namespace {
 // player_frame of every env into d_out + env * stride (and, with mirror != 0, also mirror bytes further on)
 int render_player_frame(npp_handle h, uint8_t *d_out, uint32_t stride, uint32_t mirror) {
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_player_frame: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_player_frame: no levels loaded");
     ON_DEVICE(h);
-    bool tables = !h->d_canvas;   // (observation overlap) something the second stream has to wait for was put on the caller's stream
+    bool tables = !h->ls.canvas;   // (observation overlap) something the second stream has to wait for was put on the caller's stream
     if (int rc = ensure_canvas(h)) return rc;
     KernelArgs a = base_args(h);
     {   // heavy-first env order, rebuilt from the last launch's per-env clocks on every 8th launch
-        if (!h->d_pf_order) {
-            HIP_TRY(h, hipMalloc((void **)&h->d_pf_order, (size_t)h->n * sizeof(uint32_t)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_pf_cost, (size_t)h->n * sizeof(uint32_t)));
-            HIP_TRY(h, hipMemsetAsync(h->d_pf_cost, 0, (size_t)h->n * sizeof(uint32_t), h->stream));
-            h->pf_launches = 0;
+        Orders &o = h->ord;
+        if (!o.pf_order) {
+            HIP_TRY(h, o.pf_order.alloc(h->n));
+            HIP_TRY(h, o.pf_cost.alloc(h->n));
+            HIP_TRY(h, hipMemsetAsync(o.pf_cost.get(), 0, o.pf_cost.bytes(), h->stream));
+            o.pf_launches = 0;
         }
-        if (h->pf_launches % 8 < 2) {
-            HIP_TRY(h, launch_cost_order(h->d_pf_cost, h->d_pf_order, h->n, 0, h->stream));
+        if (o.pf_launches % 8 < 2) {
+            HIP_TRY(h, launch_cost_order(o.pf_cost.get(), o.pf_order.get(), h->n, 0, h->stream));
             tables = true;
         }
-        h->pf_launches++;
-        a.wg_order = h->d_pf_order;
-        a.wg_cost = h->d_pf_cost;
+        o.pf_launches++;
+        a.wg_order = o.pf_order.get();
+        a.wg_cost = o.pf_cost.get();
     }
     const int centered = (h->flags & NPP_FLAG_FRAME_CENTERED) ? 1 : 0;
-    return obs_launch(h, a, 1, tables,
+    return obs_launch(h, a, true, tables,
                       [&](const KernelArgs &ka, hipStream_t st) { return launch_render(ka, d_out, centered, st, stride, mirror); });
 }
 }  // namespace
@@ -1410,33 +1404,30 @@ int npp_set_frame_stack(npp_handle h, int visual_k, int state_k, int padding) {
         return fail(h, NPP_ERR_INVALID, "npp_set_frame_stack: stack sizes must be 0 (off) or 1..12 and padding 0 (zero) or 1 (repeat)");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the old rings may still be read by queued work
-    hipFree(h->d_fs_frames); hipFree(h->d_fs_state);
-    h->d_fs_frames = nullptr; h->d_fs_state = nullptr;
-    h->fs_vk = h->fs_sk = 0;
+    FrameStack &fs = h->fs;
+    fs = FrameStack();
     const size_t N = (size_t)h->n;
     if (visual_k) {
-        const size_t b = N * 2 * visual_k * 84 * 84;
-        HIP_TRY(h, hipMalloc((void **)&h->d_fs_frames, b));
-        HIP_TRY(h, hipMemsetAsync(h->d_fs_frames, 0, b, h->stream));
+        HIP_TRY(h, fs.frames.alloc(N * 2 * visual_k * 84 * 84));
+        HIP_TRY(h, hipMemsetAsync(fs.frames.get(), 0, fs.frames.bytes(), h->stream));
     }
     if (state_k) {
-        const size_t b = N * 2 * state_k * NPP_GAME_STATE_DIM * sizeof(float);
-        HIP_TRY(h, hipMalloc((void **)&h->d_fs_state, b));
-        HIP_TRY(h, hipMemsetAsync(h->d_fs_state, 0, b, h->stream));
+        HIP_TRY(h, fs.state.alloc(N * 2 * state_k * NPP_GAME_STATE_DIM));
+        HIP_TRY(h, hipMemsetAsync(fs.state.get(), 0, fs.state.bytes(), h->stream));
     }
-    h->fs_vk = visual_k; h->fs_sk = state_k; h->fs_repeat = padding;
-    h->fs_vhead = visual_k ? visual_k - 1 : 0;   // the first push completes position 0
-    h->fs_shead = state_k ? state_k - 1 : 0;
+    fs.vk = visual_k; fs.sk = state_k; fs.repeat = padding;
+    fs.vhead = visual_k ? visual_k - 1 : 0;   // the first push completes position 0
+    fs.shead = state_k ? state_k - 1 : 0;
     return NPP_OK;
 }
 
 int npp_frame_stack_render(npp_handle h) {
     if (!h) return NPP_ERR_INVALID;
-    if (!h->fs_vk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_render: visual stacking is off (npp_set_frame_stack)");
-    const int K = h->fs_vk, q = (h->fs_vhead + 1) % K;
+    if (!h->fs.vk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_render: visual stacking is off (npp_set_frame_stack)");
+    const int K = h->fs.vk, q = (h->fs.vhead + 1) % K;
     const uint32_t slot = 84 * 84, stride = (uint32_t)(2 * K) * slot;
     // position q lives in slots q and q + K; slot 0 is never inside a window, so position 0 is written once
-    uint8_t *dst = h->d_fs_frames + (size_t)(q ? q : K) * slot;
+    uint8_t *dst = h->fs.frames.get() + (size_t)(q ? q : K) * slot;
     return render_player_frame(h, dst, stride, q ? (uint32_t)K * slot : 0u);
 }
 
@@ -1444,23 +1435,23 @@ int npp_frame_stack_push(npp_handle h, const float *d_game_state, const float *d
                          int reset_bits, int reset_all, float *d_terminal_stack) {
     if (!h || !d_game_state || (!reset_all && reset_bits && !d_flags) || (d_terminal_stack && !d_terminal_state))
         return fail(h, NPP_ERR_INVALID, "npp_frame_stack_push: bad arguments");
-    if (!h->fs_vk && !h->fs_sk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_push: frame stacking is off (npp_set_frame_stack)");
-    if (d_terminal_stack && !h->fs_sk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_push: a terminal stack needs state stacking");
+    if (!h->fs.vk && !h->fs.sk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_push: frame stacking is off (npp_set_frame_stack)");
+    if (d_terminal_stack && !h->fs.sk) return fail(h, NPP_ERR_STATE, "npp_frame_stack_push: a terminal stack needs state stacking");
     ON_DEVICE_JOINED(h);
-    if (h->fs_vk) h->fs_vhead = (h->fs_vhead + 1) % h->fs_vk;
-    if (h->fs_sk) h->fs_shead = (h->fs_shead + 1) % h->fs_sk;
+    if (h->fs.vk) h->fs.vhead = (h->fs.vhead + 1) % h->fs.vk;
+    if (h->fs.sk) h->fs.shead = (h->fs.shead + 1) % h->fs.sk;
     StackArgs a;
     a.n = h->n;
-    a.visual_k = h->fs_vk; a.state_k = h->fs_sk;
-    a.vhead = h->fs_vhead; a.shead = h->fs_shead;
-    a.repeat = h->fs_repeat;
+    a.visual_k = h->fs.vk; a.state_k = h->fs.sk;
+    a.vhead = h->fs.vhead; a.shead = h->fs.shead;
+    a.repeat = h->fs.repeat;
     a.reset_bits = d_flags ? reset_bits : 0;
     a.reset_all = reset_all ? 1 : 0;
     a.flags = d_flags;
     a.game_state = d_game_state;
     a.terminal_state = d_terminal_state;
-    a.frames = h->d_fs_frames;
-    a.state = h->d_fs_state;
+    a.frames = h->fs.frames.get();
+    a.state = h->fs.state.get();
     a.terminal_stack = d_terminal_stack;
     HIP_TRY(h, launch_stack_push(a, h->stream));
     return NPP_OK;
@@ -1468,11 +1459,11 @@ int npp_frame_stack_push(npp_handle h, const float *d_game_state, const float *d
 
 int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, int64_t *batch_stride) {
     if (!h || (which != 0 && which != 1) || !base || !offset || !batch_stride) return fail(h, NPP_ERR_INVALID, "npp_frame_stack_view: bad arguments");
-    const int K = which == 0 ? h->fs_vk : h->fs_sk;
+    const int K = which == 0 ? h->fs.vk : h->fs.sk;
     if (!K) return fail(h, NPP_ERR_STATE, "npp_frame_stack_view: that stack is off (npp_set_frame_stack)");
     const int64_t E = which == 0 ? 84 * 84 : NPP_GAME_STATE_DIM;
-    const int head = which == 0 ? h->fs_vhead : h->fs_shead;
-    *base = which == 0 ? (void *)h->d_fs_frames : (void *)h->d_fs_state;
+    const int head = which == 0 ? h->fs.vhead : h->fs.shead;
+    *base = which == 0 ? (void *)h->fs.frames.get() : (void *)h->fs.state.get();
     *offset = (int64_t)(head + 1) * E;
     *batch_stride = (int64_t)2 * K * E;
     return NPP_OK;
@@ -1480,17 +1471,17 @@ int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, 
 
 int npp_set_entity_pos(npp_handle h, int env, int kind, double x, double y) {
     if (!h || env < 0 || env >= h->n || (kind != 0 && kind != 1)) return fail(h, NPP_ERR_INVALID, "npp_set_entity_pos: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: no levels loaded");
-    if (h->pool_on) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the level pool is on (npp_set_level_pool)");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: no levels loaded");
+    if (h->pool.on) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the level pool is on (npp_set_level_pool)");
     {
         ON_DEVICE_JOINED(h);
         if (int rc = pull_levels(h)) return rc;
     }
-    const CompiledLevel &L = h->levels[h->env_level[env]];
+    const CompiledLevel &L = h->ls.levels[h->env_level[env]];
     if (L.obs_switch < 0) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the env's level has no exit switch / door");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    double *blk = h->d_zoo + (size_t)env * h->zoo_words;
+    double *blk = h->ls.zoo.get() + (size_t)env * h->ls.zoo_words;
     uint64_t w3 = 0;
     HIP_TRY(h, hipMemcpy(&w3, blk + 3, 8, hipMemcpyDeviceToHost));
     const bool clear = !(x == x) || !(y == y);   // NaN clears the override
@@ -1512,10 +1503,10 @@ int npp_set_entity_pos(npp_handle h, int env, int kind, double x, double y) {
 
 int npp_switch_states(npp_handle h, float *d_out) {
     if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_switch_states: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_switch_states: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_switch_states: no levels loaded");
     ON_DEVICE(h);
     KernelArgs a = base_args(h);
-    return obs_launch(h, a, 3, false, [&](const KernelArgs &ka, hipStream_t st) { return launch_switch_states(ka, d_out, st); });
+    return obs_launch(h, a, false, false, [&](const KernelArgs &ka, hipStream_t st) { return launch_switch_states(ka, d_out, st); });
 }
 
 int npp_reachability(npp_handle h, float *d_features, float *d_mine_sdf, int32_t *d_status) {
@@ -1524,20 +1515,21 @@ int npp_reachability(npp_handle h, float *d_features, float *d_mine_sdf, int32_t
 
 int npp_reachability_ex(npp_handle h, float *d_features, float *d_mine_sdf, int32_t *d_status, float *d_switch_states) {
     if (!h || (!d_features && !d_mine_sdf)) return fail(h, NPP_ERR_INVALID, "npp_reachability: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_reachability: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_reachability: no levels loaded");
     if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_reachability: exit switch / door repositioned with npp_set_entity_pos");
     ON_DEVICE(h);
-    const bool tables = !h->d_rhdr;
+    const bool tables = !h->ls.reach.hdr;
     if (int rc = ensure_reach(h)) return rc;
     KernelArgs a = base_args(h);
-    return obs_launch(h, a, 2, tables, [&](const KernelArgs &ka, hipStream_t st) {   // (tables: ensure_reach has just built them)
-        return launch_reach(ka, h->d_rhdr, h->d_rblob, h->d_rkey, h->d_rcache, h->rmiss, d_features, d_mine_sdf, d_status, d_switch_states, st);
+    const Reach &r = h->ls.reach;
+    return obs_launch(h, a, false, tables, [&](const KernelArgs &ka, hipStream_t st) {   // (tables: ensure_reach has just built them)
+        return launch_reach(ka, r.hdr.get(), r.blob.get(), r.key.get(), r.cache.get(), r.miss(), d_features, d_mine_sdf, d_status, d_switch_states, st);
     });
 }
 
 int npp_render_frame(npp_handle h, int env0, int count, uint8_t *d_out) {
     if (!h || !d_out || env0 < 0 || count <= 0 || env0 + count > h->n) return fail(h, NPP_ERR_INVALID, "npp_render_frame: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_frame: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_frame: no levels loaded");
     ON_DEVICE_JOINED(h);
     if (int rc = ensure_canvas(h)) return rc;
     KernelArgs a = base_args(h);
@@ -1547,40 +1539,42 @@ int npp_render_frame(npp_handle h, int env0, int count, uint8_t *d_out) {
 
 int npp_render_global_view(npp_handle h, uint8_t *d_out) {
     if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_render_global_view: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_global_view: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_global_view: no levels loaded");
     ON_DEVICE(h);
-    const bool tables = !h->d_gv_h || !h->d_canvas;
+    const bool tables = !h->ls.gv.h || !h->ls.canvas;
     if (int rc = ensure_gv(h)) return rc;
     KernelArgs a = base_args(h);
     int max_records = 0;
-    for (const LevelHdr &lh : h->hdrs) max_records = std::max(max_records, (int)(lh.n_door + lh.n_ent + lh.n_mov));
-    const int reorder = (h->gv_launches++ % 4) < 2;   // the order is rebuilt on launches 0, 1, 4, 5, 8, ... (costs exist from launch 1 on)
-    if (h->live_parts > 1) {   // one kernel per part of a split step; the order table is rebuilt once, ahead of all of them
-        if (reorder) HIP_TRY(h, launch_cost_order(h->d_gv_cost, h->d_gv_order, h->n, 0, h->stream));
-        return obs_launch(h, a, 0, reorder || tables, [&](const KernelArgs &ka, hipStream_t st) {
-            return launch_global_view(ka, max_records, h->d_gv_p, h->d_gv_h, h->d_gv_v, d_out, h->d_gv_x, h->d_gv_order, h->d_gv_cost, 0, st);
+    for (const LevelHdr &lh : h->ls.hdrs) max_records = std::max(max_records, (int)(lh.n_door + lh.n_ent + lh.n_mov));
+    Orders &o = h->ord;
+    const GvTables &t = h->ls.gv;
+    const int reorder = (o.gv_launches++ % 4) < 2;   // the order is rebuilt on launches 0, 1, 4, 5, 8, ... (costs exist from launch 1 on)
+    if (h->ov.live_parts > 1) {   // one kernel per part of a split step; the order table is rebuilt once, ahead of all of them
+        if (reorder) HIP_TRY(h, launch_cost_order(o.gv_cost.get(), o.gv_order.get(), h->n, 0, h->stream));
+        return obs_launch(h, a, false, reorder || tables, [&](const KernelArgs &ka, hipStream_t st) {
+            return launch_global_view(ka, max_records, t.p.get(), t.h.get(), t.v.get(), d_out, o.gv_x.get(), o.gv_order.get(), o.gv_cost.get(), 0, st);
         });
     }
-    HIP_TRY(h, launch_global_view(a, max_records, h->d_gv_p, h->d_gv_h, h->d_gv_v, d_out, h->d_gv_x, h->d_gv_order, h->d_gv_cost, reorder, h->stream));
+    HIP_TRY(h, launch_global_view(a, max_records, t.p.get(), t.h.get(), t.v.get(), d_out, o.gv_x.get(), o.gv_order.get(), o.gv_cost.get(), reorder, h->stream));
     return NPP_OK;
 }
 
 int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *i32_out) {
     if (!h || env0 < 0 || count <= 0 || env0 + count > h->n) return fail(h, NPP_ERR_INVALID, "npp_dump_state: bad range");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_state: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_state: no levels loaded");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (int rc = pull_levels(h)) return rc;
     size_t N = (size_t)h->n;
     std::vector<double> f((size_t)NF64 * count);
     std::vector<uint32_t> u((size_t)NU32 * count);
-    std::vector<uint32_t> w((size_t)h->n_words_max * count);
+    std::vector<uint32_t> w((size_t)h->ls.n_words_max * count);
     for (int k = 0; k < NF64; k++)
-        HIP_TRY(h, hipMemcpy(f.data() + (size_t)k * count, h->d_f64 + k * N + env0, sizeof(double) * count, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(f.data() + (size_t)k * count, h->env.f64.get() + k * N + env0, sizeof(double) * count, hipMemcpyDeviceToHost));
     for (int k = 0; k < NU32; k++)
-        HIP_TRY(h, hipMemcpy(u.data() + (size_t)k * count, h->d_u32 + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
-    for (int k = 0; k < h->n_words_max; k++)
-        HIP_TRY(h, hipMemcpy(w.data() + (size_t)k * count, h->d_ent + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(u.data() + (size_t)k * count, h->env.u32.get() + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+    for (int k = 0; k < h->ls.n_words_max; k++)
+        HIP_TRY(h, hipMemcpy(w.data() + (size_t)k * count, h->ls.ent.get() + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) {
         auto F = [&](int k) { return f[(size_t)k * count + i]; };
         uint32_t A = u[(size_t)U_A * count + i], B = u[(size_t)U_B * count + i], C = u[(size_t)U_C * count + i],
@@ -1598,7 +1592,7 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
             int32_t *o = i32_out + (size_t)i * NPP_DUMP_I32;
             std::memset(o, 0, sizeof(int32_t) * NPP_DUMP_I32);
             int lvl = h->env_level[env0 + i];
-            const CompiledLevel &L = h->levels[lvl];
+            const CompiledLevel &L = h->ls.levels[lvl];
             int sw_active = 2;
             if (L.obs_switch >= 0) sw_active = (w[(size_t)(L.obs_switch >> 4) * count + i] >> ((L.obs_switch & 15) * 2)) & 3;
             o[0] = A & 15; o[1] = (A >> 4) & 1; o[2] = (A >> 6) & 1; o[3] = (A >> 7) & 3;
@@ -1616,14 +1610,14 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
 
 int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out) {
     if (!h || env < 0 || env >= h->n || !out || !n_out) return fail(h, NPP_ERR_INVALID, "npp_dump_entities: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_entities: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_entities: no levels loaded");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (int rc = pull_levels(h)) return rc;
-    const CompiledLevel &L = h->levels[h->env_level[env]];
-    std::vector<uint32_t> w(h->n_words_max);
-    for (int k = 0; k < h->n_words_max; k++)
-        HIP_TRY(h, hipMemcpy(&w[k], h->d_ent + (size_t)k * h->n + env, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const CompiledLevel &L = h->ls.levels[h->env_level[env]];
+    std::vector<uint32_t> w(h->ls.n_words_max);
+    for (int k = 0; k < h->ls.n_words_max; k++)
+        HIP_TRY(h, hipMemcpy(&w[k], h->ls.ent.get() + (size_t)k * h->n + env, sizeof(uint32_t), hipMemcpyDeviceToHost));
     int n = (int)L.ent_map_order.size();
     if (n > max) n = max;
     for (int i = 0; i < n; i++) {
@@ -1636,23 +1630,23 @@ int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out) 
 
 int npp_entity_checksum(npp_handle h, int env0, int count, double *out) {
     if (!h || env0 < 0 || count <= 0 || env0 + count > h->n || !out) return fail(h, NPP_ERR_INVALID, "npp_entity_checksum: bad arguments");
-    if (h->levels.empty()) return fail(h, NPP_ERR_STATE, "npp_entity_checksum: no levels loaded");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_entity_checksum: no levels loaded");
     ON_DEVICE_JOINED(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (int rc = pull_levels(h)) return rc;
     size_t N = (size_t)h->n;
-    std::vector<uint32_t> w((size_t)h->n_words_max * count);
-    for (int k = 0; k < h->n_words_max; k++)
-        HIP_TRY(h, hipMemcpy(w.data() + (size_t)k * count, h->d_ent + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> w((size_t)h->ls.n_words_max * count);
+    for (int k = 0; k < h->ls.n_words_max; k++)
+        HIP_TRY(h, hipMemcpy(w.data() + (size_t)k * count, h->ls.ent.get() + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
     std::vector<double> zb;
-    if (h->d_zoo) {
-        zb.resize((size_t)h->zoo_words * count);
-        HIP_TRY(h, hipMemcpy(zb.data(), h->d_zoo + (size_t)env0 * h->zoo_words, sizeof(double) * zb.size(), hipMemcpyDeviceToHost));
+    if (h->ls.zoo) {
+        zb.resize((size_t)h->ls.zoo_words * count);
+        HIP_TRY(h, hipMemcpy(zb.data(), h->ls.zoo.get() + (size_t)env0 * h->ls.zoo_words, sizeof(double) * zb.size(), hipMemcpyDeviceToHost));
     }
-    const int door_words = (h->zoo_doors + 1) / 2;
+    const int door_words = (h->ls.zoo_doors + 1) / 2;
     for (int i = 0; i < count; i++) {
-        const CompiledLevel &L = h->levels[h->env_level[env0 + i]];
-        const double *blk = h->d_zoo ? zb.data() + (size_t)i * h->zoo_words : nullptr;
+        const CompiledLevel &L = h->ls.levels[h->env_level[env0 + i]];
+        const double *blk = h->ls.zoo ? zb.data() + (size_t)i * h->ls.zoo_words : nullptr;
         uint64_t head3 = 0;
         if (blk) std::memcpy(&head3, blk + 3, 8);
         const uint32_t ovr = (uint32_t)head3;
@@ -1696,9 +1690,9 @@ int npp_entity_checksum(npp_handle h, int env0, int count, double *out) {
 }
 
 int npp_dump_level_segments(npp_handle h, int level, int16_t *out, int max_rows, int *n_out) {
-    if (!h || level < 0 || level >= (int)h->levels.size() || !out || !n_out)
+    if (!h || level < 0 || level >= (int)h->ls.levels.size() || !out || !n_out)
         return fail(h, NPP_ERR_INVALID, "npp_dump_level_segments: bad arguments");
-    int r = dump_segments(h->levels[level], out, max_rows);
+    int r = dump_segments(h->ls.levels[level], out, max_rows);
     if (r < 0) return fail(h, NPP_ERR_INVALID, "npp_dump_level_segments: buffer too small");
     *n_out = r;
     return NPP_OK;
