@@ -136,7 +136,6 @@ struct Orders {
     long pf_launches = 0;
     DevBuf<uint32_t> gv_order, gv_cost;   // global_view: env order and per-env costs
     long gv_launches = 0;
-    DevBuf<unsigned char> gv_x;           // (NPP_GV_SPLIT builds) global_view's per-env scratch of the split cell pass
 };
 
 // autotuner of the step-kernel build variant (npp_kernels.hip: VariantK): windows of TUNE_WINDOW launches per variant, timed
@@ -538,11 +537,6 @@ int ensure_gv(npp_handle h) {
         HIP_TRY(h, hipMemsetAsync(o.gv_cost.get(), 0, o.gv_cost.bytes(), h->stream));
         o.gv_launches = 0;   // the first launch builds an order (any permutation) from the zero costs
     }
-#ifdef NPP_GV_SPLIT
-    if (!o.gv_x) {   // (A/B builds of the split cell pass) sized by the number of envs, not by the level set: kept across npp_load_levels
-        HIP_TRY(h, o.gv_x.alloc((size_t)h->n * GV_XSTRIDE));
-    }
-#endif
     return NPP_OK;
 }
 
@@ -1099,10 +1093,6 @@ int npp_get_env_levels(npp_handle h, int32_t *host_out) {
     return NPP_OK;
 }
 
-
-#ifndef NPP_STEP_FOLD
-#define NPP_STEP_FOLD 0
-#endif
 namespace {
 // 256 launches of warm-up (episodes desynchronise: right after a reset every env sits at its spawn and the launches are dominated by
 // the levels with a crease under the spawn, which favours variant 2 -- a first cut that tuned on launches 48 .. 288 picked it for the
@@ -1244,7 +1234,7 @@ int step_impl(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_
         if (fresh || o.step_launches % 16 == 0) {
             h->ov.phase_dirty = true;   // (observation overlap) the parts are pieces of this order
             if (fresh) HIP_TRY(h, hipMemsetAsync(o.wg_cost.get(), 0, o.wg_cost.bytes(), h->stream));
-            HIP_TRY(h, launch_cost_order(o.wg_cost.get(), o.wg_order.get(), blocks, NPP_STEP_FOLD, h->stream));
+            HIP_TRY(h, launch_cost_order(o.wg_cost.get(), o.wg_order.get(), blocks, h->stream));
             HIP_TRY(h, hipMemsetAsync(o.wg_cost.get(), 0, (size_t)blocks * sizeof(uint32_t), h->stream));   // costs are maxima over the next 16 launches
             o.wg_blocks = blocks;
         }
@@ -1379,7 +1369,7 @@ int render_player_frame(npp_handle h, uint8_t *d_out, uint32_t stride, uint32_t 
             o.pf_launches = 0;
         }
         if (o.pf_launches % 8 < 2) {
-            HIP_TRY(h, launch_cost_order(o.pf_cost.get(), o.pf_order.get(), h->n, 0, h->stream));
+            HIP_TRY(h, launch_cost_order(o.pf_cost.get(), o.pf_order.get(), h->n, h->stream));
             tables = true;
         }
         o.pf_launches++;
@@ -1550,12 +1540,12 @@ int npp_render_global_view(npp_handle h, uint8_t *d_out) {
     const GvTables &t = h->ls.gv;
     const int reorder = (o.gv_launches++ % 4) < 2;   // the order is rebuilt on launches 0, 1, 4, 5, 8, ... (costs exist from launch 1 on)
     if (h->ov.live_parts > 1) {   // one kernel per part of a split step; the order table is rebuilt once, ahead of all of them
-        if (reorder) HIP_TRY(h, launch_cost_order(o.gv_cost.get(), o.gv_order.get(), h->n, 0, h->stream));
+        if (reorder) HIP_TRY(h, launch_cost_order(o.gv_cost.get(), o.gv_order.get(), h->n, h->stream));
         return obs_launch(h, a, false, reorder || tables, [&](const KernelArgs &ka, hipStream_t st) {
-            return launch_global_view(ka, max_records, t.p.get(), t.h.get(), t.v.get(), d_out, o.gv_x.get(), o.gv_order.get(), o.gv_cost.get(), 0, st);
+            return launch_global_view(ka, max_records, t.p.get(), t.h.get(), t.v.get(), d_out, o.gv_order.get(), o.gv_cost.get(), 0, st);
         });
     }
-    HIP_TRY(h, launch_global_view(a, max_records, t.p.get(), t.h.get(), t.v.get(), d_out, o.gv_x.get(), o.gv_order.get(), o.gv_cost.get(), reorder, h->stream));
+    HIP_TRY(h, launch_global_view(a, max_records, t.p.get(), t.h.get(), t.v.get(), d_out, o.gv_order.get(), o.gv_cost.get(), reorder, h->stream));
     return NPP_OK;
 }
 

@@ -196,12 +196,10 @@ hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s);
 hipError_t launch_pool_restore(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count, const int32_t *s_trunc,
                                int32_t *level, uint32_t *count, int32_t *trunc, hipStream_t s);
 // max_records: the largest number of draw records (closed-door strokes + entities + movers) of a loaded level; sizes the LDS
-// xscr: the per-env scratch of the split cell pass (GV_XSTRIDE bytes per env); null keeps the whole cell pass inside the first kernel
-constexpr size_t GV_XSTRIDE = 14336;
 // order / cost: u32[n] each -- the launch order of the envs (heaviest first) and the clocks every env's wavefront took; `reorder`
 // rebuilds the order from the costs before the launch (null order = env order)
 hipError_t launch_global_view(const KernelArgs &a, int max_records, const uint8_t *gv_p, const float *gv_h, const uint8_t *gv_v,
-                              uint8_t *d_out, unsigned char *xscr, uint32_t *order, uint32_t *cost, int reorder, hipStream_t s);
+                              uint8_t *d_out, uint32_t *order, uint32_t *cost, int reorder, hipStream_t s);
 // per-level static tables of global_view (the level right after a reset; needs the tile canvas): gv_p u8[n_levels][600][1056]
 // (+ 16 bytes) picture, gv_h f32[n_levels][600][100] horizontal sums, gv_v u8[n_levels][176][100] view
 hipError_t launch_gv_static(const KernelArgs &a, int n_levels, uint8_t *gv_p, float *gv_h, uint8_t *gv_v, hipStream_t s);
@@ -221,10 +219,10 @@ hipError_t launch_reach(const KernelArgs &a, const ReachHdr *rh, const unsigned 
 // envs selected by a.reset_mask (NULL = all): key / cache <- the snapshot's, or "no cached vector" when src_key == NULL
 hipError_t launch_reach_restore(const KernelArgs &a, const uint32_t *src_key, const float *src_cache, uint32_t *key, float *cache,
                                 const ReachMissDev &md, hipStream_t s);
-// order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)
 hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n, const int *edge, int parts, uint8_t *phase, hipStream_t s);
 hipError_t launch_spin(long long ticks, hipStream_t s);   // a bounded idle wavefront (stream calibration)
-hipError_t launch_cost_order(const uint32_t *cost, uint32_t *order, int n, int fold, hipStream_t s);
+// order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)
+hipError_t launch_cost_order(const uint32_t *cost, uint32_t *order, int n, hipStream_t s);
 hipError_t launch_tile_tables(hipStream_t s);   // per-device tile gray tables of the player_frame kernel
 hipError_t launch_tile_canvas(const LevelHdr *d_hdr, const unsigned char *d_blob, uint8_t *d_canvas, int n_levels, hipStream_t s);
 

@@ -1891,17 +1891,14 @@ DEV void run(const KernelArgs &a, unsigned char *smem) {
 //   (launch mean 120 -> 108 us, p50 111 -> 96: no second residency round any more; p95 221 -> 246: the slowest chain shares its SIMD for
 //   the first ~30 us) and the mine levels from 80.0 to 97.7 M (102 -> 84 us), and cost the door levels 5 % (241 -> 253 us: every launch
 //   there is one long chain).
-// So: G >= 16 (up to 16 384 envs) is built for 2 wavefronts per SIMD, G <= 8 and the zoo kernels keep the allocator's free hand
-// (1 wavefront per SIMD, AGPRs as spill space).  -DNPP_MIN_WAVES=1 rebuilds the uncapped G >= 16 kernels for A/B runs.
-#ifndef NPP_ZOO_WAVES   // the zoo kernels (21.8 k instructions, 389 registers): 1 = uncapped; -DNPP_ZOO_WAVES=2 is the A/B build
-#define NPP_ZOO_WAVES 1
-#endif
-#ifndef NPP_MIN_WAVES
-#define NPP_MIN_WAVES 2
-#endif
-
+// * round 3: the zoo kernels (21.8 k instructions, 389 registers) capped at 2 wavefronts per SIMD spill 181-189 VGPRs and take 428
+//   instead of 430 us per step: the SIMDs are issue-bound on them.
+// So: G >= 16 (up to 16 384 envs) is built for 2 wavefronts per SIMD, except variant 2, the uncapped build of rounds 1-2 that the
+// autotuner picks where it wins; G <= 8 and the zoo kernels keep the allocator's free hand (1 wavefront per SIMD,
+// AGPRs as spill space).  The build switches that uncapped every G >= 16 kernel or capped the zoo kernels were measured and
+// removed; 771647e is the last commit that builds them.
 template <int G, bool LDS_LEVEL, bool ZOO, bool MANY, int V>
-__global__ __launch_bounds__(256, (ZOO ? NPP_ZOO_WAVES : ((G < 16 || V == 2) ? 1 : NPP_MIN_WAVES))) void npp_step_kernel(KernelArgs a) {
+__global__ __launch_bounds__(256, (ZOO ? 1 : ((G < 16 || V == 2) ? 1 : 2))) void npp_step_kernel(KernelArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     run<G, LDS_LEVEL, ZOO, MANY, V>(a, smem);
 }

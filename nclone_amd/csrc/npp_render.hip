@@ -690,14 +690,10 @@ __device__ inline uint32_t pixel_full(const FrameLds &L, const Window &wd, const
     return (uint32_t)composite(eg, ea, (int)gray_cnt[g]);
 }
 
-#ifndef NPP_RENDER_OCC
-#define NPP_RENDER_OCC 5
-#endif
 // `stride`: bytes from one env's frame to the next (FW * FH for a plain [N, 84, 84] output; the frame-stack ring of
 // npp_stack.hip passes 2 K * FW * FH).  `mirror`: when non-zero, every dword is also written `mirror` bytes further on (the ring's
 // second copy of the slot); 0 for the plain output.
-__global__ __launch_bounds__(256, NPP_RENDER_OCC) void npp_render_kernel(KernelArgs a, uint8_t *out, int centered, uint32_t stride,
-                                                                        uint32_t mirror) {
+__global__ __launch_bounds__(256, 5) void npp_render_kernel(KernelArgs a, uint8_t *out, int centered, uint32_t stride, uint32_t mirror) {
     __shared__ FrameLds L;
     if ((int)blockIdx.x >= a.n) return;
     // heavy-first: the envs whose frame took longest last time (many drawables in the window) are dispatched first
@@ -899,35 +895,9 @@ __global__ __launch_bounds__(128) void npp_gv_static_v_kernel(const float *gv_h,
     gv_v[((size_t)lvl * GV_ROWS + r) * GV_COLS + col] = (uint8_t)fminf(fmaxf(rintf(acc), 0.f), 255.f);   // cvRound + saturate
 }
 
-#ifndef NPP_GV_Q   // (the three LDS budgets are build options for occupancy A/B runs; running out of any of them stays exact)
-#define NPP_GV_Q 512
-#endif
-#ifndef NPP_GV_PATCH
-#define NPP_GV_PATCH 3072
-#endif
-#ifndef NPP_GV_BOX_MAX
-#define NPP_GV_BOX_MAX 192
-#endif
-constexpr int GV_Q = NPP_GV_Q, GV_WORDS = (GV_CELLS + 31) / 32;
-constexpr int GV_PBOX = 32, GV_PATCH = NPP_GV_PATCH;   // dirty boxes whose pixels are composed up front into LDS patches, patch bytes
-// The cell pass as a kernel of its own (round 2): npp_global_view_kernel's launch lasted as long as its HEAVIEST env (cell pass: 36 k
-// clocks at the median, 250-380 k at the maximum), so an env with at most GV_XQ dirty cells now EXPORTS what the cell pass needs
-// (boxes, patch rectangles, patches, the cell queue; the draw list only if some row may have to compose in place) to a per-env
-// scratch block in HBM, and npp_gv_cells_kernel runs GV_XWAVES wavefronts per env, wavefront j taking the queue slices j, j + GV_XWAVES,
-// ... of GV_ITEM_CELLS cells: the cells of a heavy env are recomputed by several wavefronts at once and the wavefronts of light envs
-// retire after one header read.  (First cut: a global work list with one atomic per item -- 18 k same-address atomics took longer,
-// 280 us, than the cell pass they distributed.)  Same arithmetic, same order per cell.
-// MEASURED AND NOT SHIPPED (-DNPP_GV_SPLIT builds it): 8192 envs on the door levels, fused 223 us; split with one wavefront per env
-// 115 + 122 us, with four 115 + 196 us (32 768 workgroups: ~60 cycles of dispatch each per XCD).  Both halves stay bound by their
-// slowest wavefront -- list + patches up to 149 k clocks, cells up to 202 k (an env with 10 dirty boxes and 110 dirty cells on
-// `switch-simple`) -- and the heavy envs sit late in the grid, so two kernels pay two tails.
-#ifndef NPP_GV_XWAVES
-#define NPP_GV_XWAVES 4
-#endif
-constexpr int GV_XQ = 1024, GV_ITEM_CELLS = 32, GV_BOX_MAX = NPP_GV_BOX_MAX, GV_XWAVES = NPP_GV_XWAVES;
-constexpr int XS_HDR = 0, XS_BOX = 16, XS_PRECT = XS_BOX + GV_BOX_MAX * 8, XS_POFF = XS_PRECT + GV_PBOX * 8, XS_QUEUE = XS_POFF + GV_PBOX * 2,
-              XS_PATCH = XS_QUEUE + GV_XQ * 2, XS_DRAW = XS_PATCH + GV_PATCH, XS_CBOX = XS_DRAW + 224 * 28, XS_END = XS_CBOX + 224 * 4;
-static_assert(XS_DRAW % 16 == 0 && XS_PATCH % 4 == 0 && XS_END <= GV_XSTRIDE, "scratch block layout");
+// LDS budgets of one env (running out of any of them stays exact: queue rounds, cells composed in place, everything dirty)
+constexpr int GV_Q = 512, GV_WORDS = (GV_CELLS + 31) / 32, GV_BOX_MAX = 192;
+constexpr int GV_PBOX = 32, GV_PATCH = 3072;   // dirty boxes whose pixels are composed up front into LDS patches, patch bytes
 // LDS of one env (dynamic: the draw list and the box list are sized for the level SET -- the largest number of draw records of
 // a loaded level -- so that ordinary sets leave room for 12 wavefronts per CU instead of 8)
 struct GvLds {
@@ -1001,8 +971,7 @@ __device__ inline void wave_sync() {   // LDS traffic of one wavefront: order it
 }
 
 // One destination cell of the view, recomputed by the 8 lanes of a group (one source row per lane, then an ordered accumulation
-// through the group's lanes): shared by the in-place cell pass of npp_global_view_kernel and by npp_gv_cells_kernel.  Every lane of
-// the calling wavefront whose group has a cell calls it (the shuffles stay inside a group).
+// through the group's lanes).  Every lane of the calling wavefront whose group has a cell calls it (the shuffles stay inside a group).
 __device__ inline void gv_cell(const GvLds &L, int nd, int nb, const uint8_t *canvas, const uint8_t *pstat, const float *hrow,
                                uint8_t *out_env, int cell, int lane) {
     const int sub = lane & 7;
@@ -1106,7 +1075,6 @@ __device__ inline void gv_cell(const GvLds &L, int nd, int nb, const uint8_t *ca
             GV_ROW_RECT(0, rx0, rw0, ro0) GV_ROW_RECT(1, rx1, rw1, ro1) GV_ROW_RECT(2, rx2, rw2, ro2) GV_ROW_RECT(3, rx3, rw3, ro3)
 #undef GV_ROW_RECT
             if (!inline_compose) {
-#ifndef NPP_GV_NO_UNROLL_X
                 // a slice is 11 or 12 pixels: a fixed trip count lets the patch reads of all of them be in flight together (the sum
                 // stays in x order)
                 int pixv[12];
@@ -1115,7 +1083,7 @@ __device__ inline void gv_cell(const GvLds &L, int nd, int nb, const uint8_t *ca
                     const int x = tx.a + i;
                     const int o = x - xb0, sh = (o & 3) * 8;
                     int pix = (int)(((o < 4 ? pw.x : (o < 8 ? pw.y : (o < 12 ? pw.z : pw.w))) >> sh) & 0xffu);
-                    int pa = -1;
+                    int pa = -1;   // every patch holds the finished pixel, so whichever covers x will do
                     if (x >= rx0 && x < rx0 + rw0) pa = ro0 + x;
                     else if (x >= rx1 && x < rx1 + rw1) pa = ro1 + x;
                     else if (x >= rx2 && x < rx2 + rw2) pa = ro2 + x;
@@ -1128,18 +1096,6 @@ __device__ inline void gv_cell(const GvLds &L, int nd, int nb, const uint8_t *ca
                     const int x = tx.a + i;
                     if (x < tx.b) hs += tab_w3(x, tx_s1, tx_s2, tx_wh, tx_wm, tx_wt) * (float)pixv[i];
                 }
-#else
-                for (int x = tx.a; x < tx.b; x++) {
-                    const int o = x - xb0, sh = (o & 3) * 8;
-                    int pix = (int)(((o < 4 ? pw.x : (o < 8 ? pw.y : (o < 12 ? pw.z : pw.w))) >> sh) & 0xffu);
-                    // every patch holds the finished pixel, so whichever covers x will do
-                    if (x >= rx0 && x < rx0 + rw0) pix = L.patch[ro0 + x];
-                    else if (x >= rx1 && x < rx1 + rw1) pix = L.patch[ro1 + x];
-                    else if (x >= rx2 && x < rx2 + rw2) pix = L.patch[ro2 + x];
-                    else if (x >= rx3 && x < rx3 + rw3) pix = L.patch[ro3 + x];
-                    hs += tab_w3(x, tx_s1, tx_s2, tx_wh, tx_wm, tx_wt) * (float)pix;
-                }
-#endif
             } else {
                 const uint32_t *cp = reinterpret_cast<const uint32_t *>(canvas + (size_t)y * 1056 + xb0);
                 const uint4 cw = make_uint4(cp[0], cp[1], cp[2], cp[3]);
@@ -1180,29 +1136,19 @@ __device__ inline void gv_cell(const GvLds &L, int nd, int nb, const uint8_t *ca
     if (sub == 0) out_env[cell] = (uint8_t)fminf(fmaxf(rintf(acc), 0.f), 255.f);   // cvRound + saturate
 }
 
-// Occupancy (round 2): 3 wavefronts per SIMD (136 VGPRs, ~12 KB of LDS per env on the door levels).  Capping the registers at
-// 128 and trimming the LDS for 4 per SIMD was measured and dropped (246 -> 288 us inside the config-5 step): the launch lasts as
-// long as its heaviest env (cells phase p50 36 k clocks, max 250-380 k), not as long as the average one.
-#ifndef NPP_GV_WAVES
-#define NPP_GV_WAVES 3
-#endif
-// wavefronts (= envs) per workgroup: the wavefronts of a workgroup never synchronise with each other, a workgroup only bundles
-// them for the dispatcher
-#ifndef NPP_GV_WPB
-#define NPP_GV_WPB 1
-#endif
-constexpr int GV_WPB = NPP_GV_WPB;
-// One WAVEFRONT per env (the per-env work is small and serial phases dominate: no workgroup barriers, ~20 KB of LDS, many envs
-// in flight per CU).  Phases: copy the level's view; build the current draw list from the level's compact draw-order records
-// and collect the dirty boxes; mark + queue the dirty destination cells; recompute them, 8 lanes per cell (one source row per
-// lane, then an ordered accumulation through lane 0 of the group).
-__global__ __launch_bounds__(64 * GV_WPB, NPP_GV_WAVES) void npp_global_view_kernel(KernelArgs a, int draw_cap, const uint8_t *gv_p, const float *gv_h,
-                                                              const uint8_t *gv_v, uint8_t *out, unsigned char *xscr,
-                                                              const uint32_t *order, uint32_t *cost) {
+// Occupancy (round 2): 3 wavefronts per SIMD (136 VGPRs, ~12 KB of LDS per env on the door levels).  Measured and removed (771647e
+// is the last commit that builds them): 128 registers with the LDS trimmed for 4 per SIMD, 246 -> 288 us inside the config-5 step
+// (the launch lasts as long as its heaviest env: cells phase p50 36 k clocks, max 250-380 k); 2 or 4 envs per workgroup, no change.
+// One WAVEFRONT per env, one per workgroup (the per-env work is small and serial phases dominate: no workgroup barriers, ~20 KB of
+// LDS, many envs in flight per CU).  Phases: copy the level's view; build the current draw list from the level's compact draw-order
+// records and collect the dirty boxes; mark + queue the dirty destination cells; recompute them, 8 lanes per cell (one source row
+// per lane, then an ordered accumulation through lane 0 of the group).  The cell pass as a second kernel over per-env scratch blocks
+// was measured and removed too (two kernels pay two tails: 115 + 122 us against 223 us fused).
+__global__ __launch_bounds__(64, 3) void npp_global_view_kernel(KernelArgs a, int draw_cap, const uint8_t *gv_p, const float *gv_h,
+                                                                const uint8_t *gv_v, uint8_t *out, const uint32_t *order, uint32_t *cost) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gv_lds[];
-    const int wv = threadIdx.x >> 6;
-    const GvLds L = gv_lds_layout(gv_lds + (size_t)wv * gv_lds_bytes(draw_cap), draw_cap);
-    const int slot = blockIdx.x * GV_WPB + wv, lane = threadIdx.x & 63;
+    const GvLds L = gv_lds_layout(gv_lds, draw_cap);
+    const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot >= a.n) return;
     // heavy envs first: `order` lists the envs by the clocks their wavefront took in an earlier launch (npp_gv_order_kernel)
     const int env = order ? (int)order[slot] : slot;
@@ -1381,7 +1327,6 @@ __global__ __launch_bounds__(64 * GV_WPB, NPP_GV_WAVES) void npp_global_view_ker
                 L.poff[b] = 0;
             }
         }
-        L.ctr[3] = used;
     }
     wave_sync();
     // may a row slice have to compose pixels in place (a dirty box without a patch, or five boxes on one slice)?  Only then does the
@@ -1470,64 +1415,7 @@ __global__ __launch_bounds__(64 * GV_WPB, NPP_GV_WAVES) void npp_global_view_ker
 #ifdef NPP_GV_STATS
     const unsigned long long t3 = __builtin_amdgcn_s_memtime();
 #endif
-    {   // ---- few dirty cells (the usual case): hand the cell pass to npp_gv_cells_kernel
-        int tot = 0;
-        for (int w = lane; w < GV_WORDS; w += 64) tot += __popc(L.dirty[w]);
-#pragma unroll
-        for (int sft = 32; sft; sft >>= 1) tot += __shfl_xor(tot, sft, 64);
-        if (xscr != nullptr && tot <= GV_XQ) {
-            unsigned char *x = xscr + (size_t)env * GV_XSTRIDE;
-            unsigned short *xq = reinterpret_cast<unsigned short *>(x + XS_QUEUE);
-            for (int w = lane; w < GV_WORDS; w += 64) {
-                uint32_t m = L.dirty[w];
-                while (m) {
-                    const int bit = __builtin_ctz(m);
-                    m &= m - 1;
-                    xq[atomicAdd(&L.ctr[1], 1)] = (unsigned short)(w * 32 + bit);
-                }
-            }
-            const int used = L.ctr[3];
-            // may a row have to compose in place?  (a dirty box without a patch, or five boxes on one row slice)
-            const bool inl = may_inline;
-            if (lane == 0) *reinterpret_cast<int4 *>(x + XS_HDR) = make_int4(nd, nb, tot, used | (inl ? (int)0x80000000 : 0));
-            {
-                uint2 *xb = reinterpret_cast<uint2 *>(x + XS_BOX);
-                const uint2 *lb = reinterpret_cast<const uint2 *>(L.box);
-                for (int i = lane; i < nb; i += 64) xb[i] = lb[i];
-                uint2 *xr = reinterpret_cast<uint2 *>(x + XS_PRECT);
-                const uint2 *lr = reinterpret_cast<const uint2 *>(L.prect);
-                unsigned short *xo = reinterpret_cast<unsigned short *>(x + XS_POFF);
-                for (int i = lane; i < npb; i += 64) { xr[i] = lr[i]; xo[i] = L.poff[i]; }
-                uint32_t *xp = reinterpret_cast<uint32_t *>(x + XS_PATCH);
-                const uint32_t *lp = reinterpret_cast<const uint32_t *>(L.patch);
-                for (int i = lane; i < (used + 3) / 4; i += 64) xp[i] = lp[i];
-                if (inl) {
-                    uint32_t *xd = reinterpret_cast<uint32_t *>(x + XS_DRAW);
-                    const uint32_t *ld = reinterpret_cast<const uint32_t *>(L.draw);
-                    for (int i = lane; i < nd * 7; i += 64) xd[i] = ld[i];
-                    uint32_t *xc = reinterpret_cast<uint32_t *>(x + XS_CBOX);
-                    const uint32_t *lc = reinterpret_cast<const uint32_t *>(L.cbox);
-                    for (int i = lane; i < ((nd + 3) & ~3); i += 64) xc[i] = lc[i];
-                }
-            }
-#ifdef NPP_GV_STATS
-            wave_sync();
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane == 0) {   // diagnostic build only: the stamps of this kernel's phases over the view's first bytes (a cell of the
-                               // first row that npp_gv_cells_kernel recomputes overwrites one of them)
-                const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-                uint32_t *dbg = reinterpret_cast<uint32_t *>(out + (size_t)env * GV_CELLS);
-                dbg[0] = (uint32_t)(t1 - t0); dbg[1] = (uint32_t)(t2 - t1); dbg[2] = (uint32_t)(t3 - t2); dbg[3] = (uint32_t)(t4 - t3);
-                dbg[4] = (uint32_t)nd; dbg[5] = (uint32_t)nb; dbg[6] = (uint32_t)tot; dbg[7] = H.n_ent + H.n_mov;
-                dbg[8] = (uint32_t)(t1b - t1);
-                for (int k = 9; k < 14; k++) dbg[k] = 0u;
-            }
-#endif
-            return;
-        }
-        if (xscr != nullptr && lane == 0) *reinterpret_cast<int4 *>(xscr + (size_t)env * GV_XSTRIDE + XS_HDR) = make_int4(0, 0, 0, 0);   // nothing exported
-    }
-    // ---- many dirty cells (a crowd of movers, "everything dirty"): the cell pass runs in place
+    // ---- recompute the dirty cells in place
     // the dword copy of the view must have landed before single bytes of it are overwritten
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     for (;;) {
@@ -1564,7 +1452,6 @@ __global__ __launch_bounds__(64 * GV_WPB, NPP_GV_WAVES) void npp_global_view_ker
         dbg[0] = (uint32_t)(t1 - t0); dbg[1] = (uint32_t)(t2 - t1); dbg[2] = (uint32_t)(t3 - t2); dbg[3] = (uint32_t)(t4 - t3);
         dbg[4] = (uint32_t)nd; dbg[5] = (uint32_t)nb; dbg[6] = (uint32_t)stat_nq; dbg[7] = H.n_ent + H.n_mov;
         dbg[8] = (uint32_t)(t1b - t1);
-        for (int k = 9; k < 14; k++) dbg[k] = 0u;
     }
 #endif
     if (cost && lane == 0) cost[env] = (uint32_t)(__builtin_amdgcn_s_memtime() - cost_t0);
@@ -1581,7 +1468,7 @@ __device__ inline int gv_cost_bin(uint32_t c) {
     const int msb = 31 - __builtin_clz(c);                 // 4 .. 31
     return (msb - 4) * 4 + (int)((c >> (msb - 2)) & 3u) + 1;   // 1 .. 112
 }
-__global__ __launch_bounds__(1024) void npp_gv_order_kernel(const uint32_t *cost, uint32_t *order, int n, int fold) {
+__global__ __launch_bounds__(1024) void npp_gv_order_kernel(const uint32_t *cost, uint32_t *order, int n) {
     __shared__ int hist[128];
     __shared__ int base[128];
     if (threadIdx.x < 128) hist[threadIdx.x] = 0;
@@ -1593,88 +1480,10 @@ __global__ __launch_bounds__(1024) void npp_gv_order_kernel(const uint32_t *cost
         for (int b = 127; b >= 0; b--) { base[b] = acc; acc += hist[b]; }
     }
     __syncthreads();
-    // `fold` > 0 (npp_step, two workgroups per CU): positions fold .. 2 fold - 1 are filled backwards, so that if the dispatcher gives
-    // workgroup fold + k the second slot of workgroup k's CU the heaviest workgroups share their CU with the lightest ones
     for (int e = threadIdx.x; e < n; e += blockDim.x) {
-        int pos = atomicAdd(&base[gv_cost_bin(cost[e])], 1);
-        if (fold > 0 && pos >= fold && pos < 2 * fold) {
-            const int hi = (2 * fold < n ? 2 * fold : n) - 1;
-            pos = fold + (hi - pos);
-        }
+        const int pos = atomicAdd(&base[gv_cost_bin(cost[e])], 1);
         order[pos] = (uint32_t)e;
     }
-}
-
-// The cell pass of the envs that exported it: GV_XWAVES wavefronts per env; wavefront j stages the env's boxes / patches from its
-// scratch block once and runs the same per-cell code as the in-place pass on the queue slices j, j + GV_XWAVES, ...
-struct GvCellsLds {
-    Draw draw[224];
-    uchar4 cbox[224];
-    short4 box[GV_BOX_MAX];
-    short4 prect[GV_PBOX];
-    unsigned short poff[GV_PBOX];
-    unsigned short queue[GV_ITEM_CELLS];
-    __attribute__((aligned(4))) unsigned char patch[GV_PATCH];
-};
-__global__ __launch_bounds__(64 * GV_WPB, NPP_GV_WAVES) void npp_gv_cells_kernel(KernelArgs a, const uint8_t *gv_p, const float *gv_h,
-                                                                         const unsigned char *xscr, uint8_t *out) {
-    __shared__ __attribute__((aligned(16))) GvCellsLds SS[GV_WPB];
-    GvCellsLds &S = SS[threadIdx.x >> 6];
-    const int lane = threadIdx.x & 63, grp = lane >> 3;
-    const int gw = blockIdx.x * GV_WPB + (threadIdx.x >> 6);
-    const int env = gw / GV_XWAVES, j = gw - env * GV_XWAVES;
-    if (env >= a.n) return;
-#ifdef NPP_GV_STATS
-    const unsigned long long k2t0 = __builtin_amdgcn_s_memtime();
-#endif
-    const unsigned char *x = xscr + (size_t)env * GV_XSTRIDE;
-    const int4 hd = *reinterpret_cast<const int4 *>(x + XS_HDR);
-    const int nd = hd.x, nb = hd.y, nq = hd.z, used = hd.w & 0xffff;
-    if (j * GV_ITEM_CELLS >= nq) return;   // nothing for this wavefront (also: the env ran its cell pass in place, nq = 0)
-    const bool inl = hd.w < 0;
-    GvLds L;
-    L.draw = S.draw; L.cbox = S.cbox; L.box = S.box; L.prect = S.prect; L.poff = S.poff; L.queue = S.queue; L.patch = S.patch;
-    L.dirty = nullptr; L.ctr = nullptr; L.draw_cap = 224; L.box_cap = GV_BOX_MAX;
-    const int npb = nb < GV_PBOX ? nb : GV_PBOX;
-    {
-        const uint2 *xb = reinterpret_cast<const uint2 *>(x + XS_BOX);
-        uint2 *lb = reinterpret_cast<uint2 *>(S.box);
-        for (int i = lane; i < nb; i += 64) lb[i] = xb[i];
-        const uint2 *xr = reinterpret_cast<const uint2 *>(x + XS_PRECT);
-        uint2 *lr = reinterpret_cast<uint2 *>(S.prect);
-        const unsigned short *xo = reinterpret_cast<const unsigned short *>(x + XS_POFF);
-        for (int i = lane; i < npb; i += 64) { lr[i] = xr[i]; S.poff[i] = xo[i]; }
-        const uint32_t *xp = reinterpret_cast<const uint32_t *>(x + XS_PATCH);
-        uint32_t *lp = reinterpret_cast<uint32_t *>(S.patch);
-        for (int i = lane; i < (used + 3) / 4; i += 64) lp[i] = xp[i];
-        if (inl) {
-            const uint32_t *xd = reinterpret_cast<const uint32_t *>(x + XS_DRAW);
-            uint32_t *ld = reinterpret_cast<uint32_t *>(S.draw);
-            for (int i = lane; i < nd * 7; i += 64) ld[i] = xd[i];
-            const uint32_t *xc = reinterpret_cast<const uint32_t *>(x + XS_CBOX);
-            uint32_t *lc = reinterpret_cast<uint32_t *>(S.cbox);
-            for (int i = lane; i < ((nd + 3) & ~3); i += 64) lc[i] = xc[i];
-        }
-    }
-    const int lvl = __builtin_amdgcn_readfirstlane(a.env_level[env]);
-    const uint8_t *canvas = a.tile_canvas + (size_t)lvl * 600 * 1056;
-    const uint8_t *pstat = gv_p + (size_t)lvl * 600 * 1056;
-    const float *hrow = gv_h + (size_t)lvl * 600 * GV_COLS;
-    const unsigned short *xq = reinterpret_cast<const unsigned short *>(x + XS_QUEUE);
-    for (int q0 = j * GV_ITEM_CELLS; q0 < nq; q0 += GV_XWAVES * GV_ITEM_CELLS) {
-        const int ncell = nq - q0 < GV_ITEM_CELLS ? nq - q0 : GV_ITEM_CELLS;
-        wave_sync();   // the previous slice's cells are done with the queue
-        if (lane < ncell) S.queue[lane] = xq[q0 + lane];
-        wave_sync();
-        for (int qi = grp; qi < ncell; qi += 8) gv_cell(L, nd, nb, canvas, pstat, hrow, out + (size_t)env * GV_CELLS, S.queue[qi], lane);
-    }
-#ifdef NPP_GV_STATS
-    wave_sync();
-    if (lane == 0 && j == 0) {   // diagnostic build only: this wavefront's duration, dirty cells, in-place flag
-        uint32_t *dbg = reinterpret_cast<uint32_t *>(out + (size_t)env * GV_CELLS);
-        dbg[8] = (uint32_t)(__builtin_amdgcn_s_memtime() - k2t0); dbg[9] = (uint32_t)nq; dbg[10] = inl ? 1u : 0u; dbg[11] = (uint32_t)used;
-    }
-#endif
 }
 
 // The whole gray canvas of one env range (NPlayHeadless.render() in grayscale mode: nsim_renderer.py:71-134, array of shape
@@ -1738,17 +1547,11 @@ hipError_t launch_render(const KernelArgs &a, uint8_t *d_out, int centered, hipS
 }
 
 hipError_t launch_global_view(const KernelArgs &a, int max_records, const uint8_t *gv_p, const float *gv_h, const uint8_t *gv_v,
-                              uint8_t *d_out, unsigned char *xscr, uint32_t *order, uint32_t *cost, int reorder, hipStream_t s) {
+                              uint8_t *d_out, uint32_t *order, uint32_t *cost, int reorder, hipStream_t s) {
     int cap = max_records + 1;   // + the ninja
     cap = cap < 16 ? 16 : (cap > GV_DRAW ? GV_DRAW : cap);
-#ifndef NPP_GV_SPLIT
-    xscr = nullptr;   // shipped: the whole cell pass inside the first kernel (the split variant is an A/B build, see above)
-#endif
-    if (order && reorder) hipLaunchKernelGGL(npp_gv_order_kernel, dim3(1), dim3(1024), 0, s, cost, order, a.n, 0);
-    hipLaunchKernelGGL(npp_global_view_kernel, dim3((a.n + GV_WPB - 1) / GV_WPB), dim3(64 * GV_WPB), GV_WPB * gv_lds_bytes(cap), s, a, cap, gv_p, gv_h,
-                       gv_v, d_out, xscr, order, cost);
-    if (xscr)
-        hipLaunchKernelGGL(npp_gv_cells_kernel, dim3((a.n * GV_XWAVES + GV_WPB - 1) / GV_WPB), dim3(64 * GV_WPB), 0, s, a, gv_p, gv_h, xscr, d_out);
+    if (order && reorder) hipLaunchKernelGGL(npp_gv_order_kernel, dim3(1), dim3(1024), 0, s, cost, order, a.n);
+    hipLaunchKernelGGL(npp_global_view_kernel, dim3(a.n), dim3(64), gv_lds_bytes(cap), s, a, cap, gv_p, gv_h, gv_v, d_out, order, cost);
     return hipGetLastError();
 }
 
@@ -1784,8 +1587,8 @@ hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n
     return hipGetLastError();
 }
 
-hipError_t launch_cost_order(const uint32_t *cost, uint32_t *order, int n, int fold, hipStream_t s) {
-    hipLaunchKernelGGL(npp_gv_order_kernel, dim3(1), dim3(1024), 0, s, cost, order, n, fold);
+hipError_t launch_cost_order(const uint32_t *cost, uint32_t *order, int n, hipStream_t s) {
+    hipLaunchKernelGGL(npp_gv_order_kernel, dim3(1), dim3(1024), 0, s, cost, order, n);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // Workgroup dispatch microbenchmark: N workgroups that each spin for a fixed number of shader clocks; how long does the launch take for
-// different workgroup sizes / LDS sizes?  (Why do 2048 single-wavefront workgroups of ~17 us each take 100 us in npp_gv_cells_kernel?)
+// different workgroup sizes / LDS sizes?  (Why did 2048 single-wavefront workgroups of ~17 us each take 100 us in the split global_view cell pass, DESIGN.md 4.8?)
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench/dispatch.hip -o build_ab/dispatch && build_ab/dispatch
 #include <hip/hip_runtime.h>
 #include <cstdio>
