@@ -374,6 +374,27 @@ int npp_env_level_view(npp_handle h, const int32_t **d_levels);
 int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed, const int32_t *envs, const uint32_t *counts, int count,
                              int32_t *out);
 
+/* Graph observations for the GCN encoder: graph_node_feats, graph_edge_index, graph_node_mask, graph_edge_mask of the reference's
+ * training Dict (OBSERVATION_SPACE_README.md; gym_environment/npp_environment.py:245-271).  The reference builds the graph at every
+ * reset from the freshly loaded level (mixins/graph_mixin.py:96-109, 340-376) and keeps it for the episode, so it is a constant per
+ * level: the masked, flood-filled `adjacency` of GraphBuilder.build_graph (the one npp_reachability restates) converted by
+ * create_graph_data (graph/edge_building.py:124-272) with the node features of graph/feature_builder.py:67-197, entities in their
+ * spawn state.  Nodes: the endpoints of edges in (x, y) order, at most 2500 (one node at (0, 0) when there is no edge); edges in the
+ * adjacency's dict order, those touching a truncated node skipped, at most 20000.  Unlike npp_reachability, levels with several exits
+ * are served.
+ * npp_graph_observation: rows of env e -- d_node_feats f32[N][2500][6], d_edge_index u16[N][2][20000], d_node_mask u8[N][2500],
+ *   d_edge_mask u8[N][20000], zero padded -- hold the graph of the level env e plays.  The handle keeps, per env, the level its rows
+ *   hold (-1 = none) and rewrites, whole, only the rows of envs whose current level (npp_env_level_view) differs; a call on an
+ *   unchanged batch is one small launch.  A call with another buffer set than the last, or with flags bit 0, rewrites every row.
+ *   npp_load_levels forgets what the rows hold.  d_node_feats, d_edge_index and d_edge_mask must be 16-byte aligned.  Joins an
+ *   observation overlap first (the result does not depend on it).  NPP_ERR_UNSUPPORTED while an entity is repositioned with
+ *   npp_set_entity_pos (the reference rebuilds from the moved positions; not restated).  The per-level tables are built at the first
+ *   call (host work, about 140 KB of HBM per level at most).
+ * npp_graph_compile (host-only, no GPU, no handle): one level's rows -- feats f32[2500][6], edge_index u16[2][20000], zero padded --
+ *   and counts i32[2] = (num_nodes, num_edges); any output may be NULL. */
+int npp_graph_observation(npp_handle h, float *d_node_feats, uint16_t *d_edge_index, uint8_t *d_node_mask, uint8_t *d_edge_mask, int flags);
+int npp_graph_compile(const double *map, int64_t n, float *feats, uint16_t *edge_index, int32_t *counts);
+
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);
 

@@ -32,6 +32,7 @@ EXPORTS = [
     "npp_set_obs_overlap", "npp_set_obs_overlap_parts", "npp_join",
     "npp_set_frame_stack", "npp_frame_stack_render", "npp_frame_stack_push", "npp_frame_stack_view",
     "npp_set_level_pool", "npp_draw_levels", "npp_get_env_levels", "npp_env_level_view", "npp_level_pool_draw_host",
+    "npp_graph_observation", "npp_graph_compile",
 ]
 
 
@@ -129,6 +130,8 @@ def lib():
     L.npp_draw_levels.argtypes = [H, C.POINTER(C.c_uint8)]
     L.npp_get_env_levels.argtypes = [H, C.POINTER(C.c_int32)]
     L.npp_env_level_view.argtypes = [H, C.POINTER(C.c_void_p)]
+    L.npp_graph_observation.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.npp_graph_compile.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.npp_level_pool_draw_host.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int,
                                            C.POINTER(C.c_int32)]
     L.npp_num_envs.argtypes = [H]

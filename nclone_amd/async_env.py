@@ -81,7 +81,8 @@ class NppAsyncVecEnvironment:
     step_wait_partial(k)           just sub-batch k: rows [k * n/S, (k + 1) * n/S) -- lets a learner overlap
     step_async_partial(k, actions) re-enqueue just sub-batch k
 
-    No frame stacking here (NppVecEnvironment has it): observations are single entries.
+    No frame stacking here (NppVecEnvironment has it): observations are single entries.  No graph observations either
+    (NppVecEnvironment(enable_graph_observations=True) has them).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",

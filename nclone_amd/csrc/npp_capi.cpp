@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/npp_amd.h"
+#include "npp_graph.hpp"
 #include "npp_host.hpp"
 #include "npp_internal.hpp"
 #include "npp_level.hpp"
@@ -92,6 +93,14 @@ struct Reach {
     ReachMissDev miss() const { return {stamp.get(), raw.get(), epoch.get(), last_episode.get()}; }
 };
 
+// graph observations (npp_graph_observation): per-level tables + what the caller's rows hold
+struct GraphObs {
+    DevBuf<GraphHdr> hdr;
+    DevBuf<unsigned char> blob;
+    DevBuf<int32_t> row_level;   // [n] the level env e's rows hold, -1 = none
+    const void *rows[4] = {nullptr, nullptr, nullptr, nullptr};   // the buffer set row_level describes
+};
+
 // The loaded level set and everything derived from it: replaced whole by npp_load_levels
 struct LevelSet {
     std::vector<CompiledLevel> levels;
@@ -107,6 +116,7 @@ struct LevelSet {
     DevBuf<uint8_t> canvas;       // tile-layer coverage canvas of every level (render paths)
     GvTables gv;
     Reach reach;
+    GraphObs graph;
     std::vector<int32_t> level_trunc;   // [n_levels] dynamic truncation limit (empty = not computed)
     DevBuf<int32_t> d_level_trunc;      // the same on the device (level pool + dynamic truncation)
     DevBuf<double> pool_cdf;            // [n_levels] (level pool)
@@ -576,6 +586,28 @@ int ensure_reach(npp_handle h) {
     HIP_TRY(h, r.hdr.alloc(nl));
     HIP_TRY(h, hipMemcpy(r.hdr.get(), hdrs.data(), r.hdr.bytes(), hipMemcpyHostToDevice));
     h->ls.reach = std::move(r);
+    return NPP_OK;
+}
+
+// The graph observation tables (npp_graph.cpp) likewise, at the first npp_graph_observation: at most ~140 KB of HBM per level
+int ensure_graph(npp_handle h) {
+    if (h->ls.graph.hdr) return NPP_OK;
+    const size_t nl = h->ls.levels.size();
+    std::vector<GraphHdr> hdrs(nl);
+    std::vector<unsigned char> blob;
+    for (size_t i = 0; i < nl; i++) {
+        GraphBuilt G;
+        build_graph_obs(h->ls.levels[i], G);
+        pack_graph_obs(G, hdrs[i], blob);
+    }
+    GraphObs g;   // complete or not at all
+    HIP_TRY(h, g.blob.alloc(blob.size()));
+    HIP_TRY(h, hipMemcpy(g.blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, g.row_level.alloc((size_t)h->n));
+    HIP_TRY(h, hipMemset(g.row_level.get(), 0xff, g.row_level.bytes()));
+    HIP_TRY(h, g.hdr.alloc(nl));
+    HIP_TRY(h, hipMemcpy(g.hdr.get(), hdrs.data(), g.hdr.bytes(), hipMemcpyHostToDevice));
+    h->ls.graph = std::move(g);
     return NPP_OK;
 }
 
@@ -1515,6 +1547,34 @@ int npp_reachability_ex(npp_handle h, float *d_features, float *d_mine_sdf, int3
     return obs_launch(h, a, false, tables, [&](const KernelArgs &ka, hipStream_t st) {   // (tables: ensure_reach has just built them)
         return launch_reach(ka, r.hdr.get(), r.blob.get(), r.key.get(), r.cache.get(), r.miss(), d_features, d_mine_sdf, d_status, d_switch_states, st);
     });
+}
+
+int npp_graph_observation(npp_handle h, float *d_node_feats, uint16_t *d_edge_index, uint8_t *d_node_mask, uint8_t *d_edge_mask, int flags) {
+    if (!h || !d_node_feats || !d_edge_index || !d_node_mask || !d_edge_mask || (flags & ~1))
+        return fail(h, NPP_ERR_INVALID, "npp_graph_observation: bad arguments");
+    if (((uintptr_t)d_node_feats | (uintptr_t)d_edge_index | (uintptr_t)d_edge_mask) & 15)
+        return fail(h, NPP_ERR_INVALID, "npp_graph_observation: node features, edge index and edge mask must be 16-byte aligned");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_graph_observation: no levels loaded");
+    if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_graph_observation: an entity is repositioned with npp_set_entity_pos");
+    ON_DEVICE_JOINED(h);
+    if (int rc = ensure_graph(h)) return rc;
+    GraphObs &g = h->ls.graph;
+    const void *rows[4] = {d_node_feats, d_edge_index, d_node_mask, d_edge_mask};
+    GraphArgs a;
+    a.n = h->n;
+    a.n_levels = (int)h->ls.levels.size();
+    a.all = (flags & 1) || !std::equal(rows, rows + 4, g.rows);
+    a.env_level = h->env.level.get();
+    a.row_level = g.row_level.get();
+    a.hdr = g.hdr.get();
+    a.blob = g.blob.get();
+    a.feats = d_node_feats;
+    a.edges = d_edge_index;
+    a.node_mask = d_node_mask;
+    a.edge_mask = d_edge_mask;
+    HIP_TRY(h, launch_graph_rows(a, h->stream));
+    std::copy(rows, rows + 4, g.rows);
+    return NPP_OK;
 }
 
 int npp_render_frame(npp_handle h, int env0, int count, uint8_t *d_out) {

@@ -195,6 +195,21 @@ hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s);
 // envs selected by mask (null = all): level, draw count and truncation limit <- the snapshot's
 hipError_t launch_pool_restore(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count, const int32_t *s_trunc,
                                int32_t *level, uint32_t *count, int32_t *trunc, hipStream_t s);
+// npp_graph.hip: graph observation rows (see npp_graph_observation in include/npp_amd.h; tables: npp_graph.hpp)
+struct GraphHdr;
+struct GraphArgs {
+    int n, n_levels;
+    int all;                      // 1: rewrite every row
+    const int32_t *env_level;     // [n] the level env e plays
+    int32_t *row_level;           // [n] the level env e's rows hold, -1 = none; set to env_level[e] once they are written
+    const GraphHdr *hdr;          // [n_levels]
+    const unsigned char *blob;
+    float *feats;                 // [n][2500][6]     (16-byte aligned)
+    uint16_t *edges;              // [n][2][20000]    (16-byte aligned)
+    uint8_t *node_mask;           // [n][2500]
+    uint8_t *edge_mask;           // [n][20000]       (16-byte aligned)
+};
+hipError_t launch_graph_rows(const GraphArgs &a, hipStream_t s);
 // max_records: the largest number of draw records (closed-door strokes + entities + movers) of a loaded level; sizes the LDS
 // order / cost: u32[n] each -- the launch order of the envs (heaviest first) and the clocks every env's wavefront took; `reorder`
 // rebuilds the order from the costs before the launch (null order = env order)

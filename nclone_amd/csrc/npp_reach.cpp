@@ -439,6 +439,69 @@ int goal_node_for_start(const std::vector<int> &order, int qx, int qy, int entit
 
 }  // namespace
 
+// the final `adjacency` of GraphBuilder.build_graph (graph_builder.py:735-866): base graph, physics cache, toggle-mine mask, flood
+// fill from the spawn.  Shared by the reachability tables and the graph observation (npp_graph.cpp); nothing in it depends on the
+// exits, so it serves levels build_reach refuses.
+void build_adjacency(const CompiledLevel &L, ReachAdjacency &A) {
+    std::vector<int> mines1, mines21;
+    for (size_t k = 0; k < L.ent_map_order.size(); k++) {
+        const int s = L.ent_map_order[k];
+        if ((L.ent_meta[s] & 15u) == EK_MINE) (((L.ent_meta[s] >> 24) & 63u) == 1 ? mines1 : mines21).push_back(s);
+    }
+    Graph base;
+    build_base(L, base);
+    build_physics(base, A.phys);
+    A.base_in = base.in; A.base_adj = base.adj;
+    Graph masked = base;
+    {
+        std::vector<uint8_t> blocked(RNODES, 0);
+        auto block = [&](const std::vector<int> &ms) {
+            for (int s : ms) {
+                const int mx = (int)L.ent_x[s] - 24, my = (int)L.ent_y[s] - 24;   // _get_entity_pixel_position: int() then the offset
+                for (int id = 0; id < RNODES; id++) {
+                    if (!base.in[id]) continue;
+                    const long ex = reach_node_x(id) - mx, ey = reach_node_y(id) - my;
+                    if ((double)(ex * ex + ey * ey) < 14.0 * 14.0) blocked[id] = 1;   // NINJA_RADIUS + RADII[0]
+                }
+            }
+        };
+        block(mines1);
+        block(mines21);
+        A.blocked = blocked;
+        for (int id = 0; id < RNODES; id++) {
+            if (!masked.in[id]) continue;
+            if (blocked[id]) { masked.in[id] = 0; masked.adj[id] = 0; continue; }
+            const int i = id / RH, j = id % RH;
+            uint8_t m = masked.adj[id];
+            for (int d = 0; d < 8; d++)
+                if ((m >> d) & 1u) {
+                    const int nb = nid(i + DX[d], j + DY[d]);
+                    if (blocked[nb]) m &= (uint8_t)~(1u << d);
+                }
+            masked.adj[id] = m;
+        }
+    }
+    Graph fin = masked;
+    {
+        std::vector<uint8_t> reach;
+        // graph_builder.py:844-866: physics_cache is None there, grounding comes from base_adjacency -- the same bits
+        int cnt = flood_fill(masked, A.phys, L.spawn_x, L.spawn_y, reach);
+        if (cnt == 0) {   // "Using ALL adjacency nodes as fallback"
+            for (int id = 0; id < RNODES; id++) reach[id] = masked.in[id];
+        }
+        for (int id = 0; id < RNODES; id++) {
+            if (!fin.in[id]) continue;
+            if (!reach[id]) { fin.in[id] = 0; fin.adj[id] = 0; continue; }
+            const int i = id / RH, j = id % RH;
+            uint8_t m = fin.adj[id];
+            for (int d = 0; d < 8; d++)
+                if (((m >> d) & 1u) && !reach[nid(i + DX[d], j + DY[d])]) m &= (uint8_t)~(1u << d);
+            fin.adj[id] = m;
+        }
+    }
+    A.in = fin.in; A.adj = fin.adj;
+}
+
 bool build_reach(const double *map, int64_t n, ReachBuilt &R, std::string &err) {
     CompiledLevel L;
     if (!compile_level(map, n, L, err)) return false;
@@ -478,58 +541,9 @@ void build_reach(const CompiledLevel &L, ReachBuilt &R) {
     for (int s : mines21) R.mine_mask[s >> 4] |= 1u << ((s & 15) * 2);
     if (R.mine_mask.empty()) R.mine_mask.push_back(0u);
     // ---- base graph, physics, entity mask, flood fill from the spawn
-    Graph base;
-    build_base(L, base);
-    build_physics(base, R.phys);
-    R.base_in = base.in; R.base_adj = base.adj;
-    Graph masked = base;
-    {
-        std::vector<uint8_t> blocked(RNODES, 0);
-        auto block = [&](const std::vector<int> &ms) {
-            for (int s : ms) {
-                const int mx = (int)L.ent_x[s] - 24, my = (int)L.ent_y[s] - 24;   // _get_entity_pixel_position: int() then the offset
-                for (int id = 0; id < RNODES; id++) {
-                    if (!base.in[id]) continue;
-                    const long ex = reach_node_x(id) - mx, ey = reach_node_y(id) - my;
-                    if ((double)(ex * ex + ey * ey) < 14.0 * 14.0) blocked[id] = 1;   // NINJA_RADIUS + RADII[0]
-                }
-            }
-        };
-        block(mines1);
-        block(mines21);
-        R.blocked = blocked;
-        for (int id = 0; id < RNODES; id++) {
-            if (!masked.in[id]) continue;
-            if (blocked[id]) { masked.in[id] = 0; masked.adj[id] = 0; continue; }
-            const int i = id / RH, j = id % RH;
-            uint8_t m = masked.adj[id];
-            for (int d = 0; d < 8; d++)
-                if ((m >> d) & 1u) {
-                    const int nb = nid(i + DX[d], j + DY[d]);
-                    if (blocked[nb]) m &= (uint8_t)~(1u << d);
-                }
-            masked.adj[id] = m;
-        }
-    }
-    Graph fin = masked;
-    {
-        std::vector<uint8_t> reach;
-        // graph_builder.py:844-866: physics_cache is None there, grounding comes from base_adjacency -- the same bits
-        int cnt = flood_fill(masked, R.phys, L.spawn_x, L.spawn_y, reach);
-        if (cnt == 0) {   // "Using ALL adjacency nodes as fallback"
-            for (int id = 0; id < RNODES; id++) reach[id] = masked.in[id];
-        }
-        for (int id = 0; id < RNODES; id++) {
-            if (!fin.in[id]) continue;
-            if (!reach[id]) { fin.in[id] = 0; fin.adj[id] = 0; continue; }
-            const int i = id / RH, j = id % RH;
-            uint8_t m = fin.adj[id];
-            for (int d = 0; d < 8; d++)
-                if (((m >> d) & 1u) && !reach[nid(i + DX[d], j + DY[d])]) m &= (uint8_t)~(1u << d);
-            fin.adj[id] = m;
-        }
-    }
-    R.in = fin.in; R.adj = fin.adj;
+    build_adjacency(L, R);
+    Graph fin;
+    fin.in = R.in; fin.adj = R.adj;
     int n_adj = 0;
     for (int id = 0; id < RNODES; id++) n_adj += fin.in[id];
     H.n_adj = (uint32_t)n_adj;

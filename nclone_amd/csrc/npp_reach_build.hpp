@@ -9,12 +9,16 @@
 
 namespace npp {
 
-struct ReachBuilt {
-    ReachHdr hdr;
+// the graph stages of GraphBuilder.build_graph, per node id of the RW x RH lattice
+struct ReachAdjacency {
     std::vector<uint8_t> base_in, base_adj;   // base graph (tiles only): node present, edge bits N E S W NE SE SW NW
     std::vector<uint8_t> phys;                // bit 0 grounded, bit 1 walled (on the base graph)
     std::vector<uint8_t> blocked;             // nodes within 14 px of a toggle mine
     std::vector<uint8_t> in, adj;             // final adjacency (mask + flood fill from the spawn)
+};
+
+struct ReachBuilt : ReachAdjacency {
+    ReachHdr hdr;
     std::vector<double> dist[2];              // [RNODES] per goal
     std::vector<int16_t> hop[2];              // [RNODES]
     std::vector<double> mh[2];                // [RNODES][2]
@@ -30,6 +34,7 @@ struct ReachBuilt {
 };
 
 struct CompiledLevel;
+void build_adjacency(const CompiledLevel &level, ReachAdjacency &out);
 bool build_reach(const double *map, int64_t n, ReachBuilt &out, std::string &err);
 void build_reach(const CompiledLevel &level, ReachBuilt &out);
 // appends the level's tables to `blob` (offsets in `hdr` relative to hdr.base)

@@ -61,6 +61,10 @@ _FIELDS = {
     "mine_sdf_features": ((3,), torch.float32),
     "reach_status": ((), torch.int32),
 }
+# graph observations (NppBatch.graph_observation): shape per env and dtype; kept out of the packed output block, which numpy-mode
+# environments copy to the host every step
+GRAPH_KEYS = {"graph_node_feats": ((2500, 6), torch.float32), "graph_edge_index": ((2, 20000), torch.uint16),
+              "graph_node_mask": ((2500,), torch.uint8), "graph_edge_mask": ((20000,), torch.uint8)}
 _ALWAYS = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags", "terminal_state")
 _PACKED = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags")
 _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_frame", "global_view", "reachability_features",
@@ -403,6 +407,30 @@ class NppBatch:
         sw = C.c_void_p(t["switch_states"].data_ptr()) if with_switch_states else None
         nat.check(self.h, self.lib.npp_reachability_ex(self.h, *ptr, sw))
 
+    def graph_observation(self, node_feats=None, edge_index=None, node_mask=None, edge_mask=None, rewrite_all=False):
+        """The graph observations of every env (include/npp_amd.h npp_graph_observation): graph_node_feats f32 [N, 2500, 6],
+        graph_edge_index u16 [N, 2, 20000], graph_node_mask u8 [N, 2500], graph_edge_mask u8 [N, 20000], CUDA tensors updated
+        in place.  They are a constant of each env's level: only the rows of envs whose level changed since the last call are
+        rewritten.  Without arguments the four tensors are the batch's own (allocated at the first call, 162.5 KB per env,
+        outside the packed output block); a call with other tensors, or rewrite_all, rewrites every row.  Returns the four
+        tensors as a dict keyed by observation name."""
+        given = (node_feats, edge_index, node_mask, edge_mask)
+        if all(t is None for t in given):
+            if getattr(self, "_graph", None) is None:
+                with self._ctx():
+                    # (zeroed as int16: uint16 tensors have few kernels; the native call writes every row anyway)
+                    self._graph = {k: torch.zeros((self.n,) + shape, dtype=torch.int16 if dt == torch.uint16 else dt,
+                                                  device=self.device).view(dt) for k, (shape, dt) in GRAPH_KEYS.items()}
+            bufs = self._graph
+        else:
+            bufs = dict(zip(GRAPH_KEYS, given))
+            for k, (shape, dt) in GRAPH_KEYS.items():
+                t = bufs[k]
+                assert t is not None and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (self.n,) + shape, k
+        nat.check(self.h, self.lib.npp_graph_observation(self.h, *[C.c_void_p(bufs[k].data_ptr()) for k in GRAPH_KEYS],
+                                                         1 if rewrite_all else 0))
+        return bufs
+
     def render_frame(self, env0=0, count=1):
         """uint8 CUDA tensor [count, 600, 1056, 1]: the whole gray frame (the reference's render() array) of some envs."""
         with self._ctx():
@@ -551,6 +579,19 @@ def reach_level_info(map_data):
     nat.check(None, L.npp_reach_compile(m.ctypes.data_as(C.POINTER(C.c_double)), len(m), info.ctypes.data_as(C.c_void_p),
                                         *([None] * 11)))
     return {"supported": bool(info[0]), "nodes": int(info[1]), "mines": int(info[11]), "surface_area": int(info[13])}
+
+
+def graph_tables(map_data):
+    """Host-only: one level's graph observation rows (npp_graph_compile): (node_feats f32 [2500, 6], edge_index u16 [2, 20000],
+    num_nodes, num_edges); the masks are 1 on the first num_nodes / num_edges entries."""
+    L = nat.lib()
+    m = np.ascontiguousarray(np.asarray(map_data, dtype=np.float64))
+    feats = np.zeros(GRAPH_KEYS["graph_node_feats"][0], dtype=np.float32)
+    edges = np.zeros(GRAPH_KEYS["graph_edge_index"][0], dtype=np.uint16)
+    counts = np.zeros(2, dtype=np.int32)
+    nat.check(None, L.npp_graph_compile(m.ctypes.data_as(C.POINTER(C.c_double)), len(m), feats.ctypes.data_as(C.c_void_p),
+                                        edges.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+    return feats, edges, int(counts[0]), int(counts[1])
 
 
 def level_truncation_limit(map_data):

@@ -63,9 +63,11 @@ def check_frame_stack(visual_stack_size=4, state_stack_size=4, padding_type="zer
         raise ValueError("padding_type must be 'zero' or 'repeat'")
 
 
-def observation_space(visual=False, spatial_context=False, switch_states=False, reachability=False, visual_stack=0, state_stack=0):
+def observation_space(visual=False, spatial_context=False, switch_states=False, reachability=False, visual_stack=0, state_stack=0,
+                      graph=False):
     """visual_stack / state_stack: K > 0 stacks player_frame to (K, 84, 84, 1) / game_state to (K, 41) with the bounds of the
-    reference's stacked space (frame_stack_wrapper.py:139-181); global_view and the other keys pass through."""
+    reference's stacked space (frame_stack_wrapper.py:139-181); global_view and the other keys pass through.  graph: the four
+    graph observation keys (npp_environment.py:245-271)."""
     spaces = {
         "game_state": Box(-1.0, 1.0, (state_stack, 41) if state_stack else (41,), np.float32),
         "action_mask": Box(0, 1, (6,), np.int8),
@@ -81,4 +83,9 @@ def observation_space(visual=False, spatial_context=False, switch_states=False, 
     if reachability:   # npp_environment.py observation space: reachability_features (38), mine_sdf_features (3)
         spaces["reachability_features"] = Box(0.0, 1.0, (38,), np.float32)   # the reference declares [0, 1] (npp_environment.py:236)
         spaces["mine_sdf_features"] = Box(-1.0, 1.0, (3,), np.float32)
+    if graph:   # N_MAX_NODES = 2500, NODE_FEATURE_DIM = 6, E_MAX_EDGES = 20000 (graph/common.py:42-58)
+        spaces["graph_node_feats"] = Box(-np.inf, np.inf, (2500, 6), np.float32)
+        spaces["graph_edge_index"] = Box(0, 2499, (2, 20000), np.uint16)
+        spaces["graph_node_mask"] = Box(0, 1, (2500,), np.uint8)
+        spaces["graph_edge_mask"] = Box(0, 1, (20000,), np.uint8)
     return Dict(spaces)

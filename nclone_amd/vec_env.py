@@ -15,7 +15,7 @@ import torch
 
 from . import _native as nat
 from . import spaces
-from .engine import NppBatch
+from .engine import GRAPH_KEYS, NppBatch, _as_f64_blob, graph_tables
 
 ACTION_TABLE = [(0, 0), (-1, 0), (1, 0), (0, 1), (-1, 1), (1, 1)]  # base_environment.py:366-402
 DEATH_CAUSES = {0: None, 1: "mine", 2: "terminal_impact", 3: None}   # 3: drone / thwump / death ball / crush: kill() without a cause
@@ -91,6 +91,14 @@ class NppVecEnvironment:
     reference's Python `random` stream.  reset(seed=s) reseeds the pool with s.  set_level_weights() changes the weights between
     steps (curriculum); expand_category_weights() turns per-category weights into per-level ones.  level_weights=None (default):
     every env keeps the level level_ids gives it, as before.  info["level_id"] (both modes): the level each env plays after the step.
+
+    Graph observations (the reference's EnvironmentConfig.enable_graph_observations): enable_graph_observations=True
+    adds graph_node_feats [N, 2500, 6] f32, graph_edge_index [N, 2, 20000] u16, graph_node_mask [N, 2500] u8 and graph_edge_mask
+    [N, 20000] u8, and their Boxes to observation_space.  The reference builds the graph at every reset from the loaded level and
+    keeps it for the episode, so the rows are a constant of each env's level: they are rewritten only for envs whose level changed.
+    output="torch": persistent device tensors updated in place (the same lifetime as the other keys).  output="numpy": two host
+    buffer sets alternate, filled from host copies of the per-level tables (no per-step device-to-host copy of these 162.5 KB per
+    env), so the previous step's arrays stay valid.  Not part of the terminal info.  Off by default.
     """
 
     metadata = {"render_modes": []}
@@ -99,7 +107,7 @@ class NppVecEnvironment:
                  truncation_limit="dynamic", output="torch", autoreset=True, enable_spatial_context=False,
                  enable_switch_states=False, fast_reset=True, stream=None, enable_reachability=False, obs_overlap=0,
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
-                 frame_stack_padding_type="zero", level_weights=None, level_seed=None):
+                 frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False):
         assert output in ("torch", "numpy")
         spaces.check_frame_stack(visual_stack_size, state_stack_size, frame_stack_padding_type)
         self.num_envs = int(num_envs)
@@ -114,7 +122,8 @@ class NppVecEnvironment:
                                                                  spatial_context=bool(enable_spatial_context),
                                                                  switch_states=bool(enable_switch_states),
                                                                  reachability=bool(enable_reachability),
-                                                                 visual_stack=self._vk, state_stack=self._sk)
+                                                                 visual_stack=self._vk, state_stack=self._sk,
+                                                                 graph=bool(enable_graph_observations))
         self.action_space = self.single_action_space
         self.observation_space = self.single_observation_space
         outputs = ["positions"]
@@ -163,6 +172,9 @@ class NppVecEnvironment:
                 with self._b._ctx():
                     self._term_stack = torch.zeros((self.num_envs, self._sk, 41), dtype=torch.float32, device=self._b.device)
             self._host_stack = {}   # name -> [pinned buffer, pinned buffer, next]: host copies alternate like the output block's
+        self._graph = None
+        if enable_graph_observations:
+            self._graph = _HostGraphRows(levels, self.num_envs) if output == "numpy" else {}
 
     # -- helpers ------------------------------------------------------------------------------------------------
     def _produce(self, reset_all=False):
@@ -181,6 +193,8 @@ class NppVecEnvironment:
         if "reachability_features" in b.out.t:
             b.reachability(with_switch_states=fused)
         b.join()   # (obs_overlap) the handle's stream waits for the kernels that went to the second stream
+        if self._graph is not None and self.output == "torch":
+            self._graph = b.graph_observation()
         if self._vk or self._sk:
             b.frame_stack_push(self._reset_bits, reset_all, None if reset_all else self._term_stack)
 
@@ -283,11 +297,11 @@ class NppVecEnvironment:
         self._b.observe()
         self._produce(reset_all=True)
         if self.output == "torch":
-            return self._obs(self._stacked(self._b.out.t)), info
+            return self._with_graph(self._obs(self._stacked(self._b.out.t))), info
         stk = self._stacked({})
         src = self._b.to_host(self._obs_names)
         src.update(stk)
-        return self._obs(src), info
+        return self._with_graph(self._obs(src)), info
 
     @property
     def _level_weights_now(self):
@@ -306,6 +320,17 @@ class NppVecEnvironment:
             with self._b._ctx():
                 return self._b.env_level_view().clone()
         return self._level_ids_np.copy() if numpy else self._level_ids
+
+    def _with_graph(self, obs, levels=None):
+        """obs plus the graph keys (enable_graph_observations): the device tensors (torch), or the host buffer set of this
+        observation, brought up to the levels the envs play (numpy)."""
+        if self._graph is None:
+            return obs
+        if self.output == "torch":
+            obs.update(self._graph)
+        else:
+            obs.update(self._graph.update(self._level_id(True) if levels is None else levels))
+        return obs
 
     def snapshot(self):
         """Save the state of every env on the device (one slot); reset(options={"checkpoint": "snapshot"}) restores it."""
@@ -350,7 +375,7 @@ class NppVecEnvironment:
         if "terminal_game_state_stack" in src:
             info["terminal_game_state_stack"] = src["terminal_game_state_stack"]
         info["level_id"] = self._level_id(self.output == "numpy")
-        return self._obs(src), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
+        return self._with_graph(self._obs(src), info["level_id"]), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
         """actions: int array/tensor [N] in 0..5.  Returns (obs, reward, terminated, truncated, info) with batch dims."""
@@ -365,6 +390,45 @@ class NppVecEnvironment:
         return self._b
 
 
+class _HostGraphRows:
+    """output="numpy" graph observations: the device's changed-rows rule on the host.  Two buffer sets alternate (the previous
+    observation's arrays stay valid); each records the level its rows hold and rewrites, whole, the rows of envs whose level
+    differs.  The per-level rows come from npp_graph_compile, built the first time a level is needed."""
+
+    def __init__(self, levels, n):
+        self._blob, self._off = _as_f64_blob(levels)
+        self._n = n
+        self._tabs = {}
+        self._sets = [None, None]
+        self._next = 0
+
+    def _table(self, level):
+        t = self._tabs.get(level)
+        if t is None:
+            feats, edges, nn, ne = graph_tables(self._blob[self._off[level]:self._off[level + 1]])
+            t = self._tabs[level] = {"graph_node_feats": feats, "graph_edge_index": edges,
+                                     "graph_node_mask": (np.arange(2500) < nn).astype(np.uint8),
+                                     "graph_edge_mask": (np.arange(20000) < ne).astype(np.uint8)}
+        return t
+
+    def update(self, levels):
+        levels = np.asarray(levels, dtype=np.int32)
+        k = self._next
+        self._next ^= 1
+        if self._sets[k] is None:
+            np_dtype = {torch.float32: np.float32, torch.uint16: np.uint16, torch.uint8: np.uint8}
+            bufs = {name: np.zeros((self._n,) + shape, dtype=np_dtype[dt]) for name, (shape, dt) in GRAPH_KEYS.items()}
+            self._sets[k] = (bufs, np.full(self._n, -1, dtype=np.int32))
+        bufs, held = self._sets[k]
+        changed = np.flatnonzero(held != levels)
+        for level in np.unique(levels[changed]):
+            envs = changed[levels[changed] == level]
+            for name, row in self._table(int(level)).items():
+                bufs[name][envs] = row
+            held[envs] = level
+        return dict(bufs)
+
+
 class NppEnvironment:
     """Single-environment adapter with the reference's exact call signatures (base_environment.py:483,
     npp_environment.py:504).  One GPU lane group does the work of one Python simulator; use NppVecEnvironment for
@@ -374,7 +438,7 @@ class NppEnvironment:
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
-                 state_stack_size=4, frame_stack_padding_type="zero"):
+                 state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False):
         if map_data is None:
             if custom_map_path is None:
                 raise ValueError("NppEnvironment needs map_data or custom_map_path")
@@ -387,7 +451,8 @@ class NppEnvironment:
                                     enable_switch_states=enable_switch_states, enable_reachability=enable_reachability,
                                     enable_visual_frame_stacking=enable_visual_frame_stacking, visual_stack_size=visual_stack_size,
                                     enable_state_stacking=enable_state_stacking, state_stack_size=state_stack_size,
-                                    frame_stack_padding_type=frame_stack_padding_type)
+                                    frame_stack_padding_type=frame_stack_padding_type,
+                                    enable_graph_observations=enable_graph_observations)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
