@@ -692,6 +692,22 @@ void build_reach(const CompiledLevel &L, ReachBuilt &R) {
             }
         }
     }
+    // ---- a goal the level cache does not reach from the spawn.  The cache holds distances FROM the goal node along the directed
+    //      `adjacency` (one-way drops); a pocket that only leads out towards the goal keeps +inf there.  With the spawn in such a
+    //      pocket, get_distance leaves the level cache on the first observation of every episode and runs its physics A* search
+    //      (path_distance_calculator.py:1218-1485; nclone/test_maps/complex-path-switch-required: both goals, 29 nodes around the
+    //      spawn).  That branch is only restated for the exit door of the miss_exit levels: refused like several exits.
+    if (H.supported) {
+        ReachHdr P;
+        std::vector<unsigned char> blob;
+        pack_reach(R, P, blob);
+        const ReachTabs T{&P, blob.data() + P.base};
+        float f[REACH_DIM], sd[3];
+        if (reach_features(T, L.spawn_x, L.spawn_y, H.n_mines, 0, f, sd) & 1) {
+            H.supported = 0;
+            R.note = "a goal is not in the level cache at the spawn (the reference runs its physics A* search there)";
+        }
+    }
 }
 
 // pack one level's tables behind `hdr` into `blob` (16-byte aligned sections); offsets are relative to the blob start

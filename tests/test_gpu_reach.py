@@ -18,6 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # levels whose exit door lies within 24 px of its switch: every exit-door query takes the reference's cache-miss branch there
 MISS_BRANCH = {"doors:hcorr:door:100053", "mines:hcorr:mines:100025", "c0:replay:20", "c0:replay:63", "c0:replay:68", "c0:replay:78",
                "mines:hcorr:mines:100008"}
+# reach4.npz: the spawn lies where the level cache has no distance to either goal; refused (test_reach_host.py)
+REFUSED = {"test_maps:complex-path-switch-required"}
 OUT = ("positions", "reachability_features", "mine_sdf_features", "reach_status")
 
 
@@ -63,23 +65,47 @@ def _follow_rollouts(levels, names, ra, rp, rf, rm=None):
     b.close()
 
 
-@pytest.mark.parametrize("fixture", ["reach.npz", "reach2.npz", "reach3.npz"])
+@pytest.mark.parametrize("fixture", ["reach.npz", "reach2.npz", "reach3.npz", "reach4.npz"])
 def test_reachability_along_reference_rollouts(fixture):
     """reach.npz: 43 levels (locked doors, mines, exit-only); reach2.npz: 83 more (all 26 entity-zoo maps -- drones, thwumps,
     doors of every kind, launch pads ... --, 48 of config 4's generated levels).  7 of the 126 are the levels npp_reachability
     refused until round 3 (MISS_BRANCH): the reference answers their exit-door queries with its physics A* and keeps the costs in
     a per-episode dictionary, so these rows also pin the episode bookkeeping on the device (state word E's episode counter)."""
     z, names, _sup = _load(fixture)
-    ks = list(range(len(names)))
+    ks = [k for k in range(len(names)) if names[k] not in REFUSED]
     recomputed = int(sum(z["rc%d" % k].sum() for k in ks))
     episodes = int(sum(z["rt%d" % k].sum() for k in ks))
     if fixture == "reach3.npz":   # four of the reference's five official tutorial levels (the fifth: test_reach_host.py)
         assert len(ks) == 4 and recomputed > 250
+    elif fixture == "reach4.npz":   # 15 of the reference's 16 held-out test maps (the 16th: test_refused_test_map_fails_loudly)
+        assert len(ks) == 15 and recomputed == 938 and episodes == 41
+        assert {"test_maps:slopes", "test_maps:minefield"} <= {names[k] for k in ks}
     else:
         assert sum(names[k] in MISS_BRANCH for k in ks) in (2, 5)
         assert recomputed > 1800 and episodes > 40 and len(ks) >= 43
     _follow_rollouts([z["m%d" % k] for k in ks], [names[k] for k in ks], np.stack([z["ra%d" % k] for k in ks]),
                      np.stack([z["rp%d" % k] for k in ks]), np.stack([z["rf%d" % k] for k in ks]), np.stack([z["rm%d" % k] for k in ks]))
+
+
+def test_refused_test_map_fails_loudly():
+    """`complex-path-switch-required` (reach4.npz): every episode starts where the reference leaves its level cache for both goals
+    (its physics A* search, not restated for the switch), so npp_reachability refuses the level instead of serving flagged rows;
+    the physics path still steps it."""
+    from nclone_amd import _native as nat
+    from nclone_amd.engine import NppBatch
+
+    z, names, _sup = _load("reach4.npz")
+    k = names.index("test_maps:complex-path-switch-required")
+    b = NppBatch(64, outputs=OUT)
+    b.load_levels([z["m%d" % (k + 1)], z["m%d" % k]])
+    b.assign_levels(np.arange(64) % 2)
+    b.reset()
+    with pytest.raises(nat.NppError) as e:
+        b.reachability()
+    assert e.value.code == nat.NPP_ERR_UNSUPPORTED and "level 1" in str(e.value) and "level cache at the spawn" in str(e.value)
+    b.step(torch.zeros(64, dtype=torch.uint8, device="cuda"))
+    torch.cuda.synchronize()
+    b.close()
 
 
 def test_reachability_dictionary_shared_by_switch_and_door():

@@ -13,16 +13,19 @@ torch = pytest.importorskip("torch")
 N = 8192
 
 
-def test_config4_mixed_set_shard_vs_oracle(oracle_mod):
+@pytest.mark.parametrize("shard", [0, 1, 2, 3])
+def test_config4_mixed_set_shard_vs_oracle(oracle_mod, shard):
     """One GPU's shard of config 4 (8192 of the 65 536 envs) on the 512-level mixed set: replicas hold identical bits, a
-    192-env sample re-simulated by the CPU oracle matches bit for bit, G = 1 equals G = 16."""
+    192-env sample re-simulated by the CPU oracle matches bit for bit, G = 1 equals G = 16.  Shards 0-3 cover level blocks
+    0-511 (8192 / 64 = 128 blocks each), so every level of the set runs under this shard layout."""
     from nclone_amd.engine import NppBatch
     from nclone_amd.levels import c3_mixed_levels
 
     levels, tags = c3_mixed_levels()
     assert len(levels) == 512
-    # shard 3 of 8: global env index decides the level, as in bench.py
-    level_ids = ((np.arange(N) + 3 * N) // 64) % len(levels)
+    # shard `shard` of 8: global env index decides the level, as in bench.py
+    level_ids = ((np.arange(N) + shard * N) // 64) % len(levels)
+    assert np.array_equal(np.unique(level_ids), np.arange(128 * shard, 128 * (shard + 1)) % len(levels))
     steps = 60
     acts_np = np.random.default_rng(2).integers(0, 6, size=(steps, N)).astype(np.uint8).reshape(steps, N // 64, 64)
     acts_np[:, :, 32:] = acts_np[:, :, :32]

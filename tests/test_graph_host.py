@@ -31,10 +31,9 @@ def test_fixture_covers_the_cases(graph):
     assert int(z["nn%d" % k]) == 2500 and int(z["ne%d" % k]) > 19000   # node list truncated, edges into it skipped
 
 
-def test_graph_compile_matches_reference(graph):
+def _compare_graph_rows(z, names):
     from nclone_amd.engine import graph_tables
 
-    z, names = graph
     for k, name in enumerate(names):
         feats, edges, nn, ne = graph_tables(z["m%d" % k])
         assert (nn, ne) == (int(z["nn%d" % k]), int(z["ne%d" % k])), name
@@ -42,6 +41,23 @@ def test_graph_compile_matches_reference(graph):
         assert not feats[nn:].any(), name
         assert np.array_equal(edges[:, :ne], z["e%d" % k]), name
         assert not edges[:, ne:].any(), name
+
+
+def test_graph_compile_matches_reference(graph):
+    _compare_graph_rows(*graph)
+
+
+def test_graph_compile_matches_reference_on_test_maps():
+    """graph2.npz (make_golden_graph.py 2): the reference's 16 held-out test maps -- locked doors, a trap door and one-way
+    platforms, 29 toggle mines, four open maps past the 2500-node limit, a map without entities."""
+    from nclone_amd import build_native
+
+    build_native.build()
+    z = np.load(os.path.join(ROOT, "tests", "golden", "graph2.npz"))
+    names = bytes(z["names"]).decode().split("\n")
+    assert len(names) == 16 and all(n.startswith("test_maps:") for n in names)
+    assert sum(int(z["nn%d" % k]) == 2500 for k in range(16)) == 4
+    _compare_graph_rows(z, names)
 
 
 def test_several_exits_and_empty_adjacency():

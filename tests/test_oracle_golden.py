@@ -337,3 +337,75 @@ def test_oracle_fast_reset_rollouts(golden, oracle_mod, fixture, rollouts, total
         assert row == len(T)
         ticks += row
     assert ticks == total_ticks
+
+
+HELDOUT_TRUNC = 240   # tests/golden/make_golden_heldout.py: TRUNC
+
+
+@pytest.mark.parametrize("variant", ["pow", "mul"])
+def test_oracle_heldout_replays(golden, oracle_mod, variant):
+    """The reference's held-out replays (`bc_replays_tmp/`, heldout.npz from make_golden_heldout.py): six human runs of a level
+    no other fixture holds ("006 both flavours of ramp jumping": ramp jumps, slope landings, entity types 1, 2, 3) and two runs
+    corpus.npz already has.  Every tick bit for bit, under the libm-pow squaring and the multiply-square twin of the GPU."""
+    h = golden.z("heldout")
+    names = golden.names("heldout")
+    assert len(names) == 8 and sum("ramp jumping" in n for n in names) == 6
+    corpus = golden.names("corpus")
+    assert sum(n in corpus for n in names) == 2
+    ticks = 0
+    for i in range(len(names)):
+        o = oracle_mod.Oracle(variant)
+        assert o.load(h["m%d" % i].astype(np.float64)) == 0
+        T, D = h["t%d" % i], h["d%d" % i]
+        for k in range(len(T)):
+            hh, j = oracle_mod.controls(int(h["in%d" % i][k]))
+            o.tick(hh, j)
+            f, d = o.core()
+            assert np.array_equal(f[:4], T[k]), (names[i], k, f[:4], T[k])
+            assert np.array_equal(d[:20].clip(0, 255), D[k]), (names[i], k)
+        final = h["final"][i]
+        assert (int(final[0]), int(final[1])) == (len(T), int(d[0])) and f[0] == final[2] and f[1] == final[3], names[i]
+        ticks += len(T)
+    assert ticks == 2796 and np.all(h["final"][:, 1] == 8)
+
+
+@pytest.mark.parametrize("variant", ["pow", "mul"])
+def test_oracle_heldout_test_map_rollouts(golden, oracle_mod, variant):
+    """Random-action frame-skip rollouts on all 16 of the reference's `nclone/test_maps/` (heldout.npz): locked doors, a trap
+    door and one-way platforms, 29 toggle mines, a map without entities.  Episodes end on a win, a death or sim.frame >= 240;
+    the first reset of a rollout is Simulator.reset, the later ones Simulator.fast_reset.  Every tick's ninja state, and per
+    step the end kind, game_state, action mask and entity checksum, bit for bit."""
+    h = golden.z("heldout")
+    names = golden.names("heldout", "rnames")
+    assert len(names) == 16
+    ticks = 0
+    kinds = np.zeros(4, np.int64)
+    for r in range(len(names)):
+        o = oracle_mod.Oracle(variant)
+        assert o.load(h["rm%d" % r]) == 0, names[r]
+        T, D, S, G, K, E = (h["r%s%d" % (k, r)] for k in "tdsgke")
+        row = resets = 0
+        for s, a in enumerate(h["ra%d" % r]):
+            hh, j = oracle_mod.ACTIONS[int(a)]
+            ex, kind, frame, mode = (int(v) for v in S[s])
+            for _ in range(ex):
+                o.tick(hh, j)
+                f, d = o.core()
+                assert np.array_equal(f[:4], T[row]), (names[r], s, row, f[:4], T[row])
+                assert np.array_equal(d[:20].clip(0, 255), D[row]), (names[r], s, row)
+                row += 1
+            got = 1 if d[0] == 8 else (2 if d[0] in (6, 7) else (3 if o.frame >= HELDOUT_TRUNC else 0))
+            assert (got, o.frame) == (kind, frame), (names[r], s)
+            assert np.array_equal(o.ninja_state().astype(np.float32), G[s]), (names[r], s)
+            assert o.action_mask() == K[s], (names[r], s)
+            assert np.array_equal(o.entity_checksum(), E[s]), (names[r], s, o.entity_checksum(), E[s])
+            kinds[kind] += 1
+            assert mode == (0 if kind == 0 else (1 if resets == 0 else 2)), (names[r], s)
+            resets += kind != 0
+            if mode == 1:
+                o.reset()
+            elif mode == 2:
+                o.fast_reset()
+        assert row == len(T)
+        ticks += row
+    assert ticks == 10213 and tuple(kinds[1:]) == (7, 9, 28)   # won, dead, truncated
