@@ -70,6 +70,7 @@ enum {
 #define NPP_ACTION_DIM 6        /* base_environment.py:150 Discrete(6) */
 #define NPP_ENTITY_POS_DIM 6    /* observation_processor.py:340-361 */
 #define NPP_SPATIAL_CONTEXT_DIM 112 /* gym_environment/constants.py SPATIAL_CONTEXT_DIM */
+#define NPP_MINIMAL_OBS_DIM 40  /* gym_environment/constants.py MINIMAL_OBSERVATION_DIM */
 #define NPP_FRAME_W 84          /* gym_environment/constants.py:12-13 */
 #define NPP_FRAME_H 84
 #define NPP_DUMP_F64 12
@@ -197,6 +198,37 @@ int npp_reachability(npp_handle h, float *d_features, float *d_mine_sdf, int32_t
 /* ... and, when d_switch_states (f32[n_envs][25]) is not NULL, npp_switch_states's output from the same launch (an idle lane of
  * every env's lane group writes it: the full observation Dict needs one kernel less). */
 int npp_reachability_ex(npp_handle h, float *d_features, float *d_mine_sdf, int32_t *d_status, float *d_switch_states);
+
+/* The reference's MINIMAL observation mode (gym_environment/config.py:17-20 `observation_mode`; space npp_environment.py:211-231,
+ * content :2232-2270): minimal_observation f32[n_envs][40] = compute_minimal_observation (observation_processor.py:505-567):
+ *    0-11  xspeed / MAX_HOR_SPEED, yspeed / MAX_HOR_SPEED, one-hot of min(state, 4), airborn and walled as +-1, wall_normal if
+ *          walled else 0, floor_normalized_x / y
+ *   12-19  reachability_features[13:15], [15:17], [8:10], [12], [24]
+ *   20-35  the first 4 of the 8 nearest mines of spatial_context[64:], features 0, 1, 2, 5 of each 6
+ *   36-39  jump_buffer / 5, floor_buffer / 5, wall_buffer / 5, launch_pad_buffer / 4, or -1 where the buffer is negative
+ * every quotient in f64 and rounded once to f32, as the reference's assignment into its float32 array does.
+ * npp_set_minimal_observation(h, enable): the mode's switch (off by default).  The mine columns are the step kernel's
+ *   spatial_context rows, so while the mode is on every npp_step / npp_step_many / npp_observe writes them: into the caller's
+ *   d_spatial_context, or, when the npp_step_out has none, into a buffer of the handle (448 bytes per env, allocated by the first such
+ *   launch, freed by npp_destroy).  Nothing else changes; with the mode off nothing new runs.  The handle remembers WHERE the last
+ *   such launch wrote the rows and npp_minimal_observation reads there: a caller's d_spatial_context must stay allocated until the
+ *   next of these launches; a caller that frees or replaces the buffer first calls npp_set_minimal_observation(h, 1) again, which
+ *   makes the handle forget the pointer (npp_minimal_observation is then NPP_ERR_STATE until the next launch).
+ * npp_minimal_observation(h, d_out, d_status): the rows of the current state, from npp_reachability's launch -- it IS the
+ *   observation's reachability call (same cache rule, same tables, same d_status), it additionally assembles the 40 floats, and it
+ *   writes neither reachability_features nor mine_sdf_features.  Call it after the npp_step / npp_observe of the observation
+ *   (NPP_ERR_STATE when there was none since the mode was switched on).  A call of npp_reachability[_ex] for the same observation,
+ *   before or after, finds the key unchanged and both give the bits either gives alone.  The rows are a function of saved state
+ *   only: npp_snapshot / npp_restore, resets, the level pool and the observation overlap (one launch per part) need nothing new.
+ *   Refused like npp_reachability: NPP_ERR_UNSUPPORTED for levels with several exit switches and while an entity is repositioned with
+ *   npp_set_entity_pos.  There is no terminal minimal observation (the reference defines none). */
+int npp_set_minimal_observation(npp_handle h, int enable);
+/* Host-only: the state encodings the device kernel runs (npp_minimal.hpp compiles for both) -- columns 0-11 and 36-39 of `count` rows
+ * out f32[count][40] (the other columns are left alone) from state_a u32[count] (state word A: state bits 0-3, airborn 4, walled 6,
+ * wall normal + 1 bits 7-8, jump / floor / wall / launch pad buffer + 1 at bits 15, 18, 21, 24, three bits each) and planes
+ * f64[count][4] = xspeed, yspeed, floor_normalized_x, floor_normalized_y. */
+int npp_minimal_encode_host(const uint32_t *state_a, const double *planes, int count, float *out);
+int npp_minimal_observation(npp_handle h, float *d_out /* [N,40] */, int32_t *d_status /* [N] or NULL */);
 
 /* The whole gray frame of envs [env0, env0 + count): what NPlayHeadless.render() returns in grayscale mode
  * (nplay_headless.py:144-156, nsim_renderer.py:71-134).  d_out: u8[count][600][1056]. */

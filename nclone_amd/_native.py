@@ -19,6 +19,7 @@ FLAG_FRAME_CENTERED = 4
 FLAG_FAST_RESET = 8
 F_WON, F_DEAD, F_SWITCH, F_TRUNCATED, F_CAUSE_MINE, F_CAUSE_IMPACT = 1, 2, 4, 8, 16, 32
 GAME_STATE_DIM = 41
+MINIMAL_OBS_DIM = 40
 DUMP_F64 = 12
 DUMP_I32 = 32
 
@@ -33,6 +34,7 @@ EXPORTS = [
     "npp_set_frame_stack", "npp_frame_stack_render", "npp_frame_stack_push", "npp_frame_stack_view",
     "npp_set_level_pool", "npp_draw_levels", "npp_get_env_levels", "npp_env_level_view", "npp_level_pool_draw_host",
     "npp_graph_observation", "npp_graph_compile",
+    "npp_set_minimal_observation", "npp_minimal_observation", "npp_minimal_encode_host",
 ]
 
 
@@ -134,6 +136,9 @@ def lib():
     L.npp_graph_compile.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.npp_level_pool_draw_host.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int,
                                            C.POINTER(C.c_int32)]
+    L.npp_set_minimal_observation.argtypes = [H, C.c_int]
+    L.npp_minimal_observation.argtypes = [H, C.c_void_p, C.c_void_p]
+    L.npp_minimal_encode_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

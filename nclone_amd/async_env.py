@@ -82,12 +82,16 @@ class NppAsyncVecEnvironment:
     step_async_partial(k, actions) re-enqueue just sub-batch k
 
     No frame stacking here (NppVecEnvironment has it): observations are single entries.  No graph observations either
-    (NppVecEnvironment(enable_graph_observations=True) has them).
+    (NppVecEnvironment(enable_graph_observations=True) has them), and no minimal observation mode: observation_mode other than
+    "full" is refused (NppVecEnvironment(observation_mode="minimal") has it).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
-                 output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None):
+                 output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full"):
         assert output in ("torch", "numpy")
+        if observation_mode != "full":
+            raise NotImplementedError("NppAsyncVecEnvironment has no observation_mode other than 'full' (%r asked for): "
+                                      "NppVecEnvironment(observation_mode='minimal') has the minimal observation" % (observation_mode,))
         if level_weights is not None or level_seed is not None:
             raise NotImplementedError("NppAsyncVecEnvironment has no level pool (level_weights): use NppVecEnvironment")
         self.num_envs, self.frame_skip, self.output = int(num_envs), int(frame_skip), output

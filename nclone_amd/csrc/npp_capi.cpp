@@ -213,6 +213,15 @@ struct Pool {
     DevBuf<uint8_t> changed;   // [n] envs that drew another level (device reset / observe mask)
 };
 
+// minimal observation (npp_set_minimal_observation / npp_minimal_observation): its mine columns are read from the spatial_context
+// rows of the step kernel, so with the mode on every step / observe launch writes them -- into the caller's d_spatial_context, or
+// into `sc` when the caller's npp_step_out has none
+struct Minimal {
+    bool on = false;
+    DevBuf<float> sc;            // [n][112], allocated by the first launch that needs it
+    const float *rows = nullptr; // where the last step / observe launch wrote the rows (the caller's buffer or `sc`)
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -243,6 +252,7 @@ struct npp_handle_s {
     Overlap ov;
     FrameStack fs;
     Pool pool;
+    Minimal mini;
 };
 
 
@@ -519,6 +529,23 @@ void fill_out(KernelArgs &a, const npp_step_out *o) {
     a.out.work = o->d_work;
 }
 
+// fill_out for the launches that produce an observation (step, step_many, observe, the level pool's masked observe): with the
+// minimal observation on, a launch whose caller asked for no spatial_context writes the rows into the handle's own buffer
+int fill_obs_out(npp_handle h, KernelArgs &a, const npp_step_out *o) {
+    fill_out(a, o);
+    Minimal &m = h->mini;
+    if (!m.on) return NPP_OK;
+    if (!a.out.spatial_context) {
+        if (!m.sc) {
+            HIP_TRY(h, m.sc.alloc((size_t)h->n * NPP_SPATIAL_CONTEXT_DIM));
+            HIP_TRY(h, hipMemsetAsync(m.sc.get(), 0, m.sc.bytes(), h->stream));
+        }
+        a.out.spatial_context = m.sc.get();
+    }
+    m.rows = a.out.spatial_context;
+    return NPP_OK;
+}
+
 // The render kernels read the tile layer from a per-level coverage canvas (npp_render.hip); it is built the first time a
 // frame is asked for, so handles that never render pay neither the memory (633 600 B per level) nor the kernel.
 int ensure_canvas(npp_handle h) {
@@ -705,7 +732,7 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
         o.n_ticks = 0;
         o.mode = 0;
         o.autoreset = 0;
-        fill_out(o, out);
+        if (int rc = fill_obs_out(h, o, out)) return rc;
         o.out.flags = nullptr; o.out.reward = nullptr; o.out.frames = nullptr; o.out.terminal_state = nullptr; o.out.work = nullptr;
         o.obs_mask = h->pool.changed.get();
         HIP_TRY(h, launch_step(o, h->stream));
@@ -1251,7 +1278,7 @@ int step_impl(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_
     a.inputs = d_actions;
     a.n_ticks = frame_skip;
     a.mode = 0;
-    fill_out(a, out);
+    if (int rc = fill_obs_out(h, a, out)) return rc;
     Orders &o = h->ord;
     {   // heavy-first workgroup order: rebuilt from the per-block costs every 16th launch (and whenever the launch geometry changes)
         const int epb = (64 / (h->plan.g > 0 ? h->plan.g : 1)) * (h->plan.wpb > 0 ? h->plan.wpb : 1);
@@ -1350,7 +1377,7 @@ int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame
     a.n_ticks = frame_skip;
     a.n_steps = n_steps;
     a.mode = 0;
-    fill_out(a, out);
+    if (int rc = fill_obs_out(h, a, out)) return rc;
     a.out.terminal_state = nullptr;   // pre-reset observations exist for single steps only
     HIP_TRY(h, launch_step(a, h->stream));
     return NPP_OK;
@@ -1377,7 +1404,7 @@ int npp_observe(npp_handle h, const npp_step_out *out) {
     a.n_ticks = 0;
     a.mode = 0;
     a.autoreset = 0;
-    fill_out(a, out);
+    if (int rc = fill_obs_out(h, a, out)) return rc;
     HIP_TRY(h, launch_step(a, h->stream));
     return NPP_OK;
 }
@@ -1545,7 +1572,33 @@ int npp_reachability_ex(npp_handle h, float *d_features, float *d_mine_sdf, int3
     KernelArgs a = base_args(h);
     const Reach &r = h->ls.reach;
     return obs_launch(h, a, false, tables, [&](const KernelArgs &ka, hipStream_t st) {   // (tables: ensure_reach has just built them)
-        return launch_reach(ka, r.hdr.get(), r.blob.get(), r.key.get(), r.cache.get(), r.miss(), d_features, d_mine_sdf, d_status, d_switch_states, st);
+        return launch_reach(ka, r.hdr.get(), r.blob.get(), r.key.get(), r.cache.get(), r.miss(), d_features, d_mine_sdf, d_status, d_switch_states,
+                            nullptr, nullptr, st);
+    });
+}
+
+int npp_set_minimal_observation(npp_handle h, int enable) {
+    if (!h) return NPP_ERR_INVALID;
+    h->mini.on = enable != 0;
+    h->mini.rows = nullptr;   // the next step / observe launch says where the rows are
+    return NPP_OK;
+}
+
+int npp_minimal_observation(npp_handle h, float *d_out, int32_t *d_status) {
+    if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_minimal_observation: bad arguments");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_minimal_observation: no levels loaded");
+    if (!h->mini.on) return fail(h, NPP_ERR_STATE, "npp_minimal_observation: switch the mode on first (npp_set_minimal_observation)");
+    if (!h->mini.rows)
+        return fail(h, NPP_ERR_STATE, "npp_minimal_observation: no npp_step / npp_observe since the mode was switched on (they write the mine rows)");
+    if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_reachability: exit switch / door repositioned with npp_set_entity_pos");
+    ON_DEVICE(h);
+    const bool tables = !h->ls.reach.hdr;
+    if (int rc = ensure_reach(h)) return rc;   // (refuses what npp_reachability refuses, with its message)
+    KernelArgs a = base_args(h);
+    const Reach &r = h->ls.reach;
+    const float *rows = h->mini.rows;
+    return obs_launch(h, a, false, tables, [&](const KernelArgs &ka, hipStream_t st) {
+        return launch_reach(ka, r.hdr.get(), r.blob.get(), r.key.get(), r.cache.get(), r.miss(), nullptr, nullptr, d_status, nullptr, d_out, rows, st);
     });
 }
 

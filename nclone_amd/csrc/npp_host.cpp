@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../../include/npp_amd.h"
+#include "npp_minimal.hpp"
 #include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
 
@@ -26,6 +27,13 @@ int fail(std::nullptr_t, int code, const std::string &msg) {
 }  // namespace
 
 extern "C" {
+
+int npp_minimal_encode_host(const uint32_t *state_a, const double *planes, int count, float *out) {
+    if (count < 0 || (count > 0 && (!state_a || !planes || !out))) return fail(nullptr, NPP_ERR_INVALID, "npp_minimal_encode_host: bad arguments");
+    for (int i = 0; i < count; i++)
+        minobs_encode_state(state_a[i], planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3], out + (size_t)i * MINOBS_DIM);
+    return NPP_OK;
+}
 
 int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed, const int32_t *envs, const uint32_t *counts, int count,
                              int32_t *out) {

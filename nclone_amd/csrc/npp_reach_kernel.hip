@@ -5,9 +5,12 @@
 // (gym_environment/mixins/reachability_mixin.py:150-222), kept because the cached vector is what the reference returns.
 // Roofline: latency/issue bound; bytes per env = 152 (features out) + 12 (sdf out) + 16 (x, y) + 8 (key, level) + 156 cache
 // row read (+ written back when recomputed) ~ 350 B -> 2.9 MB per launch at 8192 envs.
+// The same launch assembles the minimal observation (npp_minimal_observation: f32[N, 40]) when asked to: 160 B out
+// per env instead of the 164 above, + 40 B of state planes and 64 B of the step kernel's spatial_context row read.
 #include <hip/hip_runtime.h>
 
 #include "npp_internal.hpp"
+#include "npp_minimal.hpp"
 #include "npp_reach_features.hpp"
 
 namespace npp {
@@ -20,11 +23,16 @@ namespace {
 // is the right layout for that; round 2 had one lane walk its own 156-byte row).
 constexpr int REACH_EPB = 16;
 
+// minimal observation (npp_minimal_observation; npp_minimal.hpp has the state encodings)
+// columns 12-19 = reachability_features[13:15], [15:17], [8:10], [12], [24]: one byte per column, column 12 in the low byte
+constexpr unsigned long long MINOBS_REACH_COLS = 0x180C0908100F0E0DULL;   // 13, 14, 15, 16, 8, 9, 12, 24
+
 __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const ReachHdr *rh, const unsigned char *rblob, uint32_t *key,
                                                        float *cache, ReachMissDev md, float *out, float *sdf_out, int32_t *status,
-                                                       float *sw_out) {
+                                                       float *sw_out, float *min_out, const float *sc_rows) {
     __shared__ float rows[REACH_EPB * (REACH_DIM + 1)];
     __shared__ float sdfs[REACH_EPB * 3];
+    __shared__ float mins[REACH_EPB * MINOBS_DIM];   // the 16 envs' minimal rows: 2560 contiguous bytes of the output
     __shared__ int fresh[REACH_EPB];      // 1: the env's row in `rows` was recomputed (write it back to the cache)
     const int env0 = blockIdx.x * REACH_EPB;
     // observation overlap: the host splits a step only when its workgroups hold a multiple of 16 envs, so these 16 share a phase
@@ -33,9 +41,39 @@ __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const Reach
     const int l = threadIdx.x;
     const int el = l >> 2, env = env0 + el;
     constexpr int ROW = REACH_DIM + 1;
+    // minimal observation, the columns that do not come from the reachability row.  Their loads are issued here, ahead of the
+    // staging loop, by all lanes and WITHOUT a per-lane condition (indices clamped into the workgroup's rows instead), so that the
+    // wavefront waits for them together with the staging loads: a load under a lane condition makes the compiler wait for it at
+    // the end of its branch (DESIGN.md 14 has the measurements).  Mines (columns 20-35: features 0, 1, 2, 5 of the first four of
+    // the eight nearest, from the spatial_context row the step kernel wrote for this observation): 16 envs x 16 floats, four per
+    // lane.  Physics (0-11) and buffers (36-39): lane e < 16 reads env e's state planes -- SoA, so consecutive lanes read
+    // consecutive addresses (the other lanes re-read the last env's, and drop them).
+    // The five plane loads are not even under `if (min_out)`: with zeros on the other path the compiler moves the f64 -> f32
+    // conversions of the floor normal up behind the loads and waits for them there (the planes exist in every mode; a launch
+    // without min_out reads 36 bytes per env that it drops).
+    float mv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (min_out) {
+        const int last = n_here * 16 - 1;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int i = min(l + 64 * j, last), e = i >> 4, c = i & 15;
+            mv[j] = sc_rows[(size_t)(env0 + e) * 112 + 64 + 6 * (c >> 2) + ((c & 3) == 3 ? 5 : (c & 3))];
+        }
+    }
+    const size_t pN = (size_t)a.n, pe = (size_t)(env0 + min(l, n_here - 1));
+    const uint32_t pa = a.u32[U_A * pN + pe];
+    const double pv[4] = {a.f64[F_VX * pN + pe], a.f64[F_VY * pN + pe], a.f64[F_FNX * pN + pe], a.f64[F_FNY * pN + pe]};
     // ---- stage the cached rows (contiguous for the workgroup's envs)
     for (int i = l; i < n_here * ROW; i += 64) rows[i] = cache[(size_t)env0 * ROW + i];
     if (l < REACH_EPB) fresh[l] = 0;
+    if (min_out) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int i = l + 64 * j;
+            if (i < n_here * 16) mins[(i >> 4) * MINOBS_DIM + 20 + (i & 15)] = mv[j];
+        }
+        if (l < n_here) minobs_encode_state(pa, pv[0], pv[1], pv[2], pv[3], mins + l * MINOBS_DIM);
+    }
     __syncthreads();
     // switch_states (npp_switch_states_kernel's arithmetic, npp_render.hip) by the env's second lane, which has nothing else to do:
     // npp_reachability_ex saves the launch of that 8-us kernel
@@ -90,7 +128,7 @@ __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const Reach
             col = col < 0 ? 0 : (col > SDF_W - 1 ? SDF_W - 1 : col);
             row = row < 0 ? 0 : (row > SDF_H - 1 ? SDF_H - 1 : row);
             sd[0] = 1.f; sd[1] = 0.f; sd[2] = 0.f;
-            if (H.off_sdf) {
+            if (H.off_sdf && sdf_out) {   // (nobody reads it otherwise: npp_minimal_observation)
                 sd[0] = T.sdf()[row * SDF_W + col];
                 sd[1] = T.grad()[(row * SDF_W + col) * 2];
                 sd[2] = T.grad()[(row * SDF_W + col) * 2 + 1];
@@ -127,6 +165,13 @@ __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const Reach
         } else if (status) status[env0 + e] = (int)v;
     }
     if (sdf_out && l < n_here * 3) sdf_out[(size_t)env0 * 3 + l] = sdfs[l];
+    // minimal rows: the reachability columns from `rows` (final since the barrier above), the others from `mins`; all 64 lanes,
+    // consecutive floats of one contiguous block
+    if (min_out)
+        for (int i = l; i < n_here * MINOBS_DIM; i += 64) {
+            const int e = i / MINOBS_DIM, c = i - e * MINOBS_DIM;
+            min_out[(size_t)env0 * MINOBS_DIM + i] = (c >= 12 && c < 20) ? rows[e * ROW + (int)((MINOBS_REACH_COLS >> (8 * (c - 12))) & 0xffu)] : mins[i];
+        }
 }
 
 __global__ __launch_bounds__(256) void npp_reach_restore_kernel(KernelArgs a, const uint32_t *src_key, const float *src_cache,
@@ -151,9 +196,10 @@ hipError_t launch_reach_restore(const KernelArgs &a, const uint32_t *src_key, co
 }
 
 hipError_t launch_reach(const KernelArgs &a, const ReachHdr *rh, const unsigned char *rblob, uint32_t *key, float *cache,
-                        const ReachMissDev &md, float *out, float *sdf_out, int32_t *status, float *sw_out, hipStream_t s) {
+                        const ReachMissDev &md, float *out, float *sdf_out, int32_t *status, float *sw_out, float *min_out,
+                        const float *sc_rows, hipStream_t s) {
     hipLaunchKernelGGL(npp_reach_kernel, dim3((a.n + REACH_EPB - 1) / REACH_EPB), dim3(64), 0, s, a, rh, rblob, key, cache, md, out, sdf_out, status,
-                       sw_out);
+                       sw_out, min_out, sc_rows);
     return hipGetLastError();
 }
 

@@ -60,6 +60,7 @@ _FIELDS = {
     "reachability_features": ((38,), torch.float32),
     "mine_sdf_features": ((3,), torch.float32),
     "reach_status": ((), torch.int32),
+    "minimal_observation": ((40,), torch.float32),
 }
 # graph observations (NppBatch.graph_observation): shape per env and dtype; kept out of the packed output block, which numpy-mode
 # environments copy to the host every step
@@ -68,7 +69,7 @@ GRAPH_KEYS = {"graph_node_feats": ((2500, 6), torch.float32), "graph_edge_index"
 _ALWAYS = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags", "terminal_state")
 _PACKED = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags")
 _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_frame", "global_view", "reachability_features",
-             "mine_sdf_features", "reach_status")
+             "mine_sdf_features", "reach_status", "minimal_observation")
 
 
 def _device_tensor(ptr, numel, dtype, device):
@@ -124,17 +125,18 @@ class OutputBlock:
         return out
 
     def to_host(self, stream, names=None):
-        """One async copy of the block (up to the last requested field) into a pinned mirror on `stream`, one
+        """One async copy of the block (from the first to the last requested field) into a pinned mirror on `stream`, one
         synchronisation; returns {name: numpy view}.  Two mirrors alternate, so the arrays of the previous call stay valid
         until the call after this one (obs_t and obs_t+1 can be held together)."""
         names = self.names if names is None else [k for k in self.names if k in names]
+        start = min(self.offsets[k][0] for k in names)   # (fields start 256-byte aligned) nothing in front of the first one asked for
         end = max(self.offsets[k][0] + self.offsets[k][1] for k in names)
         if self._host[self._flip] is None:
             self._host[self._flip] = torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True)
         host = self._host[self._flip]
         self._flip ^= 1
         with torch.cuda.stream(stream):
-            host[:end].copy_(self.dev[:end], non_blocking=True)
+            host[start:end].copy_(self.dev[start:end], non_blocking=True)
         stream.synchronize()
         return {k: self._view(host, k).numpy() for k in names}
 
@@ -186,9 +188,15 @@ class NppBatch:
                                 ptr("frames"), ptr("terminal_state"), ptr("spatial_context"), ptr("positions"), ptr("work"))
         self._out_min = nat.StepOut(ptr("game_state"), ptr("action_mask"), ptr("entity_pos"), ptr("flags"), ptr("reward"),
                                     ptr("frames"), None, ptr("spatial_context"), ptr("positions"), ptr("work"))
+        if "minimal_observation" in t:
+            # the mode's switch: from now on every step / observe launch writes the mine rows the 40 floats are assembled from
+            # (into spatial_context when that output is enabled, else into a buffer of the handle).  Called again whenever the
+            # block is re-allocated: the handle forgets where the last launch wrote the rows (they may have been in the old block),
+            # so a minimal_observation() before the next step() / observe() is an error instead of a read of freed memory
+            nat.check(self.h, self.lib.npp_set_minimal_observation(self.h, 1))
 
     def enable_outputs(self, *names):
-        """Add optional outputs (spatial_context, positions, work, switch_states, player_frame, global_view, reachability_features, mine_sdf_features, reach_status); the output
+        """Add optional outputs (spatial_context, positions, work, switch_states, player_frame, global_view, reachability_features, mine_sdf_features, reach_status, minimal_observation); the output
         block is re-allocated, so tensors obtained earlier are stale."""
         new = [k for k in names if k not in self._enabled]
         for k in new:
@@ -406,6 +414,21 @@ class NppBatch:
             raise RuntimeError('enable_outputs("reachability_features") and / or "mine_sdf_features" first')
         sw = C.c_void_p(t["switch_states"].data_ptr()) if with_switch_states else None
         nat.check(self.h, self.lib.npp_reachability_ex(self.h, *ptr, sw))
+
+    def minimal_observation(self, out=None):
+        """float32 CUDA tensor [N, 40]: the reference's minimal observation (compute_minimal_observation) of the current state;
+        default: the block's minimal_observation field (outputs=("minimal_observation",) / enable_outputs).  It is this
+        observation's reachability call (same cache rule; fills reach_status when enabled) -- call it once per observation, after
+        step() / observe(), instead of or beside reachability()."""
+        t = self.out.t
+        if "minimal_observation" not in t:
+            raise RuntimeError('enable_outputs("minimal_observation") first: it switches the mode on for the step launches')
+        if out is None:
+            out = t["minimal_observation"]
+        assert out.dtype == torch.float32 and out.is_cuda and out.numel() == self.n * 40 and out.is_contiguous()
+        st = C.c_void_p(t["reach_status"].data_ptr()) if "reach_status" in t else None
+        nat.check(self.h, self.lib.npp_minimal_observation(self.h, C.c_void_p(out.data_ptr()), st))
+        return out
 
     def graph_observation(self, node_feats=None, edge_index=None, node_mask=None, edge_mask=None, rewrite_all=False):
         """The graph observations of every env (include/npp_amd.h npp_graph_observation): graph_node_feats f32 [N, 2500, 6],

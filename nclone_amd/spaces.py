@@ -63,11 +63,33 @@ def check_frame_stack(visual_stack_size=4, state_stack_size=4, padding_type="zer
         raise ValueError("padding_type must be 'zero' or 'repeat'")
 
 
+OBSERVATION_MODES = ("full", "minimal")   # gym_environment/config.py:17-20 ObservationMode
+
+
+def check_observation_mode(observation_mode, **options):
+    """The observation_mode argument of the host classes: "full" or "minimal" (anything else raises ValueError), and in minimal
+    mode every option that is switched on although it has nothing to act on there -- `options` maps the constructor's names
+    (enable_visual_observations, enable_state_stacking, ...) to their values -- raises ValueError naming the conflict.  Needs no
+    device.  Returns True for minimal mode."""
+    if observation_mode not in OBSERVATION_MODES:
+        raise ValueError("observation_mode must be 'full' or 'minimal', not %r" % (observation_mode,))
+    if observation_mode == "full":
+        return False
+    on = [k for k, v in options.items() if v]
+    if on:
+        raise ValueError("observation_mode='minimal' conflicts with %s: the minimal observation is minimal_observation (40 floats) and "
+                         "action_mask only, so that option has nothing to act on" % ", ".join(on))
+    return True
+
+
 def observation_space(visual=False, spatial_context=False, switch_states=False, reachability=False, visual_stack=0, state_stack=0,
-                      graph=False):
-    """visual_stack / state_stack: K > 0 stacks player_frame to (K, 84, 84, 1) / game_state to (K, 41) with the bounds of the
+                      graph=False, minimal=False):
+    """minimal: the reference's two-key Dict of its MINIMAL observation mode (npp_environment.py:211-231), whatever the other
+    arguments say.  visual_stack / state_stack: K > 0 stacks player_frame to (K, 84, 84, 1) / game_state to (K, 41) with the bounds of the
     reference's stacked space (frame_stack_wrapper.py:139-181); global_view and the other keys pass through.  graph: the four
     graph observation keys (npp_environment.py:245-271)."""
+    if minimal:
+        return Dict({"minimal_observation": Box(-1.0, 1.0, (40,), np.float32), "action_mask": Box(0, 1, (6,), np.int8)})
     spaces = {
         "game_state": Box(-1.0, 1.0, (state_stack, 41) if state_stack else (41,), np.float32),
         "action_mask": Box(0, 1, (6,), np.int8),

@@ -99,6 +99,20 @@ class NppVecEnvironment:
     output="torch": persistent device tensors updated in place (the same lifetime as the other keys).  output="numpy": two host
     buffer sets alternate, filled from host copies of the per-level tables (no per-step device-to-host copy of these 162.5 KB per
     env), so the previous step's arrays stay valid.  Not part of the terminal info.  Off by default.
+
+    Minimal observation mode (the reference's EnvironmentConfig.observation_mode = MINIMAL, config.py:17-20):
+    observation_mode="minimal" makes `obs` the reference's small observation (npp_environment.py:2232-2270): minimal_observation
+    [N, 40] f32 (compute_minimal_observation, observation_processor.py:505-567: 12 physics, 8 path guidance, 4 mines x 4, 4
+    buffers), action_mask [N, 6] i8 and the pass-through scalars player_x / player_y, player_won, player_dead, death_cause (the
+    code of info["death_cause_code"]), switch_activated, switch_x / switch_y, exit_door_x / exit_door_y -- of the state the
+    observation shows, so an env that was auto-reset reports its spawn state (not won, not dead); the reward subsystem's
+    `_cached_*_distance` keys are left out.  game_state, entity_positions and the 112 / 38 / 3 / 25-float keys are not in `obs`
+    and (output="numpy") not copied to the host; the 38 / 3 / 25-float outputs are not allocated.  observation_space is the
+    reference's two-key Dict.  reward, terminated, truncated and info keep their meaning (info["terminal_observation"] stays the
+    terminal game_state: there is NO terminal minimal observation, the reference defines none).  Options with nothing to act on
+    in this mode (visual observations, either frame stacking, graph observations, enable_spatial_context / enable_reachability /
+    enable_switch_states) raise ValueError, as does any other mode string; levels npp_reachability refuses (several exit switches)
+    are refused at the first reset().  "full" (default): everything above, unchanged.
     """
 
     metadata = {"render_modes": []}
@@ -107,8 +121,14 @@ class NppVecEnvironment:
                  truncation_limit="dynamic", output="torch", autoreset=True, enable_spatial_context=False,
                  enable_switch_states=False, fast_reset=True, stream=None, enable_reachability=False, obs_overlap=0,
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
-                 frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False):
+                 frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
+                 observation_mode="full"):
         assert output in ("torch", "numpy")
+        self._minimal = spaces.check_observation_mode(
+            observation_mode, enable_visual_observations=enable_visual_observations,
+            enable_visual_frame_stacking=enable_visual_frame_stacking, enable_state_stacking=enable_state_stacking,
+            enable_graph_observations=enable_graph_observations, enable_spatial_context=enable_spatial_context,
+            enable_reachability=enable_reachability, enable_switch_states=enable_switch_states)
         spaces.check_frame_stack(visual_stack_size, state_stack_size, frame_stack_padding_type)
         self.num_envs = int(num_envs)
         self.frame_skip = int(frame_skip)
@@ -123,10 +143,12 @@ class NppVecEnvironment:
                                                                  switch_states=bool(enable_switch_states),
                                                                  reachability=bool(enable_reachability),
                                                                  visual_stack=self._vk, state_stack=self._sk,
-                                                                 graph=bool(enable_graph_observations))
+                                                                 graph=bool(enable_graph_observations), minimal=self._minimal)
         self.action_space = self.single_action_space
         self.observation_space = self.single_observation_space
         outputs = ["positions"]
+        if self._minimal:
+            outputs.append("minimal_observation")
         if enable_spatial_context:
             outputs.append("spatial_context")
         if enable_switch_states:
@@ -165,6 +187,8 @@ class NppVecEnvironment:
             self._actions = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
         self._reset_bits = 11 if autoreset else 0
         self._obs_names = ["game_state", "action_mask", "entity_pos", "positions", "flags"] + outputs[1:]
+        if self._minimal:   # (the packed block keeps game_state and entity_pos in front; they are neither returned nor copied)
+            self._obs_names = ["action_mask", "positions", "flags", "minimal_observation"]
         self._term_stack = None
         if self._vk or self._sk:
             self._b.set_frame_stack(self._vk, self._sk, frame_stack_padding_type)
@@ -192,6 +216,8 @@ class NppVecEnvironment:
             b.render_global_view()
         if "reachability_features" in b.out.t:
             b.reachability(with_switch_states=fused)
+        if self._minimal:
+            b.minimal_observation()
         b.join()   # (obs_overlap) the handle's stream waits for the kernels that went to the second stream
         if self._graph is not None and self.output == "torch":
             self._graph = b.graph_observation()
@@ -229,6 +255,17 @@ class NppVecEnvironment:
     def _obs(self, src):
         """src: {name: tensor-or-array} (device tensors, or the host views of ONE staged copy)."""
         pos = src["positions"]
+        if self._minimal:   # npp_environment.py:2232-2270; scalars of the state the observation shows (spawn state after an auto-reset)
+            live = (src["flags"] & self._reset_bits) == 0
+            return {
+                "minimal_observation": src["minimal_observation"],
+                "action_mask": src["action_mask"],
+                "player_x": pos[:, 0], "player_y": pos[:, 1],
+                "player_won": ((src["flags"] & 1) != 0) & live, "player_dead": ((src["flags"] & 2) != 0) & live,
+                "death_cause": ((src["flags"] >> 4) & 3) * live,
+                "switch_activated": ((src["flags"] & 4) != 0) & live,
+                "switch_x": pos[:, 2], "switch_y": pos[:, 3], "exit_door_x": pos[:, 4], "exit_door_y": pos[:, 5],
+            }
         obs = {
             "game_state": src["game_state"],
             "action_mask": src["action_mask"],
@@ -433,12 +470,18 @@ class NppEnvironment:
     """Single-environment adapter with the reference's exact call signatures (base_environment.py:483,
     npp_environment.py:504).  One GPU lane group does the work of one Python simulator; use NppVecEnvironment for
     throughput.  Frame stacking takes NppVecEnvironment's arguments; stacked keys come without the batch dimension
-    (player_frame (K, 84, 84, 1), game_state (K, 41))."""
+    (player_frame (K, 84, 84, 1), game_state (K, 41)).  observation_mode="minimal": NppVecEnvironment's minimal mode
+    (minimal_observation (40,), action_mask (6,) and the pass-through scalars; no terminal minimal observation)."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
-                 state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False):
+                 state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full"):
+        spaces.check_observation_mode(
+            observation_mode, enable_visual_observations=enable_visual_observations,
+            enable_visual_frame_stacking=enable_visual_frame_stacking, enable_state_stacking=enable_state_stacking,
+            enable_graph_observations=enable_graph_observations, enable_spatial_context=enable_spatial_context,
+            enable_reachability=enable_reachability, enable_switch_states=enable_switch_states)
         if map_data is None:
             if custom_map_path is None:
                 raise ValueError("NppEnvironment needs map_data or custom_map_path")
@@ -452,7 +495,7 @@ class NppEnvironment:
                                     enable_visual_frame_stacking=enable_visual_frame_stacking, visual_stack_size=visual_stack_size,
                                     enable_state_stacking=enable_state_stacking, state_stack_size=state_stack_size,
                                     frame_stack_padding_type=frame_stack_padding_type,
-                                    enable_graph_observations=enable_graph_observations)
+                                    enable_graph_observations=enable_graph_observations, observation_mode=observation_mode)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -462,7 +505,11 @@ class NppEnvironment:
         out = {k: v[0].copy() if isinstance(v[0], np.ndarray) else v[0] for k, v in obs.items()}
         for k in ("player_x", "player_y", "switch_x", "switch_y", "exit_door_x", "exit_door_y"):
             out[k] = float(out[k])
-        out["switch_activated"] = bool(out["switch_activated"])
+        for k in ("switch_activated", "player_won", "player_dead"):   # (the last two: minimal mode)
+            if k in out:
+                out[k] = bool(out[k])
+        if "death_cause" in out:
+            out["death_cause"] = int(out["death_cause"])
         return out
 
     def reset(self, seed=None, options=None):
