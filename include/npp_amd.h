@@ -427,6 +427,45 @@ int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed,
 int npp_graph_observation(npp_handle h, float *d_node_feats, uint16_t *d_edge_index, uint8_t *d_node_mask, uint8_t *d_edge_mask, int flags);
 int npp_graph_compile(const double *map, int64_t n, float *feats, uint16_t *edge_index, int32_t *counts);
 
+/* Frame augmentation of player_frame and global_view: what the reference's FrameStackWrapper.observation does to both keys at every
+ * observation when AugmentationConfig.enable_augmentation is set, its default (gym_environment/config.py:64-87;
+ * frame_stack_wrapper.py:343-377, 402-462 -> frame_augmentation.apply_augmentation; a stacked player_frame gets ONE transform for all
+ * its frames, _apply_consistent_augmentation).  The four transforms, their order and their gates are the reference's pipeline
+ * (frame_augmentation.py:56-103): translate (gate 0.8 p), horizontal flip (0.4 p), coarse dropout (0.5 p), brightness / contrast
+ * (0.4 p).  PARITY WITH ALBUMENTATIONS' PIXELS IS UNPINNED, and the draws are a counter-based hash, not numpy's stream: what is pinned
+ * is the integer definition of DESIGN.md 15 (nclone_amd/csrc/npp_augment.hpp; numpy model tests/frame_aug_ref.py), bit for bit.
+ * One parameter set is AugParams, 14 int32 words: gate mask (bit 0 translate, 1 flip, 2 dropout, 3 brightness / contrast), sx, sy
+ * (shift in 1/32 px), hole count, two holes of (h, w, y0, x0), a, b (v <- clamp((a v + b) >> 8, 0, 255)).
+ * npp_set_frame_augmentation(h, enable, p, scale, seed): enable != 0 allocates (or keeps) the two destination buffers -- u8
+ *   [n_envs][max(K, 1)][84][84] for player_frame, K the visual stack size of npp_set_frame_stack, and u8 [n_envs][176][100] for
+ *   global_view -- and sets the augmentation call count to 0; enable == 0 frees them (the default: nothing allocated, nothing
+ *   launched).  p outside [0, 1], a scale other than 0.7 (light), 1.0 (medium) or 1.3 (strong), or a handle without visual outputs --
+ *   no player_frame rendered or stacked, or no global_view rendered yet -- return NPP_ERR_INVALID.  Synchronises the handle's stream.
+ *   Call it again after npp_set_frame_stack changed K.
+ * npp_frame_augment(h, host_params): one augmentation call for every env, on the handle's stream.  It reads player_frame from the
+ *   frame ring's current window when the handle stacks it, else from where npp_render_player_frame last wrote, and global_view from
+ *   where npp_render_global_view last wrote (both must still be allocated, 16-byte aligned), and never writes them: the ring keeps
+ *   clean frames, which come back in later stacks under other draws.  Call it after npp_join and after npp_frame_stack_push (the
+ *   padding of reset envs must be in the ring).  host_params == NULL: env e draws its parameters for target t (0 player_frame, 1
+ *   global_view) from (seed, e, call count c, t):
+ *     base = mix(mix(((uint64_t)e << 32) | c) ^ seed ^ (t * 0xD1B54A32D192ED03)), word j = mix(base + j)     (mix: npp_set_level_pool)
+ *     words: 0 translate gate, 1 sx, 2 sy, 3 flip gate, 4 dropout gate, 5 hole count, 6-9 / 10-13 holes, 14 b/c gate, 15 a, 16 b;
+ *     a gate passes when (word >> 11) * 2^-53 < probability; an integer in [lo, hi] is lo + (((word >> 32) * (hi - lo + 1)) >> 32)
+ *   otherwise host_params is int32 [n_envs][2][14], AugParams per env and target, used in place of the draw (rejected with
+ *   NPP_ERR_INVALID when a hole leaves the image or a value leaves the arithmetic's range).  Either way the call count advances by
+ *   one; npp_snapshot / npp_restore leave it alone (observation noise, not simulation state).
+ * npp_frame_augment_view(h, which, base, bytes): which 0 = the player_frame destination, 1 = global_view's; valid until the next
+ *   npp_set_frame_augmentation, rewritten by the next npp_frame_augment.  NPP_ERR_STATE while the feature is off.
+ * npp_frame_augment_params_host (host-only): the draw for `count` (env, call count, target) triples, out int32 [count][14].
+ * npp_frame_augment_apply_host (host-only): the per-pixel function the kernel compiles on `count` frames u8 [count][height][width]
+ *   with params int32 [count][14]. */
+int npp_set_frame_augmentation(npp_handle h, int enable, double p, double scale, uint64_t seed);
+int npp_frame_augment(npp_handle h, const int32_t *host_params);
+int npp_frame_augment_view(npp_handle h, int which, void **base, int64_t *bytes);
+int npp_frame_augment_params_host(uint64_t seed, double p, double scale, const int32_t *envs, const uint32_t *counts, const int32_t *targets,
+                                  int count, int32_t *out);
+int npp_frame_augment_apply_host(const uint8_t *frames, int count, int height, int width, const int32_t *params, uint8_t *out);
+
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);
 

@@ -35,6 +35,8 @@ EXPORTS = [
     "npp_set_level_pool", "npp_draw_levels", "npp_get_env_levels", "npp_env_level_view", "npp_level_pool_draw_host",
     "npp_graph_observation", "npp_graph_compile",
     "npp_set_minimal_observation", "npp_minimal_observation", "npp_minimal_encode_host",
+    "npp_set_frame_augmentation", "npp_frame_augment", "npp_frame_augment_view", "npp_frame_augment_params_host",
+    "npp_frame_augment_apply_host",
 ]
 
 
@@ -139,6 +141,11 @@ def lib():
     L.npp_set_minimal_observation.argtypes = [H, C.c_int]
     L.npp_minimal_observation.argtypes = [H, C.c_void_p, C.c_void_p]
     L.npp_minimal_encode_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_set_frame_augmentation.argtypes = [H, C.c_int, C.c_double, C.c_double, C.c_uint64]
+    L.npp_frame_augment.argtypes = [H, C.c_void_p]
+    L.npp_frame_augment_view.argtypes = [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.npp_frame_augment_params_host.argtypes = [C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_frame_augment_apply_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

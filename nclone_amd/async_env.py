@@ -83,12 +83,17 @@ class NppAsyncVecEnvironment:
 
     No frame stacking here (NppVecEnvironment has it): observations are single entries.  No graph observations either
     (NppVecEnvironment(enable_graph_observations=True) has them), and no minimal observation mode: observation_mode other than
-    "full" is refused (NppVecEnvironment(observation_mode="minimal") has it).
+    "full" is refused (NppVecEnvironment(observation_mode="minimal") has it).  No frame augmentation (there are no visual
+    observations here): enable_augmentation is refused likewise (NppVecEnvironment(enable_augmentation=True) has it).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
-                 output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full"):
+                 output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
+                 enable_augmentation=False):
         assert output in ("torch", "numpy")
+        if enable_augmentation:
+            raise NotImplementedError("NppAsyncVecEnvironment has no frame augmentation (it has no visual observations): "
+                                      "NppVecEnvironment(enable_augmentation=True) has it")
         if observation_mode != "full":
             raise NotImplementedError("NppAsyncVecEnvironment has no observation_mode other than 'full' (%r asked for): "
                                       "NppVecEnvironment(observation_mode='minimal') has the minimal observation" % (observation_mode,))

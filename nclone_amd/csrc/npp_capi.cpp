@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/npp_amd.h"
+#include "npp_augment.hpp"
 #include "npp_graph.hpp"
 #include "npp_host.hpp"
 #include "npp_internal.hpp"
@@ -222,6 +223,20 @@ struct Minimal {
     const float *rows = nullptr; // where the last step / observe launch wrote the rows (the caller's buffer or `sc`)
 };
 
+// frame augmentation (npp_set_frame_augmentation / npp_frame_augment, npp_augment.hip): augmented copies of the player_frame
+// window and of global_view in buffers of the handle; the sources are where the render entries last wrote
+struct FrameAug {
+    bool on = false;
+    double p = 0.0;
+    int s10 = 10;                // intensity scale * 10
+    uint64_t seed = 0;
+    uint32_t count = 0;          // augmentation calls since npp_set_frame_augmentation (observation noise: not in the snapshot)
+    int k = 1;                   // player_frame entries per env of `pf` (the visual stack size it was allocated for, or 1)
+    DevBuf<uint8_t> pf, gv;      // [n][k][84 * 84], [n][176 * 100]
+    DevBuf<int32_t> params;      // [n][2][AUG_WORDS] a caller's parameters, allocated by the first call that brings some
+    const uint8_t *pf_out = nullptr, *gv_out = nullptr;   // d_out of the last npp_render_player_frame / npp_render_global_view
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -253,6 +268,7 @@ struct npp_handle_s {
     FrameStack fs;
     Pool pool;
     Minimal mini;
+    FrameAug aug;
 };
 
 
@@ -1445,6 +1461,7 @@ extern "C" {
 
 int npp_render_player_frame(npp_handle h, uint8_t *d_out) {
     if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_render_player_frame: bad arguments");
+    h->aug.pf_out = d_out;   // (frame augmentation reads the unstacked frame there)
     return render_player_frame(h, d_out, 84 * 84, 0);
 }
 
@@ -1515,6 +1532,88 @@ int npp_frame_stack_view(npp_handle h, int which, void **base, int64_t *offset, 
     *base = which == 0 ? (void *)h->fs.frames.get() : (void *)h->fs.state.get();
     *offset = (int64_t)(head + 1) * E;
     *batch_stride = (int64_t)2 * K * E;
+    return NPP_OK;
+}
+
+int npp_set_frame_augmentation(npp_handle h, int enable, double p, double scale, uint64_t seed) {
+    if (!h) return NPP_ERR_INVALID;
+    FrameAug &A = h->aug;
+    if (!enable) {
+        if (!A.on && !A.pf) return NPP_OK;
+        ON_DEVICE_JOINED(h);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // the buffers may still be written by a queued call
+        A.on = false;
+        A.pf.reset(); A.gv.reset(); A.params.reset();
+        return NPP_OK;
+    }
+    if (!(p >= 0.0 && p <= 1.0)) return fail(h, NPP_ERR_INVALID, "npp_set_frame_augmentation: p must be between 0.0 and 1.0");
+    const int s10 = scale == 0.7 ? 7 : scale == 1.0 ? 10 : scale == 1.3 ? 13 : 0;
+    if (!s10) return fail(h, NPP_ERR_INVALID, "npp_set_frame_augmentation: scale must be 0.7 (light), 1.0 (medium) or 1.3 (strong)");
+    if (!(h->fs.vk || A.pf_out) || !A.gv_out)
+        return fail(h, NPP_ERR_INVALID, "npp_set_frame_augmentation: the handle has no visual outputs (render player_frame, or stack it, "
+                                        "and global_view first)");
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n;
+    const int k = h->fs.vk ? h->fs.vk : 1;
+    A.on = false;
+    if (A.pf.size() != N * k * NPP_FRAME_H * NPP_FRAME_W) HIP_TRY(h, A.pf.alloc(N * k * NPP_FRAME_H * NPP_FRAME_W));
+    if (!A.gv) HIP_TRY(h, A.gv.alloc(N * AUG_GV_H * AUG_GV_W));
+    HIP_TRY(h, hipMemsetAsync(A.pf.get(), 0, A.pf.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(A.gv.get(), 0, A.gv.bytes(), h->stream));
+    A.k = k; A.p = p; A.s10 = s10; A.seed = seed; A.count = 0;
+    A.on = true;
+    return NPP_OK;
+}
+
+int npp_frame_augment(npp_handle h, const int32_t *host_params) {
+    if (!h) return NPP_ERR_INVALID;
+    FrameAug &A = h->aug;
+    if (!A.on) return fail(h, NPP_ERR_STATE, "npp_frame_augment: frame augmentation is off (npp_set_frame_augmentation)");
+    if (A.k != (h->fs.vk ? h->fs.vk : 1))
+        return fail(h, NPP_ERR_STATE, "npp_frame_augment: the visual stack changed since npp_set_frame_augmentation (call it again)");
+    const uint8_t *pf_src = h->fs.vk ? h->fs.frames.get() + (size_t)(h->fs.vhead + 1) * NPP_FRAME_H * NPP_FRAME_W : A.pf_out;
+    if (!pf_src || !A.gv_out) return fail(h, NPP_ERR_STATE, "npp_frame_augment: nothing was rendered since the outputs changed");
+    if (((uintptr_t)pf_src | (uintptr_t)A.gv_out) & 15)
+        return fail(h, NPP_ERR_INVALID, "npp_frame_augment: the rendered player_frame / global_view buffers must be 16-byte aligned");
+    const size_t N = (size_t)h->n;
+    if (host_params) {
+        const AugParams *P = reinterpret_cast<const AugParams *>(host_params);
+        for (size_t i = 0; i < 2 * N; i++)
+            if (!aug_params_ok(P[i], (i & 1) ? AUG_GV_H : AUG_PF_H, (i & 1) ? AUG_GV_W : AUG_PF_W))
+                return fail(h, NPP_ERR_INVALID, "npp_frame_augment: parameters of env " + std::to_string(i / 2) + ", target " +
+                                                    std::to_string(i & 1) + " are outside the image or the arithmetic's range");
+    }
+    ON_DEVICE_JOINED(h);
+    if (host_params) {
+        if (!A.params) HIP_TRY(h, A.params.alloc(2 * N * AUG_WORDS));
+        HIP_TRY(h, hipMemcpyAsync(A.params.get(), host_params, A.params.bytes(), hipMemcpyHostToDevice, h->stream));
+    }
+    AugArgs a;
+    a.n = h->n;
+    a.k = A.k;
+    a.pf_src = pf_src;
+    a.pf_stride = (size_t)(h->fs.vk ? 2 * h->fs.vk : 1) * NPP_FRAME_H * NPP_FRAME_W;
+    a.gv_src = A.gv_out;
+    a.pf_dst = A.pf.get();
+    a.gv_dst = A.gv.get();
+    a.params = host_params ? A.params.get() : nullptr;
+    a.seed = A.seed;
+    a.count = A.count;
+    a.p = A.p;
+    a.s10 = A.s10;
+    HIP_TRY(h, launch_frame_augment(a, h->stream));
+    A.count++;
+    if (host_params) HIP_TRY(h, hipStreamSynchronize(h->stream));   // host_params is caller memory: finish the copy
+    return NPP_OK;
+}
+
+int npp_frame_augment_view(npp_handle h, int which, void **base, int64_t *bytes) {
+    if (!h || (which != 0 && which != 1) || !base || !bytes) return fail(h, NPP_ERR_INVALID, "npp_frame_augment_view: bad arguments");
+    if (!h->aug.on) return fail(h, NPP_ERR_STATE, "npp_frame_augment_view: frame augmentation is off (npp_set_frame_augmentation)");
+    const DevBuf<uint8_t> &b = which == 0 ? h->aug.pf : h->aug.gv;
+    *base = (void *)b.get();
+    *bytes = (int64_t)b.bytes();
     return NPP_OK;
 }
 
@@ -1643,6 +1742,7 @@ int npp_render_frame(npp_handle h, int env0, int count, uint8_t *d_out) {
 int npp_render_global_view(npp_handle h, uint8_t *d_out) {
     if (!h || !d_out) return fail(h, NPP_ERR_INVALID, "npp_render_global_view: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_render_global_view: no levels loaded");
+    h->aug.gv_out = d_out;   // (frame augmentation reads global_view there)
     ON_DEVICE(h);
     const bool tables = !h->ls.gv.h || !h->ls.canvas;
     if (int rc = ensure_gv(h)) return rc;

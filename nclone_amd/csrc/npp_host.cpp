@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../../include/npp_amd.h"
+#include "npp_augment.hpp"
 #include "npp_minimal.hpp"
 #include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
@@ -43,6 +44,35 @@ int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed,
     std::string err;
     if (!pool_cdf(weights, n_levels, n_levels, cdf, last, err)) return fail(nullptr, NPP_ERR_INVALID, err);
     for (int i = 0; i < count; i++) out[i] = pool_pick(cdf.data(), n_levels, last, seed, (uint32_t)envs[i], counts[i]);
+    return NPP_OK;
+}
+
+int npp_frame_augment_params_host(uint64_t seed, double p, double scale, const int32_t *envs, const uint32_t *counts, const int32_t *targets,
+                                  int count, int32_t *out) {
+    if (count < 0 || (count > 0 && (!envs || !counts || !targets || !out)))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_frame_augment_params_host: bad arguments");
+    if (!(p >= 0.0 && p <= 1.0)) return fail(nullptr, NPP_ERR_INVALID, "npp_frame_augment_params_host: p must be between 0.0 and 1.0");
+    const int s10 = scale == 0.7 ? 7 : scale == 1.0 ? 10 : scale == 1.3 ? 13 : 0;
+    if (!s10) return fail(nullptr, NPP_ERR_INVALID, "npp_frame_augment_params_host: scale must be 0.7 (light), 1.0 (medium) or 1.3 (strong)");
+    for (int i = 0; i < count; i++) {
+        if (targets[i] != 0 && targets[i] != 1) return fail(nullptr, NPP_ERR_INVALID, "npp_frame_augment_params_host: target must be 0 or 1");
+        const AugParams P = aug_draw(seed, (uint32_t)envs[i], counts[i], targets[i], p, s10);
+        std::memcpy(out + (size_t)i * AUG_WORDS, &P, sizeof(P));
+    }
+    return NPP_OK;
+}
+
+int npp_frame_augment_apply_host(const uint8_t *frames, int count, int height, int width, const int32_t *params, uint8_t *out) {
+    if (count < 0 || height <= 0 || width <= 0 || height > 1024 || width > 1024 || (count > 0 && (!frames || !params || !out)))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_frame_augment_apply_host: bad arguments");
+    const size_t E = (size_t)height * width;
+    for (int i = 0; i < count; i++) {
+        AugParams P;
+        std::memcpy(&P, params + (size_t)i * AUG_WORDS, sizeof(P));
+        if (!aug_params_ok(P, height, width)) return fail(nullptr, NPP_ERR_INVALID, "npp_frame_augment_apply_host: parameters outside the image");
+        for (int y = 0; y < height; y++)
+            for (int x = 0; x < width; x++) out[i * E + (size_t)y * width + x] = aug_pixel(frames + i * E, height, width, P, y, x);
+    }
     return NPP_OK;
 }
 

@@ -195,6 +195,20 @@ hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s);
 // envs selected by mask (null = all): level, draw count and truncation limit <- the snapshot's
 hipError_t launch_pool_restore(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count, const int32_t *s_trunc,
                                int32_t *level, uint32_t *count, int32_t *trunc, hipStream_t s);
+// npp_augment.hip: one augmentation call (see npp_frame_augment in include/npp_amd.h; the draw and the pixels: npp_augment.hpp)
+struct AugArgs {
+    int n, k;                     // k: player_frame entries per env (the visual stack size, or 1)
+    const uint8_t *pf_src;        // env e's k entries are contiguous from pf_src + e * pf_stride (frame ring window / output block)
+    size_t pf_stride;
+    const uint8_t *gv_src;        // [n][176 * 100]
+    uint8_t *pf_dst, *gv_dst;     // [n][k][84 * 84], [n][176 * 100]
+    const int32_t *params;        // [n][2][AUG_WORDS] used in place of the draw; null = draw
+    uint64_t seed;
+    uint32_t count;               // the handle's augmentation call count
+    double p;
+    int s10;                      // intensity scale * 10
+};
+hipError_t launch_frame_augment(const AugArgs &a, hipStream_t s);
 // npp_graph.hip: graph observation rows (see npp_graph_observation in include/npp_amd.h; tables: npp_graph.hpp)
 struct GraphHdr;
 struct GraphArgs {

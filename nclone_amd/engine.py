@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .spaces import check_frame_augmentation
 
 
 class _DeviceStream:
@@ -70,6 +71,10 @@ _ALWAYS = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags
 _PACKED = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags")
 _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_frame", "global_view", "reachability_features",
              "mine_sdf_features", "reach_status", "minimal_observation")
+
+
+AUG_SCALES = {"light": 0.7, "medium": 1.0, "strong": 1.3}   # frame_augmentation.py:57
+AUG_WORDS = 14   # int32 words of one AugParams (npp_augment.hpp)
 
 
 def _device_tensor(ptr, numel, dtype, device):
@@ -497,6 +502,9 @@ class NppBatch:
         nat.check(self.h, self.lib.npp_set_frame_stack(self.h, int(visual_k), int(state_k), 1 if padding == "repeat" else 0))
         self.stack_k = (int(visual_k), int(state_k))
         self._stack_ring = [None, None]
+        if getattr(self, "_aug", None) is not None:   # the augmented player_frame buffer is sized by visual_k: allocated again
+            self._aug[3] = False
+            self._aug_views = None
 
     def render_player_frame_stacked(self):
         """player_frame of every env into the frame ring (the entry the next frame_stack_push completes)."""
@@ -536,6 +544,54 @@ class NppBatch:
             out.append(torch.as_strided(ring[1], (self.n, k) + shape, (stride.value, e) + tuple(
                 int(np.prod(shape[i + 1:])) for i in range(len(shape))), off.value))
         return tuple(out)
+
+    # ---- frame augmentation (include/npp_amd.h npp_set_frame_augmentation; the reference's apply_augmentation) ------
+    def set_frame_augmentation(self, enable=True, p=0.5, intensity="medium", seed=0):
+        """Augment player_frame and global_view on the device (translate, flip, coarse dropout, brightness / contrast with the
+        reference's gates; the project's own integer definition, DESIGN.md 15 -- parity with albumentations' pixels is unpinned).
+        p and intensity are checked here with the reference's messages; the native switch is thrown by the next
+        frame_augment(), after the frames it reads have been rendered (and after set_frame_stack), and restarts the call count
+        at 0.  enable=False frees the buffers at once."""
+        if not enable:
+            self._aug = None
+            nat.check(self.h, self.lib.npp_set_frame_augmentation(self.h, 0, 0.0, 1.0, 0))
+            return
+        check_frame_augmentation(p, intensity)
+        self._aug = [float(p), AUG_SCALES[intensity], int(seed) & (2**64 - 1), False]   # last: the native switch was thrown
+        self._aug_views = None
+
+    def frame_augment(self, params=None):
+        """One augmentation call: every env draws its parameters (params=None), or takes them from params, int32
+        [N, 2, 14] (AugParams per env for player_frame and global_view; how tests reach corner parameters).  Call after join()
+        and frame_stack_push().  The results are frame_augment_views()."""
+        cfg = getattr(self, "_aug", None)
+        if cfg is None:
+            raise RuntimeError("set_frame_augmentation() first")
+        if not cfg[3]:
+            nat.check(self.h, self.lib.npp_set_frame_augmentation(self.h, 1, cfg[0], cfg[1], cfg[2]))
+            cfg[3] = True
+        ptr = None
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.int32)
+            assert params.shape == (self.n, 2, AUG_WORDS)
+            ptr = params.ctypes.data_as(C.c_void_p)
+        code = self.lib.npp_frame_augment(self.h, ptr)
+        if code == nat.NPP_ERR_INVALID:
+            raise ValueError(self.lib.npp_last_error(self.h).decode())
+        nat.check(self.h, code)
+
+    def frame_augment_views(self):
+        """(player_frame [N, max(K, 1), 84, 84, 1] u8, global_view [N, 176, 100, 1] u8): CUDA tensors over the handle's
+        augmented buffers (no copy), rewritten by the next frame_augment()."""
+        if getattr(self, "_aug_views", None) is None:
+            out = []
+            for which, shape in enumerate(((84, 84, 1), (176, 100, 1))):
+                base, nbytes = C.c_void_p(), C.c_int64()
+                nat.check(self.h, self.lib.npp_frame_augment_view(self.h, which, C.byref(base), C.byref(nbytes)))
+                t = _device_tensor(base.value, nbytes.value, torch.uint8, self.device)
+                out.append(t.view((self.n, -1) + shape) if which == 0 else t.view((self.n,) + shape))
+            self._aug_views = tuple(out)
+        return self._aug_views
 
     def to_host(self, names=None):
         """{name: numpy array} of the enabled outputs through ONE async device-to-host copy of the output block into pinned
@@ -638,6 +694,37 @@ def level_pool_draw(weights, seed, envs, counts):
     code = L.npp_level_pool_draw_host(w.ctypes.data_as(C.POINTER(C.c_double)), len(w), int(seed) & (2**64 - 1),
                                       e.ctypes.data_as(C.POINTER(C.c_int32)), c.ctypes.data_as(C.POINTER(C.c_uint32)), len(e),
                                       out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if code == nat.NPP_ERR_INVALID:
+        raise ValueError(L.npp_last_error(None).decode())
+    nat.check(None, code)
+    return out
+
+
+def frame_augment_params(seed, envs, counts, targets, p=0.5, intensity="medium"):
+    """Host-only: the AugParams, int32 [len(envs), 14], env envs[i] draws at augmentation call counts[i] for target targets[i]
+    (0 player_frame, 1 global_view): the draw the device kernel compiles (npp_augment.hpp)."""
+    L = nat.lib()
+    check_frame_augmentation(p, intensity)
+    e = np.ascontiguousarray(envs, dtype=np.int32).ravel()
+    c = np.ascontiguousarray(counts, dtype=np.uint32).ravel()
+    t = np.ascontiguousarray(targets, dtype=np.int32).ravel()
+    assert len(e) == len(c) == len(t)
+    out = np.zeros((len(e), AUG_WORDS), dtype=np.int32)
+    nat.check(None, L.npp_frame_augment_params_host(int(seed) & (2**64 - 1), float(p), AUG_SCALES[intensity], e.ctypes.data_as(C.c_void_p),
+                                                    c.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), len(e),
+                                                    out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def frame_augment_apply(frames, params):
+    """Host-only: the per-pixel function the device kernel compiles, on frames u8 [n, H, W] with params int32 [n, 14]."""
+    L = nat.lib()
+    f = np.ascontiguousarray(frames, dtype=np.uint8)
+    q = np.ascontiguousarray(params, dtype=np.int32)
+    assert f.ndim == 3 and q.shape == (f.shape[0], AUG_WORDS)
+    out = np.zeros_like(f)
+    code = L.npp_frame_augment_apply_host(f.ctypes.data_as(C.c_void_p), f.shape[0], f.shape[1], f.shape[2], q.ctypes.data_as(C.c_void_p),
+                                          out.ctypes.data_as(C.c_void_p))
     if code == nat.NPP_ERR_INVALID:
         raise ValueError(L.npp_last_error(None).decode())
     nat.check(None, code)

@@ -63,6 +63,14 @@ def check_frame_stack(visual_stack_size=4, state_stack_size=4, padding_type="zer
         raise ValueError("padding_type must be 'zero' or 'repeat'")
 
 
+def check_frame_augmentation(p=0.5, intensity="medium"):
+    """The reference's argument checks, messages included (AugmentationConfig.__post_init__, config.py:82-87)."""
+    if intensity not in ["light", "medium", "strong"]:
+        raise ValueError("intensity must be one of ['light', 'medium', 'strong']")
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("p must be between 0.0 and 1.0")
+
+
 OBSERVATION_MODES = ("full", "minimal")   # gym_environment/config.py:17-20 ObservationMode
 
 

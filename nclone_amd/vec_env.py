@@ -77,11 +77,24 @@ class NppVecEnvironment:
     observation, and when the kernel auto-resets it.  Visual stacking needs enable_visual_observations (otherwise it is
     ignored, as in the reference).  The flags are taken as given, as create_evaluation_env passes them: the reference's
     create_training_env omits enable_visual_stacking, so the wrapper's default (on) applies there -- pass it explicitly.
-    Sizes outside 1..12 and other paddings raise ValueError with the reference's messages.  Augmentation is not provided.
+    Sizes outside 1..12 and other paddings raise ValueError with the reference's messages.
     With state stacking, info["terminal_game_state_stack"] [N, K, 41] is, for every env reset in this step, the stack it
     would have shown at its terminal step (the previous window's last K - 1 entries, then terminal_state), else the live stack.
     output="torch": the stacked tensors are views of device rings (no copy): each env's K entries are contiguous, but envs are
     2 K entries apart, and the rings are rewritten by the next step.  output="numpy": contiguous host arrays.
+
+    Frame augmentation (the reference's AugmentationConfig, config.py:64-87, applied by FrameStackWrapper.observation to
+    player_frame and global_view at every observation, frame_stack_wrapper.py:343-377, 402-462):
+    enable_augmentation=True returns both keys augmented on the device -- translate, horizontal flip, coarse dropout and
+    brightness / contrast, in the reference's order and with its gates 0.8 p, 0.4 p, 0.5 p, 0.4 p (augmentation_p, default 0.5)
+    and its three intensities (augmentation_intensity "light", "medium", "strong").  The pixels follow the project's own integer
+    definition: PARITY WITH ALBUMENTATIONS' PIXELS IS UNPINNED (albumentations' output is not reproduced bit for bit), and the
+    draws are a counter-based hash of (augmentation_seed, env index, observation count, key), not numpy's global stream;
+    augmentation_seed=None takes fresh entropy, reset(seed=s) restarts the stream from s.  Every observation draws anew, reset
+    observations included; all K frames of a stacked player_frame share one draw, global_view draws on its own.  Shapes and
+    spaces are unchanged; the frame rings keep clean frames.  output="torch": persistent device tensors, rewritten by the next
+    step.  Ignored without enable_visual_observations (nothing to act on, as in the reference); a bad intensity or p raises
+    ValueError with the reference's messages.  Off by default (the reference's default is on): nothing is allocated or launched.
 
     Level pool (the reference's per-episode map draw, env_map_loader.py:111-208): level_weights, one non-negative
     weight per level, makes every env draw its next level -- level l with probability w[l] / sum(w) -- whenever its episode ends in
@@ -122,13 +135,16 @@ class NppVecEnvironment:
                  enable_switch_states=False, fast_reset=True, stream=None, enable_reachability=False, obs_overlap=0,
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
-                 observation_mode="full"):
+                 observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
+                 augmentation_seed=None):
         assert output in ("torch", "numpy")
+        spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         self._minimal = spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
             enable_visual_frame_stacking=enable_visual_frame_stacking, enable_state_stacking=enable_state_stacking,
             enable_graph_observations=enable_graph_observations, enable_spatial_context=enable_spatial_context,
-            enable_reachability=enable_reachability, enable_switch_states=enable_switch_states)
+            enable_reachability=enable_reachability, enable_switch_states=enable_switch_states,
+            enable_augmentation=enable_augmentation)
         spaces.check_frame_stack(visual_stack_size, state_stack_size, frame_stack_padding_type)
         self.num_envs = int(num_envs)
         self.frame_skip = int(frame_skip)
@@ -199,6 +215,15 @@ class NppVecEnvironment:
         self._graph = None
         if enable_graph_observations:
             self._graph = _HostGraphRows(levels, self.num_envs) if output == "numpy" else {}
+        # augmentation acts on the two visual keys only (without them the wrapper has nothing to act on)
+        self._aug = bool(enable_augmentation) and self.enable_visual_observations
+        if self._aug:
+            self._aug_cfg = (float(augmentation_p), augmentation_intensity)
+            seed = int(augmentation_seed) if augmentation_seed is not None else int(np.random.SeedSequence().entropy)
+            self._b.set_frame_augmentation(True, *self._aug_cfg, seed=seed)
+            self._obs_names = [k for k in self._obs_names if k not in ("player_frame", "global_view")]   # (numpy: the clean frames stay on the device)
+            if not hasattr(self, "_host_stack"):
+                self._host_stack = {}
 
     # -- helpers ------------------------------------------------------------------------------------------------
     def _produce(self, reset_all=False):
@@ -223,14 +248,16 @@ class NppVecEnvironment:
             self._graph = b.graph_observation()
         if self._vk or self._sk:
             b.frame_stack_push(self._reset_bits, reset_all, None if reset_all else self._term_stack)
+        if self._aug:   # (after the push: the padding of reset envs is in the ring)
+            b.frame_augment()
 
     def _stacked(self, src, with_terminal=False):
         """src with the stacked windows in place of player_frame / game_state (+ terminal_game_state_stack).  Device views for
         output="torch"; for output="numpy" the copies into pinned memory are only enqueued here -- the caller's to_host()
         synchronises the stream."""
-        if not (self._vk or self._sk):
+        if not (self._vk or self._sk or self._aug):
             return src
-        pf, gs = self._b.frame_stack_views()
+        pf, gs = self._b.frame_stack_views() if (self._vk or self._sk) else (None, None)
         stk = {}
         if pf is not None:
             stk["player_frame"] = pf
@@ -238,6 +265,10 @@ class NppVecEnvironment:
             stk["game_state"] = gs
             if with_terminal:
                 stk["terminal_game_state_stack"] = self._term_stack
+        if self._aug:   # the augmented copies take the place of both visual keys
+            apf, agv = self._b.frame_augment_views()
+            stk["player_frame"] = apf if self._vk else apf[:, 0]
+            stk["global_view"] = agv
         if self.output == "numpy":
             with self._b._ctx():
                 for k, t in stk.items():
@@ -287,8 +318,9 @@ class NppVecEnvironment:
         """Reset every env to its level's spawn state (npp_environment.py:504).  The first reset of a level assignment is
         Simulator.reset (nsim.py:62); later ones are Simulator.fast_reset (nsim.py:78) unless fast_reset=False.
 
-        seed     seeds `action_space_sample()` only: the reference's seed picks the next map (env_map_loader.py), here the
-                 levels are assigned explicitly, and the simulation itself has no randomness.
+        seed     seeds `action_space_sample()` (and reseeds the level pool and the frame augmentation, when on): the reference's
+                 seed picks the next map (env_map_loader.py), here the levels are assigned explicitly, and the simulation itself
+                 has no randomness.
         options  {"checkpoint": c} restores a Go-Explore checkpoint (base_environment.py:1769-1789, _reset_to_checkpoint):
                  c = "snapshot" puts back the state saved by `snapshot()` (a device-side copy: what the replay below would
                  reproduce, bit for bit); otherwise c (or c["action_sequence"] / c.action_sequence) is the action sequence to
@@ -302,6 +334,8 @@ class NppVecEnvironment:
                 w = self._level_weights_now
                 self._b.set_level_pool(None)
                 self._b.set_level_pool(w, self._level_seed)
+            if self._aug:   # the augmentation stream restarts from the seed (observation count 0)
+                self._b.set_frame_augmentation(True, *self._aug_cfg, seed=int(seed))
         ckpt = (options or {}).get("checkpoint")
         info = {}
         if isinstance(ckpt, str):
@@ -471,17 +505,21 @@ class NppEnvironment:
     npp_environment.py:504).  One GPU lane group does the work of one Python simulator; use NppVecEnvironment for
     throughput.  Frame stacking takes NppVecEnvironment's arguments; stacked keys come without the batch dimension
     (player_frame (K, 84, 84, 1), game_state (K, 41)).  observation_mode="minimal": NppVecEnvironment's minimal mode
-    (minimal_observation (40,), action_mask (6,) and the pass-through scalars; no terminal minimal observation)."""
+    (minimal_observation (40,), action_mask (6,) and the pass-through scalars; no terminal minimal observation).
+    enable_augmentation / augmentation_p / augmentation_intensity / augmentation_seed: NppVecEnvironment's frame augmentation."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
-                 state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full"):
+                 state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
+                 enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None):
+        spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
             enable_visual_frame_stacking=enable_visual_frame_stacking, enable_state_stacking=enable_state_stacking,
             enable_graph_observations=enable_graph_observations, enable_spatial_context=enable_spatial_context,
-            enable_reachability=enable_reachability, enable_switch_states=enable_switch_states)
+            enable_reachability=enable_reachability, enable_switch_states=enable_switch_states,
+            enable_augmentation=enable_augmentation)
         if map_data is None:
             if custom_map_path is None:
                 raise ValueError("NppEnvironment needs map_data or custom_map_path")
@@ -495,7 +533,9 @@ class NppEnvironment:
                                     enable_visual_frame_stacking=enable_visual_frame_stacking, visual_stack_size=visual_stack_size,
                                     enable_state_stacking=enable_state_stacking, state_stack_size=state_stack_size,
                                     frame_stack_padding_type=frame_stack_padding_type,
-                                    enable_graph_observations=enable_graph_observations, observation_mode=observation_mode)
+                                    enable_graph_observations=enable_graph_observations, observation_mode=observation_mode,
+                                    enable_augmentation=enable_augmentation, augmentation_p=augmentation_p,
+                                    augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
