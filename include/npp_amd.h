@@ -335,6 +335,43 @@ int npp_entity_checksum(npp_handle h, int env0, int count, double *out);
 int npp_snapshot(npp_handle h);
 int npp_restore(npp_handle h, const uint8_t *env_mask);
 
+/* Checkpoint archive: restore any env from any slot.  The reference's Go-Explore checkpoints (state_checkpoint.py,
+ * action_replayer.py, base_environment.py:1769-1789 _reset_to_checkpoint) are found by one worker and restarted from by any worker
+ * on the same level, many times; npp_snapshot's single slot lets env e go back only to what env e itself was.  The archive holds
+ * n_slots records of ONE env's state each -- everything npp_restore carries for an env: the double and word planes, the entity
+ * words, the spatial-context cache row, the zoo block, the reachability key + cache row (or a "none" marker when the record was
+ * stored before the first npp_reachability), the truncation limit and the level -- as one contiguous record whose size follows
+ * from the loaded level set (npp_archive_record_bytes).
+ * npp_archive_create(h, n_slots): allocates it (empty); 0 frees it; < 0 is NPP_ERR_INVALID; needs levels loaded; a failed
+ *   allocation is NPP_ERR_HIP and leaves the previous archive in place.  npp_load_levels drops the archive.
+ * npp_archive_store / npp_archive_restore(h, d_envs, d_slots, count, d_status): d_envs / d_slots are DEVICE arrays i32[count],
+ *   d_status a device array i32[count] or NULL.  Enqueued on the handle's stream after joining an observation overlap; no
+ *   synchronisation and no host copy of the lists, so a training loop builds them on the same stream.  Entry i copies env
+ *   d_envs[i] to slot d_slots[i] (store) or the slot to the env (restore); its status is decided on the device:
+ *     0 done   1 skipped (env < 0 or slot < 0: padding of a fixed-length list)   2 level mismatch (restore: the slot's level is not
+ *     the level the env plays; the env is not touched)   3 slot empty (restore)   4 env or slot out of range (nothing read or written)
+ *   Every access stays in bounds whatever the lists hold.  The same env twice in one restore list, or the same slot twice in one
+ *   store list, is a caller error (the result is a mixture of the two); one slot restored into many envs is the normal case.
+ *   A restored env is in the reference's "reset + replay" condition exactly as after npp_restore: the per-episode reachability
+ *   dictionary is emptied, the cached reachability vector is the slot's (or absent), and the env keeps the slot's frame count and
+ *   truncation limit, so its truncation budget continues from the checkpoint (the reference's fresh budget after a replay,
+ *   truncation_checker.py:53-58, is not modelled).
+ *   NPP_ERR_STATE, with the cause in the message: no archive; the level pool is on; an entity is repositioned with
+ *   npp_set_entity_pos -- once levels move on the device or an entity is moved the host cannot know what a record's tables belong
+ *   to; for the same reason npp_set_level_pool and a repositioning npp_set_entity_pos are refused while an archive exists.
+ *   npp_assign_levels keeps the archive: records carry their level and restore checks it on the device.
+ * npp_archive_meta_view: device arrays f64[n_slots][4] = x, y, xspeed, yspeed and i32[n_slots][6] = stored (0 / 1), level, frame,
+ *   cell_x, cell_y, switch_activated, written by the store kernel from the state it copies with npp_dump_state's decode (frame =
+ *   i32 column 22, switch_activated = column 13 != 1); the cell is floor(x / 24), floor(y / 24), the reference's 24 px
+ *   discretisation (state_checkpoint.py:26, replay/demo_checkpoint_seeder.py:284-287).  Valid while the archive lives, so a
+ *   selection rule can run on them on the handle's stream. */
+int npp_archive_create(npp_handle h, int n_slots);
+int npp_archive_store(npp_handle h, const int32_t *d_envs, const int32_t *d_slots, int count, int32_t *d_status);
+int npp_archive_restore(npp_handle h, const int32_t *d_envs, const int32_t *d_slots, int count, int32_t *d_status);
+int npp_archive_meta_view(npp_handle h, const double **d_f64 /* [n_slots][4] */, const int32_t **d_i32 /* [n_slots][6] */);
+int npp_archive_num_slots(npp_handle h);
+int npp_archive_record_bytes(npp_handle h);   /* 0 without an archive */
+
 /* Launch geometry: lanes_per_env wavefront lanes cooperate on one environment (power of two, 1..64; 0 = choose from
  * n_envs so that the grid fills the chip), waves_per_block wavefronts share one LDS copy of a level (1..4, 0 = auto).
  * Results are bit-identical for every geometry; only speed changes. */

@@ -37,6 +37,8 @@ EXPORTS = [
     "npp_set_minimal_observation", "npp_minimal_observation", "npp_minimal_encode_host",
     "npp_set_frame_augmentation", "npp_frame_augment", "npp_frame_augment_view", "npp_frame_augment_params_host",
     "npp_frame_augment_apply_host",
+    "npp_archive_create", "npp_archive_store", "npp_archive_restore", "npp_archive_meta_view", "npp_archive_num_slots",
+    "npp_archive_record_bytes",
 ]
 
 
@@ -146,6 +148,12 @@ def lib():
     L.npp_frame_augment_view.argtypes = [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.npp_frame_augment_params_host.argtypes = [C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.npp_frame_augment_apply_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.npp_archive_create.argtypes = [H, C.c_int]
+    L.npp_archive_store.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_archive_restore.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_archive_meta_view.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.npp_archive_num_slots.argtypes = [H]
+    L.npp_archive_record_bytes.argtypes = [H]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

@@ -89,8 +89,12 @@ class NppAsyncVecEnvironment:
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
-                 enable_augmentation=False):
+                 enable_augmentation=False, checkpoint_slots=0):
         assert output in ("torch", "numpy")
+        if checkpoint_slots:
+            raise NotImplementedError("NppAsyncVecEnvironment has no checkpoint archive (checkpoint_slots): its sub-batches are "
+                                      "separate handles, and a slot restores only into envs of the handle that stored it; "
+                                      "NppVecEnvironment(checkpoint_slots=...) has it")
         if enable_augmentation:
             raise NotImplementedError("NppAsyncVecEnvironment has no frame augmentation (it has no visual observations): "
                                       "NppVecEnvironment(enable_augmentation=True) has it")

@@ -1,0 +1,114 @@
+// npp_archive.hip -- the checkpoint archive's two kernels (include/npp_amd.h, npp_archive_store / npp_archive_restore): entry i of
+// the device lists moves the state of env envs[i] into slot slots[i] (store) or back (restore).  One wavefront per entry: the
+// strided [plane][n] planes go one plane per lane, the contiguous rows (zoo block, spatial-context cache, reachability row) and
+// the record go over consecutive lanes, so the slot side of an entry is one contiguous stream.  Everything that decides an entry
+// (the two list values, the slot's "stored" word and level) is wave-uniform; lane 0 writes the status and the meta row.  An entry
+// whose status is not 0 reads only the list values (and, restore, the slot's meta and level words once both indices are known
+// to be in range) and writes only its status.
+#include <hip/hip_runtime.h>
+
+#include "npp_archive.hpp"
+
+namespace npp {
+namespace {
+
+constexpr int ENTRIES_PER_BLOCK = 4;   // 256 threads
+
+template <bool STORE> __global__ __launch_bounds__(256) void npp_archive_kernel(ArchiveArgs a) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int i = blockIdx.x * ENTRIES_PER_BLOCK + (threadIdx.x >> 6);
+    if (i >= a.count) return;
+    const ArchiveLayout &L = a.lay;
+    const int env = a.envs[i], slot = a.slots[i];
+    uint32_t *rec = nullptr;
+    int st = ARCHIVE_DONE;
+    if (env < 0 || slot < 0) {
+        st = ARCHIVE_SKIPPED;
+    } else if (env >= a.n || slot >= a.n_slots) {
+        st = ARCHIVE_RANGE;
+    } else {
+        rec = a.rec + (size_t)slot * L.words;
+        if (!STORE) {
+            if (a.meta_i32[(size_t)slot * ARCHIVE_META_I32] == 0) st = ARCHIVE_EMPTY;
+            else if ((int32_t)rec[L.off_tail + 1] != a.env_level[env]) st = ARCHIVE_LEVEL_MISMATCH;
+        }
+    }
+    if (lane == 0 && a.status) a.status[i] = st;
+    if (st != ARCHIVE_DONE) return;
+
+    const size_t N = (size_t)a.n, e = (size_t)env;
+    double *rec64 = reinterpret_cast<double *>(rec);   // the f64 planes and the zoo block: words [0, off_u32)
+    // strided planes, one per lane
+    for (int k = lane; k < NF64; k += WAVE) {
+        if (STORE) rec64[k] = a.f64[k * N + e];
+        else a.f64[k * N + e] = rec64[k];
+    }
+    for (int k = lane; k < NU32 + L.n_words_max; k += WAVE) {   // (off_ent == off_u32 + NU32: one run of the record)
+        uint32_t *live = k < NU32 ? a.u32 + k * N + e : a.ent + (size_t)(k - NU32) * N + e;
+        if (STORE) rec[L.off_u32 + k] = *live;
+        else *live = rec[L.off_u32 + k];
+    }
+    // contiguous rows, consecutive lanes
+    if (a.zoo) {
+        double *live = a.zoo + e * L.zoo_words;
+        for (int k = lane; k < L.zoo_words; k += WAVE) {
+            if (STORE) rec64[NF64 + k] = live[k];
+            else live[k] = rec64[NF64 + k];
+        }
+    }
+    if (lane < ARCHIVE_SC) {
+        float *live = a.sc + e * ARCHIVE_SC + lane;
+        if (STORE) rec[L.off_sc + lane] = __float_as_uint(*live);
+        else *live = __uint_as_float(rec[L.off_sc + lane]);
+    }
+    if (STORE) {
+        const bool reach = a.reach_key != nullptr;
+        if (lane < ARCHIVE_REACH_ROW) rec[L.off_reach + 1 + lane] = reach ? __float_as_uint(a.reach_cache[e * ARCHIVE_REACH_ROW + lane]) : 0u;
+        if (lane == 0) {
+            const int level = a.env_level[env];
+            rec[L.off_reach] = reach ? a.reach_key[env] : 0u;
+            rec[L.off_tail] = (uint32_t)a.trunc[env];
+            rec[L.off_tail + 1] = (uint32_t)level;
+            rec[L.off_tail + 2] = reach ? 1u : 0u;
+            // the meta row, with npp_dump_state's decode
+            const double x = a.f64[F_X * N + e], y = a.f64[F_Y * N + e];
+            double *mf = a.meta_f64 + (size_t)slot * ARCHIVE_META_F64;
+            mf[0] = x; mf[1] = y; mf[2] = a.f64[F_VX * N + e]; mf[3] = a.f64[F_VY * N + e];
+            const int sw = a.hdr[level].obs_switch;
+            int sw_state = 2;
+            if (sw >= 0) sw_state = (a.ent[(size_t)(sw >> 4) * N + e] >> ((sw & 15) * 2)) & 3;
+            int32_t *mi = a.meta_i32 + (size_t)slot * ARCHIVE_META_I32;
+            mi[1] = level;
+            mi[2] = (int32_t)(a.u32[U_D * N + e] & 0xffffu);
+            mi[3] = (int32_t)floor(x / 24.0);
+            mi[4] = (int32_t)floor(y / 24.0);
+            mi[5] = sw_state != 1;
+            mi[0] = 1;
+        }
+    } else {
+        if (lane == 0) a.trunc[env] = (int32_t)rec[L.off_tail];
+        if (a.reach_key) {
+            // "reset + replay" (base_environment.py:1769-1789): the path calculator's per-episode dictionary is empty afterwards
+            if (lane == 0 && a.reach_last_episode) a.reach_last_episode[env] = 0xffffffffu;
+            if (rec[L.off_tail + 2]) {
+                if (lane == 0) a.reach_key[env] = rec[L.off_reach];
+                if (lane < ARCHIVE_REACH_ROW) a.reach_cache[e * ARCHIVE_REACH_ROW + lane] = __uint_as_float(rec[L.off_reach + 1 + lane]);
+            } else if (lane == 0) {
+                a.reach_key[env] = 0u;   // stored before the first npp_reachability: no cached vector
+            }
+        }
+    }
+}
+
+template <bool STORE> hipError_t launch(const ArchiveArgs &a, hipStream_t s) {
+    if (a.count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(npp_archive_kernel<STORE>, dim3((a.count + ENTRIES_PER_BLOCK - 1) / ENTRIES_PER_BLOCK), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_archive_store(const ArchiveArgs &a, hipStream_t s) { return launch<true>(a, s); }
+hipError_t launch_archive_restore(const ArchiveArgs &a, hipStream_t s) { return launch<false>(a, s); }
+
+}  // namespace npp

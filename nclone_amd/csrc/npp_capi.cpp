@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/npp_amd.h"
+#include "npp_archive.hpp"
 #include "npp_augment.hpp"
 #include "npp_graph.hpp"
 #include "npp_host.hpp"
@@ -237,6 +238,16 @@ struct FrameAug {
     const uint8_t *pf_out = nullptr, *gv_out = nullptr;   // d_out of the last npp_render_player_frame / npp_render_global_view
 };
 
+// checkpoint archive (npp_archive_create, npp_archive.hip): n_slots records of one env's state each, plus a meta row per slot.
+// Sized by the loaded level set, dropped with it.
+struct Archive {
+    int n_slots = 0;              // 0 = none
+    ArchiveLayout lay;
+    DevBuf<uint32_t> rec;         // [n_slots][lay.words]
+    DevBuf<double> meta_f64;      // [n_slots][ARCHIVE_META_F64]
+    DevBuf<int32_t> meta_i32;     // [n_slots][ARCHIVE_META_I32], word 0 = the slot holds a record
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -269,6 +280,7 @@ struct npp_handle_s {
     Pool pool;
     Minimal mini;
     FrameAug aug;
+    Archive ar;
 };
 
 
@@ -886,6 +898,100 @@ int npp_restore(npp_handle h, const uint8_t *env_mask) {
     return NPP_OK;
 }
 
+namespace {
+// the refusals the three archive calls share: once levels move on the device, or an entity is repositioned, the host cannot
+// know what a record's tables belong to
+int archive_refusal(npp_handle h, const char *who) {
+    if (h->pool.on) return fail(h, NPP_ERR_STATE, std::string(who) + ": the level pool is on (npp_set_level_pool)");
+    if (h->n_ovr) return fail(h, NPP_ERR_STATE, std::string(who) + ": an exit switch / door is repositioned (npp_set_entity_pos)");
+    return NPP_OK;
+}
+
+int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_envs, const int32_t *d_slots, int count, int32_t *d_status) {
+    if (!h) return NPP_ERR_INVALID;
+    if (count < 0 || (count > 0 && (!d_envs || !d_slots))) return fail(h, NPP_ERR_INVALID, std::string(who) + ": bad arguments");
+    if (!h->ar.n_slots) return fail(h, NPP_ERR_STATE, std::string(who) + ": no archive (npp_archive_create)");
+    if (int rc = archive_refusal(h, who)) return rc;
+    ON_DEVICE_JOINED(h);
+    const LevelSet &L = h->ls;
+    Archive &A = h->ar;
+    ArchiveArgs a;
+    a.lay = A.lay;
+    a.n = h->n;
+    a.n_slots = A.n_slots;
+    a.count = count;
+    a.envs = d_envs;
+    a.slots = d_slots;
+    a.status = d_status;
+    a.rec = A.rec.get();
+    a.meta_f64 = A.meta_f64.get();
+    a.meta_i32 = A.meta_i32.get();
+    a.f64 = h->env.f64.get();
+    a.u32 = h->env.u32.get();
+    a.ent = L.ent.get();
+    a.sc = h->env.sc.get();
+    a.zoo = A.lay.zoo_words ? L.zoo.get() : nullptr;
+    a.trunc = h->env.trunc.get();
+    a.env_level = h->env.level.get();
+    a.hdr = L.hdr.get();
+    a.reach_key = L.reach.key.get();
+    a.reach_cache = L.reach.cache.get();
+    a.reach_last_episode = L.reach.last_episode.get();
+    HIP_TRY(h, store ? launch_archive_store(a, h->stream) : launch_archive_restore(a, h->stream));
+    // a restored env takes the record's truncation limit on the device: the host mirror is read back where a host path needs it
+    if (!store && count > 0) h->pool.dirty = true;
+    return NPP_OK;
+}
+}  // namespace
+
+int npp_archive_create(npp_handle h, int n_slots) {
+    if (!h) return NPP_ERR_INVALID;
+    if (n_slots < 0) return fail(h, NPP_ERR_INVALID, "npp_archive_create: n_slots must be >= 0 (0 frees the archive)");
+    ON_DEVICE_JOINED(h);
+    if (n_slots == 0) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // queued store / restore launches still read the records
+        h->ar = Archive();
+        return NPP_OK;
+    }
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_archive_create: no levels loaded");
+    if (int rc = archive_refusal(h, "npp_archive_create")) return rc;
+    Archive A;   // complete or not at all: a failed allocation leaves the previous archive in place
+    A.lay = archive_layout(h->ls.n_words_max, h->ls.zoo ? h->ls.zoo_words : 0);
+    const size_t S = (size_t)n_slots;
+    if (A.rec.alloc(S * A.lay.words) != hipSuccess || A.meta_f64.alloc(S * ARCHIVE_META_F64) != hipSuccess ||
+        A.meta_i32.alloc(S * ARCHIVE_META_I32) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, NPP_ERR_HIP, "npp_archive_create: hipMalloc of " + std::to_string(n_slots) + " slots of " +
+                                        std::to_string(A.lay.words * 4) + " bytes failed");
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemsetAsync(A.rec.get(), 0, A.rec.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(A.meta_f64.get(), 0, A.meta_f64.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(A.meta_i32.get(), 0, A.meta_i32.bytes(), h->stream));
+    A.n_slots = n_slots;
+    h->ar = std::move(A);
+    return NPP_OK;
+}
+
+int npp_archive_store(npp_handle h, const int32_t *d_envs, const int32_t *d_slots, int count, int32_t *d_status) {
+    return archive_move(h, "npp_archive_store", true, d_envs, d_slots, count, d_status);
+}
+
+int npp_archive_restore(npp_handle h, const int32_t *d_envs, const int32_t *d_slots, int count, int32_t *d_status) {
+    return archive_move(h, "npp_archive_restore", false, d_envs, d_slots, count, d_status);
+}
+
+int npp_archive_meta_view(npp_handle h, const double **d_f64, const int32_t **d_i32) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->ar.n_slots) return fail(h, NPP_ERR_STATE, "npp_archive_meta_view: no archive (npp_archive_create)");
+    if (d_f64) *d_f64 = h->ar.meta_f64.get();
+    if (d_i32) *d_i32 = h->ar.meta_i32.get();
+    return NPP_OK;
+}
+
+int npp_archive_num_slots(npp_handle h) { return h ? h->ar.n_slots : 0; }
+int npp_archive_record_bytes(npp_handle h) { return h && h->ar.n_slots ? h->ar.lay.words * 4 : 0; }
+
 int npp_set_launch_geometry(npp_handle h, int lanes_per_env, int waves_per_block) {
     if (!h) return NPP_ERR_INVALID;
     if (lanes_per_env < 0 || lanes_per_env > 64 || (lanes_per_env & (lanes_per_env - 1)) || waves_per_block < 0 || waves_per_block > 4)
@@ -1020,6 +1126,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     HIP_TRY(h, hipMemcpy(next.hdr.get(), hdrs.data(), next.hdr.bytes(), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemset(next.ent.get(), 0, next.ent.bytes()));
     h->ls = std::move(next);
+    h->ar = Archive();   // the checkpoint archive's records were laid out for the old set
     // the snapshot planes of the old set's per-env buffers go with it (the snapshot no longer matches assign_gen)
     h->snap.zoo.reset(); h->snap.rkey.reset(); h->snap.rcache.reset(); h->snap.reach = false;
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
@@ -1118,6 +1225,7 @@ int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64
     std::string err;
     if (!pool_cdf(weights, n_levels, (int)h->ls.levels.size(), cdf, last, err)) return fail(h, NPP_ERR_INVALID, "npp_set_level_pool: " + err);
     if (h->n_ovr) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: an exit switch / door is repositioned (npp_set_entity_pos)");
+    if (h->ar.n_slots) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: a checkpoint archive exists (npp_archive_create)");
     ON_DEVICE_JOINED(h);
     const size_t N = (size_t)h->n;
     DevBuf<double> &d_cdf = h->ls.pool_cdf;
@@ -1621,6 +1729,7 @@ int npp_set_entity_pos(npp_handle h, int env, int kind, double x, double y) {
     if (!h || env < 0 || env >= h->n || (kind != 0 && kind != 1)) return fail(h, NPP_ERR_INVALID, "npp_set_entity_pos: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: no levels loaded");
     if (h->pool.on) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the level pool is on (npp_set_level_pool)");
+    if (h->ar.n_slots && x == x && y == y) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: a checkpoint archive exists (npp_archive_create)");
     {
         ON_DEVICE_JOINED(h);
         if (int rc = pull_levels(h)) return rc;

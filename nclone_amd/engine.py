@@ -77,9 +77,35 @@ AUG_SCALES = {"light": 0.7, "medium": 1.0, "strong": 1.3}   # frame_augmentation
 AUG_WORDS = 14   # int32 words of one AugParams (npp_augment.hpp)
 
 
+def check_archive_lists(envs, slots, unique, what):
+    """The host-side checks of NppBatch.archive_store / archive_restore (no device needed): both lists one-dimensional, of one
+    length, int32 when they are tensors and integers when they are arrays; in an array, no value of the `unique` list ("envs" or
+    "slots") comes twice among the entries that are not skipped.  CUDA tensors are taken as they are -- no host copy, no
+    synchronisation: the device decides every entry.  Returns {"envs": ..., "slots": ...} with arrays as numpy arrays."""
+    lists = {"envs": envs, "slots": slots}
+    for name, v in lists.items():
+        if isinstance(v, torch.Tensor):
+            if v.dtype != torch.int32:
+                raise TypeError("%s: %s must be an int32 tensor, not %s" % (what, name, v.dtype))
+        else:
+            v = lists[name] = np.asarray(v)
+            if v.dtype.kind not in "iu":
+                raise TypeError("%s: %s must hold integers, not %s" % (what, name, v.dtype))
+        if v.ndim != 1:
+            raise ValueError("%s: %s must be one-dimensional" % (what, name))
+    if len(lists["envs"]) != len(lists["slots"]):
+        raise ValueError("%s: envs and slots differ in length (%d, %d)" % (what, len(lists["envs"]), len(lists["slots"])))
+    u, other = lists[unique], lists["slots" if unique == "envs" else "envs"]
+    if isinstance(u, np.ndarray):
+        live = u[(u >= 0) & (other >= 0)] if isinstance(other, np.ndarray) else u[u >= 0]
+        if len(np.unique(live)) != len(live):
+            raise ValueError("%s: the same %s comes twice" % (what, unique[:-1]))
+    return lists
+
+
 def _device_tensor(ptr, numel, dtype, device):
     """A torch tensor over `numel` elements of device memory that the native handle owns (no copy, no ownership)."""
-    typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4"}[dtype]
+    typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4", torch.float64: "<f8"}[dtype]
 
     class _Holder:
         __cuda_array_interface__ = {"shape": (int(numel),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
@@ -236,6 +262,7 @@ class NppBatch:
         nat.check(self.h, self.lib.npp_load_levels(
             self.h, blob.ctypes.data_as(C.POINTER(C.c_double)), offsets.ctypes.data_as(C.POINTER(C.c_int64)), len(offsets) - 1))
         self.n_levels = len(offsets) - 1
+        self._archive_meta = None   # (the checkpoint archive goes with the level set)
 
     def assign_levels(self, level_ids, env_ids=None):
         lv = np.ascontiguousarray(level_ids, dtype=np.int32)
@@ -382,8 +409,18 @@ class NppBatch:
         nat.check(self.h, self.lib.npp_tick(self.h, C.c_void_p(inputs.data_ptr()), int(inputs.shape[0])))
         self._keep = inputs
 
-    def observe(self):
-        nat.check(self.h, self.lib.npp_observe(self.h, C.byref(self._out_min)))
+    def observe(self, flags_out=None):
+        """Write the observation of the current state into the block.  flags_out: uint8 CUDA tensor [N] that receives the
+        flags of the observed state instead of the block; the block's flags, reward, frames and work then keep describing the
+        last step (NppVecEnvironment.restart observes between two steps)."""
+        if flags_out is None:
+            nat.check(self.h, self.lib.npp_observe(self.h, C.byref(self._out_min)))
+            return
+        assert flags_out.dtype == torch.uint8 and flags_out.is_cuda and flags_out.numel() == self.n and flags_out.is_contiguous()
+        out = nat.StepOut()
+        C.memmove(C.byref(out), C.byref(self._out_min), C.sizeof(nat.StepOut))
+        out.d_flags, out.d_reward, out.d_frames, out.d_work = flags_out.data_ptr(), None, None, None
+        nat.check(self.h, self.lib.npp_observe(self.h, C.byref(out)))
 
     def render_player_frame(self, out=None):
         """out: uint8 CUDA tensor [N, 84, 84] (or [N, 84, 84, 1]) filled with the player_frame of every env; default: the
@@ -492,6 +529,75 @@ class NppBatch:
             m = np.ascontiguousarray(mask, dtype=np.uint8)
             assert len(m) == self.n
             nat.check(self.h, self.lib.npp_restore(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    # ---- checkpoint archive (include/npp_amd.h npp_archive_create; the reference's Go-Explore checkpoints) ----------
+    def archive_create(self, n_slots):
+        """Allocate the checkpoint archive: n_slots records of one env's state each (0 frees it).  Needs levels loaded;
+        load_levels drops it."""
+        n_slots = int(n_slots)
+        if n_slots < 0:
+            raise ValueError("archive_create: n_slots must be >= 0 (0 frees the archive)")
+        nat.check(self.h, self.lib.npp_archive_create(self.h, n_slots))
+        self._archive_meta = None
+
+    def archive_num_slots(self):
+        return int(self.lib.npp_archive_num_slots(self.h))
+
+    def archive_record_bytes(self):
+        """Size of one slot's record in bytes (follows from the loaded level set); 0 without an archive."""
+        return int(self.lib.npp_archive_record_bytes(self.h))
+
+    def _archive_lists(self, envs, slots, unique, what):
+        """The two lists as int32 CUDA tensors of one length (check_archive_lists, then arrays are uploaded)."""
+        lists = check_archive_lists(envs, slots, unique, what)
+        out = []
+        with self._ctx():
+            for name in ("envs", "slots"):
+                v = lists[name]
+                if isinstance(v, np.ndarray):
+                    v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).to(self.device)
+                elif not v.is_cuda:
+                    v = v.to(self.device)
+                out.append(v.contiguous())
+        return out
+
+    def _archive_move(self, fn, envs, slots, status, unique, what):
+        e, s = self._archive_lists(envs, slots, unique, what)
+        st = None
+        if status:
+            with self._ctx():
+                st = torch.empty(len(e), dtype=torch.int32, device=self.device)
+        nat.check(self.h, fn(self.h, C.c_void_p(e.data_ptr()), C.c_void_p(s.data_ptr()), len(e),
+                             C.c_void_p(st.data_ptr()) if st is not None else None))
+        self._keep_archive = (e, s)   # the launch reads the lists in stream order
+        return st
+
+    def archive_store(self, envs, slots, status=False):
+        """Entry i copies the state of env envs[i] into slot slots[i].  envs / slots: int32 CUDA tensors [count] (used where
+        they are, nothing synchronises), or integer arrays (uploaded; a slot that comes twice raises ValueError).  A negative
+        env or slot skips the entry.  status=True returns the device status tensor i32 [count]: 0 done, 1 skipped, 4 out of
+        range."""
+        return self._archive_move(self.lib.npp_archive_store, envs, slots, status, "slots", "archive_store")
+
+    def archive_restore(self, envs, slots, status=False):
+        """Entry i puts the record of slot slots[i] into env envs[i] (any env playing the record's level; one slot may go to
+        many envs).  Arguments as archive_store (an env that comes twice in an array raises ValueError).  Status: 0 done,
+        1 skipped, 2 the slot's level is not the env's, 3 the slot is empty, 4 out of range -- only status 0 touches the env."""
+        return self._archive_move(self.lib.npp_archive_restore, envs, slots, status, "envs", "archive_restore")
+
+    def archive_meta(self):
+        """{"x", "y", "vx", "vy": f64 [n_slots]; "stored", "level", "frame", "cell_x", "cell_y", "switch_activated": i32
+        [n_slots]}: CUDA views (no copy) of the rows the store kernel writes, valid while the archive lives."""
+        if getattr(self, "_archive_meta", None) is None:
+            f, i = C.c_void_p(), C.c_void_p()
+            nat.check(self.h, self.lib.npp_archive_meta_view(self.h, C.byref(f), C.byref(i)))
+            ns = self.archive_num_slots()
+            tf = _device_tensor(f.value, ns * 4, torch.float64, self.device).view(ns, 4)
+            ti = _device_tensor(i.value, ns * 6, torch.int32, self.device).view(ns, 6)
+            meta = {k: tf[:, c] for c, k in enumerate(("x", "y", "vx", "vy"))}
+            meta.update({k: ti[:, c] for c, k in enumerate(("stored", "level", "frame", "cell_x", "cell_y", "switch_activated"))})
+            self._archive_meta = meta
+        return self._archive_meta
 
     # ---- frame stacking (include/npp_amd.h npp_set_frame_stack; the reference's FrameStackWrapper) ----------------
     def set_frame_stack(self, visual_k=0, state_k=0, padding="zero"):

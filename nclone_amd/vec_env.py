@@ -113,6 +113,13 @@ class NppVecEnvironment:
     buffer sets alternate, filled from host copies of the per-level tables (no per-step device-to-host copy of these 162.5 KB per
     env), so the previous step's arrays stay valid.  Not part of the terminal info.  Off by default.
 
+    Checkpoint archive (the reference's Go-Explore checkpoints, state_checkpoint.py / base_environment.py:1769-1789):
+    checkpoint_slots=S > 0 keeps S single-env states on the device.  archive_store(slot_ids) saves env e in slot slot_ids[e];
+    reset(options={"checkpoint": {"slots": slot_ids}}) and restart(slot_ids) put a slot into ANY env that plays the slot's level --
+    one copy instead of replaying the action sequence; archive_meta() shows each slot's position, 24 px cell, frame, level and
+    switch state to a selection rule in torch.  A restored env keeps the slot's frame count (its truncation budget continues from
+    the checkpoint).  Not together with level_weights (ValueError).
+
     Minimal observation mode (the reference's EnvironmentConfig.observation_mode = MINIMAL, config.py:17-20):
     observation_mode="minimal" makes `obs` the reference's small observation (npp_environment.py:2232-2270): minimal_observation
     [N, 40] f32 (compute_minimal_observation, observation_processor.py:505-567: 12 physics, 8 path guidance, 4 mines x 4, 4
@@ -136,8 +143,13 @@ class NppVecEnvironment:
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
-                 augmentation_seed=None):
+                 augmentation_seed=None, checkpoint_slots=0):
         assert output in ("torch", "numpy")
+        if int(checkpoint_slots) < 0:
+            raise ValueError("checkpoint_slots must be >= 0")
+        if checkpoint_slots and level_weights is not None:
+            raise ValueError("checkpoint_slots with level_weights: with the level pool on, levels move on the device and a "
+                             "checkpoint record's level can no longer be matched to its env (DESIGN.md 16)")
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         self._minimal = spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -224,6 +236,12 @@ class NppVecEnvironment:
             self._obs_names = [k for k in self._obs_names if k not in ("player_frame", "global_view")]   # (numpy: the clean frames stay on the device)
             if not hasattr(self, "_host_stack"):
                 self._host_stack = {}
+        self.checkpoint_slots = int(checkpoint_slots)
+        if self.checkpoint_slots:
+            self._b.archive_create(self.checkpoint_slots)
+            with self._b._ctx():
+                self._env_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self._b.device)
+                self._obs_flags = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
 
     # -- helpers ------------------------------------------------------------------------------------------------
     def _produce(self, reset_all=False):
@@ -326,6 +344,9 @@ class NppVecEnvironment:
                  reproduce, bit for bit); otherwise c (or c["action_sequence"] / c.action_sequence) is the action sequence to
                  replay from the spawn -- one sequence for every env, or an [N, K] array -- frame_skip ticks per action like
                  ActionReplayer.replay_to_checkpoint; c.source_frame_skip / c["source_frame_skip"] overrides the tick count.
+                 c = {"slots": slot_ids} (checkpoint_slots > 0) restarts every env from the checkpoint archive: env e from slot
+                 slot_ids[e]; with -1, or where the restore's status is not 0 (empty slot, another level, out of range), the env
+                 does an ordinary spawn reset.  info = {"checkpoint_replay": False, "restored": bool [N], "restore_status": i32 [N]}.
                  Other keys of the reference (skip_map_load, new_level, map_name) concern its map loader and are ignored."""
         if seed is not None:
             self._rng = np.random.default_rng(seed)
@@ -338,7 +359,11 @@ class NppVecEnvironment:
                 self._b.set_frame_augmentation(True, *self._aug_cfg, seed=int(seed))
         ckpt = (options or {}).get("checkpoint")
         info = {}
-        if isinstance(ckpt, str):
+        if isinstance(ckpt, dict) and "slots" in ckpt:
+            self._b.reset()
+            status = self._archive_restore(ckpt["slots"])
+            info = {"checkpoint_replay": False, "restored": self._host(status == 0), "restore_status": self._host(status)}
+        elif isinstance(ckpt, str):
             if ckpt != "snapshot":
                 raise ValueError('options["checkpoint"]: "snapshot", an action sequence, or an object with .action_sequence')
             self._b.restore()
@@ -406,6 +431,62 @@ class NppVecEnvironment:
     def snapshot(self):
         """Save the state of every env on the device (one slot); reset(options={"checkpoint": "snapshot"}) restores it."""
         self._b.snapshot()
+
+    # -- checkpoint archive (DESIGN.md 16) ------------------------------------------------------------------------
+    def _host(self, t):
+        return t if self.output == "torch" else t.cpu().numpy()
+
+    def _slot_list(self, slot_ids, what):
+        """slot_ids [N] as the `slots` argument of the batch's archive calls (a tensor stays on the device)."""
+        if not self.checkpoint_slots:
+            raise RuntimeError("%s: this env was created without checkpoint_slots (no checkpoint archive)" % what)
+        if isinstance(slot_ids, torch.Tensor):
+            with self._b._ctx():
+                slot_ids = slot_ids.to(device=self._b.device, dtype=torch.int32)
+        else:
+            slot_ids = np.asarray(slot_ids)
+        if slot_ids.ndim != 1 or len(slot_ids) != self.num_envs:
+            raise ValueError("%s: slot_ids must be [num_envs]" % what)
+        return slot_ids
+
+    def _archive_restore(self, slot_ids):
+        slots = self._slot_list(slot_ids, "checkpoint restore")
+        envs = self._env_ids if isinstance(slots, torch.Tensor) else np.arange(self.num_envs, dtype=np.int32)
+        return self._b.archive_restore(envs, slots, status=True)
+
+    def archive_store(self, slot_ids):
+        """Store env e's state in slot slot_ids[e] of the checkpoint archive ([N]; -1 = do not store; an int32 CUDA tensor stays
+        on the device, an array is checked for a slot that comes twice).  Returns the status i32 [N]: 0 stored, 1 skipped,
+        4 slot out of range."""
+        slots = self._slot_list(slot_ids, "archive_store")
+        envs = self._env_ids if isinstance(slots, torch.Tensor) else np.arange(self.num_envs, dtype=np.int32)
+        return self._host(self._b.archive_store(envs, slots, status=True))
+
+    def archive_meta(self):
+        """The archive's per-slot rows (NppBatch.archive_meta): CUDA views named by column, for a selection rule in torch."""
+        return self._b.archive_meta()
+
+    def restart(self, slot_ids):
+        """Between two steps: env e restarts from slot slot_ids[e] of the checkpoint archive; -1 leaves it alone.  The usual use
+        follows a step whose auto-reset put the finished envs at their spawn: restart(where(done, chosen, -1)).  Returns the
+        observation dict of all envs: the rows of untouched envs (and of envs whose slot was empty, of another level or out of
+        range) equal what the preceding step() / reset() returned, the rows of restarted envs show the restored state; the
+        step's reward, terminated, truncated and info stay as they were returned.
+        Raises NotImplementedError with frame stacking or frame augmentation: the rings and the draw counters advance per
+        observation, so a second observation of the untouched envs is not neutral there -- use
+        reset(options={"checkpoint": {"slots": slot_ids}}), which re-pads every stack."""
+        if self._vk or self._sk or self._aug:
+            raise NotImplementedError("restart() with frame stacking / frame augmentation: the frame rings and the augmentation's "
+                                      "draw counters advance per observation; use reset(options={'checkpoint': {'slots': ...}})")
+        b = self._b
+        status = self._archive_restore(slot_ids)
+        b.observe(flags_out=self._obs_flags)
+        with b._ctx():   # the flags of restarted envs describe the restored state; the others keep the step's
+            b.flags.copy_(torch.where(status == 0, self._obs_flags, b.flags))
+        self._produce()
+        if self.output == "torch":
+            return self._with_graph(self._obs(b.out.t))
+        return self._with_graph(self._obs(b.to_host(self._obs_names)))
 
     def action_space_sample(self):
         """uint8 [N] uniform actions from the generator reset(seed=...) seeds."""
@@ -506,13 +587,15 @@ class NppEnvironment:
     throughput.  Frame stacking takes NppVecEnvironment's arguments; stacked keys come without the batch dimension
     (player_frame (K, 84, 84, 1), game_state (K, 41)).  observation_mode="minimal": NppVecEnvironment's minimal mode
     (minimal_observation (40,), action_mask (6,) and the pass-through scalars; no terminal minimal observation).
-    enable_augmentation / augmentation_p / augmentation_intensity / augmentation_seed: NppVecEnvironment's frame augmentation."""
+    enable_augmentation / augmentation_p / augmentation_intensity / augmentation_seed: NppVecEnvironment's frame augmentation.
+    checkpoint_slots / archive_store(slot) / reset(options={"checkpoint": {"slots": [slot]}}): NppVecEnvironment's checkpoint archive."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
-                 enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None):
+                 enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
+                 checkpoint_slots=0):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -535,7 +618,8 @@ class NppEnvironment:
                                     frame_stack_padding_type=frame_stack_padding_type,
                                     enable_graph_observations=enable_graph_observations, observation_mode=observation_mode,
                                     enable_augmentation=enable_augmentation, augmentation_p=augmentation_p,
-                                    augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed)
+                                    augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed,
+                                    checkpoint_slots=checkpoint_slots)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -555,6 +639,11 @@ class NppEnvironment:
     def reset(self, seed=None, options=None):
         obs, info = self._v.reset(seed=seed, options=options)
         return self._unbatch(obs), info
+
+    def archive_store(self, slot):
+        """Store the current state in slot `slot` of the checkpoint archive (checkpoint_slots > 0); returns the status (0 =
+        stored).  reset(options={"checkpoint": {"slots": [slot]}}) restarts from it."""
+        return int(self._v.archive_store(np.array([int(slot)], dtype=np.int32))[0])
 
     def step(self, action):
         obs, rew, term, trunc, info = self._v.step(np.array([int(action)], dtype=np.uint8))
