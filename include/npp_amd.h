@@ -328,7 +328,8 @@ int npp_entity_checksum(npp_handle h, int env0, int count, double *out);
 
 /* Go-Explore style checkpoints (state_checkpoint.py / action_replayer.py in the reference restore a state by
  * reset + replaying the action sequence and validating |dpos| < 0.01 px).  Here a checkpoint is a raw copy of the
- * SoA state of ALL envs kept on the device (one slot per handle): npp_snapshot stores it, npp_restore puts it back for
+ * state of ALL envs kept on the device (one slot per handle; inside, one record per env in the checkpoint archive's layout,
+ * below, moved by the archive's kernel): npp_snapshot stores it, npp_restore puts it back for
  * the envs whose mask byte is non-zero (NULL = all).  The env -> level assignment must not have changed in between (draws of the
  * level pool are part of the state: the snapshot holds every env's level, draw count and truncation limit, and once a pool has been
  * on since npp_load_levels npp_restore puts them back together with the state). */
@@ -340,8 +341,8 @@ int npp_restore(npp_handle h, const uint8_t *env_mask);
  * on the same level, many times; npp_snapshot's single slot lets env e go back only to what env e itself was.  The archive holds
  * n_slots records of ONE env's state each -- everything npp_restore carries for an env: the double and word planes, the entity
  * words, the spatial-context cache row, the zoo block, the reachability key + cache row (or a "none" marker when the record was
- * stored before the first npp_reachability), the truncation limit and the level -- as one contiguous record whose size follows
- * from the loaded level set (npp_archive_record_bytes).
+ * stored before the first npp_reachability), the truncation limit, the level and the level pool's draw count (which only
+ * npp_restore puts back) -- as one contiguous record whose size follows from the loaded level set (npp_archive_record_bytes).
  * npp_archive_create(h, n_slots): allocates it (empty); 0 frees it; < 0 is NPP_ERR_INVALID; needs levels loaded; a failed
  *   allocation is NPP_ERR_HIP and leaves the previous archive in place.  npp_load_levels drops the archive.
  * npp_archive_store / npp_archive_restore(h, d_envs, d_slots, count, d_status): d_envs / d_slots are DEVICE arrays i32[count],

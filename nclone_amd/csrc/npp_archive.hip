@@ -1,10 +1,10 @@
-// npp_archive.hip -- the checkpoint archive's two kernels (include/npp_amd.h, npp_archive_store / npp_archive_restore): entry i of
-// the device lists moves the state of env envs[i] into slot slots[i] (store) or back (restore).  One wavefront per entry: the
-// strided [plane][n] planes go one plane per lane, the contiguous rows (zoo block, spatial-context cache, reachability row) and
-// the record go over consecutive lanes, so the slot side of an entry is one contiguous stream.  Everything that decides an entry
-// (the two list values, the slot's "stored" word and level) is wave-uniform; lane 0 writes the status and the meta row.  An entry
-// whose status is not 0 reads only the list values (and, restore, the slot's meta and level words once both indices are known
-// to be in range) and writes only its status.
+// npp_archive.hip -- the two kernels that move one env's state between the live planes and a record (npp_archive.hpp): entry i
+// moves env envs[i] into record slots[i] (store) or back (restore); without lists entry i is env i and record i, under an optional
+// env mask (the snapshot slot).  One wavefront per entry: the strided [plane][n] planes go one plane per lane, the contiguous
+// rows (zoo block, spatial-context cache, reachability row) and the record go over consecutive lanes, so the record side of an
+// entry is one contiguous stream.  Everything that decides an entry (the two list values or the mask byte, the slot's "stored"
+// word and level) is wave-uniform; lane 0 writes the status and the meta row.  An entry whose status is not 0 reads only the list
+// values (and, restore, the slot's meta and level words once both indices are known to be in range) and writes only its status.
 #include <hip/hip_runtime.h>
 
 #include "npp_archive.hpp"
@@ -19,7 +19,9 @@ template <bool STORE> __global__ __launch_bounds__(256) void npp_archive_kernel(
     const int i = blockIdx.x * ENTRIES_PER_BLOCK + (threadIdx.x >> 6);
     if (i >= a.count) return;
     const ArchiveLayout &L = a.lay;
-    const int env = a.envs[i], slot = a.slots[i];
+    int env = i, slot = i;
+    if (a.envs) { env = a.envs[i]; slot = a.slots[i]; }
+    else if (a.mask && a.mask[i] == 0) env = -1;
     uint32_t *rec = nullptr;
     int st = ARCHIVE_DONE;
     if (env < 0 || slot < 0) {
@@ -29,8 +31,8 @@ template <bool STORE> __global__ __launch_bounds__(256) void npp_archive_kernel(
     } else {
         rec = a.rec + (size_t)slot * L.words;
         if (!STORE) {
-            if (a.meta_i32[(size_t)slot * ARCHIVE_META_I32] == 0) st = ARCHIVE_EMPTY;
-            else if ((int32_t)rec[L.off_tail + 1] != a.env_level[env]) st = ARCHIVE_LEVEL_MISMATCH;
+            if (a.meta_i32 && a.meta_i32[(size_t)slot * ARCHIVE_META_I32] == 0) st = ARCHIVE_EMPTY;
+            else if (!a.level_out && (int32_t)rec[L.off_tail + 1] != a.env_level[env]) st = ARCHIVE_LEVEL_MISMATCH;
         }
     }
     if (lane == 0 && a.status) a.status[i] = st;
@@ -70,23 +72,29 @@ template <bool STORE> __global__ __launch_bounds__(256) void npp_archive_kernel(
             rec[L.off_tail] = (uint32_t)a.trunc[env];
             rec[L.off_tail + 1] = (uint32_t)level;
             rec[L.off_tail + 2] = reach ? 1u : 0u;
-            // the meta row, with npp_dump_state's decode
-            const double x = a.f64[F_X * N + e], y = a.f64[F_Y * N + e];
-            double *mf = a.meta_f64 + (size_t)slot * ARCHIVE_META_F64;
-            mf[0] = x; mf[1] = y; mf[2] = a.f64[F_VX * N + e]; mf[3] = a.f64[F_VY * N + e];
-            const int sw = a.hdr[level].obs_switch;
-            int sw_state = 2;
-            if (sw >= 0) sw_state = (a.ent[(size_t)(sw >> 4) * N + e] >> ((sw & 15) * 2)) & 3;
-            int32_t *mi = a.meta_i32 + (size_t)slot * ARCHIVE_META_I32;
-            mi[1] = level;
-            mi[2] = (int32_t)(a.u32[U_D * N + e] & 0xffffu);
-            mi[3] = (int32_t)floor(x / 24.0);
-            mi[4] = (int32_t)floor(y / 24.0);
-            mi[5] = sw_state != 1;
-            mi[0] = 1;
+            rec[L.off_tail + 3] = a.draws[env];
+            if (a.meta_i32) {   // the meta row, with npp_dump_state's decode
+                const double x = a.f64[F_X * N + e], y = a.f64[F_Y * N + e];
+                double *mf = a.meta_f64 + (size_t)slot * ARCHIVE_META_F64;
+                mf[0] = x; mf[1] = y; mf[2] = a.f64[F_VX * N + e]; mf[3] = a.f64[F_VY * N + e];
+                const int sw = a.hdr[level].obs_switch;
+                int sw_state = 2;
+                if (sw >= 0) sw_state = (a.ent[(size_t)(sw >> 4) * N + e] >> ((sw & 15) * 2)) & 3;
+                int32_t *mi = a.meta_i32 + (size_t)slot * ARCHIVE_META_I32;
+                mi[1] = level;
+                mi[2] = (int32_t)(a.u32[U_D * N + e] & 0xffffu);
+                mi[3] = (int32_t)floor(x / 24.0);
+                mi[4] = (int32_t)floor(y / 24.0);
+                mi[5] = sw_state != 1;
+                mi[0] = 1;
+            }
         }
     } else {
-        if (lane == 0) a.trunc[env] = (int32_t)rec[L.off_tail];
+        if (lane == 0) {
+            if (a.trunc) a.trunc[env] = (int32_t)rec[L.off_tail];
+            if (a.level_out) a.level_out[env] = (int32_t)rec[L.off_tail + 1];
+            if (a.draws) a.draws[env] = rec[L.off_tail + 3];
+        }
         if (a.reach_key) {
             // "reset + replay" (base_environment.py:1769-1789): the path calculator's per-episode dictionary is empty afterwards
             if (lane == 0 && a.reach_last_episode) a.reach_last_episode[env] = 0xffffffffu;

@@ -73,7 +73,7 @@ struct EnvState {
     DevBuf<uint32_t> u32;           // [NU32][n]
     DevBuf<int32_t> level, trunc;   // level and truncation limit (host mirrors: npp_handle_s::env_level / trunc)
     DevBuf<uint8_t> mask;           // a caller's env mask, copied for a launch
-    DevBuf<float> sc;               // [48][n] spatial-context cache
+    DevBuf<float> sc;               // [n][48] spatial-context cache
     DevBuf<uint32_t> count;         // level pool draw counts
 };
 
@@ -124,18 +124,12 @@ struct LevelSet {
     DevBuf<double> pool_cdf;            // [n_levels] (level pool)
 };
 
-// The snapshot slot (npp_snapshot / npp_restore): one mirror per live buffer, sized like it
+// The snapshot slot (npp_snapshot / npp_restore): one record per env in the checkpoint archive's layout (npp_archive.hpp), written
+// and read by its kernels, record e for env e
 struct Snapshot {
-    DevBuf<double> f64;
-    DevBuf<uint32_t> u32, ent;
-    DevBuf<float> sc;
-    DevBuf<int32_t> level, trunc;   // (level pool) each env's level, draw count and truncation limit go with its state
-    DevBuf<uint32_t> count;
-    DevBuf<double> zoo;             // the zoo block's head words 3..7 carry the repositioning of npp_set_entity_pos
-    DevBuf<uint32_t> rkey;          // the cached reachability vector is part of what the next observation returns
-    DevBuf<float> rcache;
-    bool reach = false;             // the slot holds a reachability cache
-    std::vector<uint8_t> ovr;       // npp_handle_s::ovr at npp_snapshot
+    ArchiveLayout lay;
+    DevBuf<uint32_t> rec;           // [n][lay.words]
+    std::vector<uint8_t> ovr;       // npp_handle_s::ovr at npp_snapshot (the records' zoo block heads carry the repositioning itself)
     unsigned long long gen = ~0ull;   // npp_handle_s::assign_gen at npp_snapshot
 };
 
@@ -754,7 +748,7 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     a.reset_fresh = 1;
     a.fast_reset = 0;   // (base_args carries the auto-reset's NPP_FLAG_FAST_RESET) a new level is a Simulator.reset
     HIP_TRY(h, launch_reset(a, h->stream));
-    if (L.reach.key) HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, L.reach.key.get(), L.reach.cache.get(), L.reach.miss(), h->stream));
+    if (L.reach.key) HIP_TRY(h, launch_reach_drop(a, L.reach.key.get(), L.reach.miss(), h->stream));
     if (out) {
         KernelArgs o = base_args(h);
         o.n_ticks = 0;
@@ -768,11 +762,28 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     return NPP_OK;
 }
 
-// snapshot: `snap` <- a copy of `live` on the stream, (re)allocated when the live buffer's size differs from the copy's
-template <class T> hipError_t mirror(DevBuf<T> &snap, const DevBuf<T> &live, hipStream_t st) {
-    if (snap.size() != live.size())
-        if (hipError_t e = snap.alloc(live.size())) return e;
-    return hipMemcpyAsync(snap.get(), live.get(), live.bytes(), hipMemcpyDeviceToDevice, st);
+ArchiveLayout record_layout(const LevelSet &L) { return archive_layout(L.n_words_max, L.zoo ? L.zoo_words : 0); }
+
+// the live state the record kernels (npp_archive.hip) move, for records laid out by `lay`; the caller fills in which entries and
+// records, and nulls what a restore is to leave alone
+ArchiveArgs record_args(npp_handle h, const ArchiveLayout &lay) {
+    const LevelSet &L = h->ls;
+    ArchiveArgs a{};
+    a.lay = lay;
+    a.n = h->n;
+    a.f64 = h->env.f64.get();
+    a.u32 = h->env.u32.get();
+    a.ent = L.ent.get();
+    a.sc = h->env.sc.get();
+    a.zoo = lay.zoo_words ? L.zoo.get() : nullptr;
+    a.trunc = h->env.trunc.get();
+    a.draws = h->env.count.get();
+    a.env_level = h->env.level.get();
+    a.hdr = L.hdr.get();
+    a.reach_key = L.reach.key.get();
+    a.reach_cache = L.reach.cache.get();
+    a.reach_last_episode = L.reach.last_episode.get();
+    return a;
 }
 
 }  // namespace
@@ -841,22 +852,15 @@ int npp_snapshot(npp_handle h) {
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_snapshot: no levels loaded");
     ON_DEVICE_JOINED(h);
     Snapshot &s = h->snap;
-    const EnvState &v = h->env;
-    const LevelSet &L = h->ls;
-    HIP_TRY(h, mirror(s.f64, v.f64, h->stream));
-    HIP_TRY(h, mirror(s.u32, v.u32, h->stream));
-    HIP_TRY(h, mirror(s.ent, L.ent, h->stream));
-    HIP_TRY(h, mirror(s.sc, v.sc, h->stream));
-    HIP_TRY(h, mirror(s.level, v.level, h->stream));
-    HIP_TRY(h, mirror(s.count, v.count, h->stream));
-    HIP_TRY(h, mirror(s.trunc, v.trunc, h->stream));
-    if (L.zoo) HIP_TRY(h, mirror(s.zoo, L.zoo, h->stream));
-    s.reach = false;
-    if (L.reach.key) {
-        HIP_TRY(h, mirror(s.rkey, L.reach.key, h->stream));
-        HIP_TRY(h, mirror(s.rcache, L.reach.cache, h->stream));
-        s.reach = true;
+    const ArchiveLayout lay = record_layout(h->ls);
+    if (!s.rec || s.lay.n_words_max != lay.n_words_max || s.lay.zoo_words != lay.zoo_words) {
+        HIP_TRY(h, s.rec.alloc((size_t)h->n * lay.words));
+        s.lay = lay;
     }
+    ArchiveArgs a = record_args(h, lay);   // identity mode: record e <- env e, no meta rows
+    a.n_slots = a.count = h->n;
+    a.rec = s.rec.get();
+    HIP_TRY(h, launch_archive_store(a, h->stream));
     s.ovr = h->ovr;
     s.gen = h->assign_gen;
     return NPP_OK;
@@ -865,24 +869,23 @@ int npp_snapshot(npp_handle h) {
 int npp_restore(npp_handle h, const uint8_t *env_mask) {
     if (!h) return NPP_ERR_INVALID;
     const Snapshot &s = h->snap;
-    if (!s.f64 || s.gen != h->assign_gen) return fail(h, NPP_ERR_STATE, "npp_restore: no snapshot for the current level assignment");
+    if (!s.rec || s.gen != h->assign_gen) return fail(h, NPP_ERR_STATE, "npp_restore: no snapshot for the current level assignment");
     ON_DEVICE_JOINED(h);
-    const LevelSet &L = h->ls;
-    EnvState &v = h->env;
-    KernelArgs a = base_args(h);
+    ArchiveArgs a = record_args(h, s.lay);   // identity mode: env e <- record e under the mask
+    a.n_slots = a.count = h->n;
+    a.rec = s.rec.get();
     if (env_mask) {
-        HIP_TRY(h, hipMemcpyAsync(v.mask.get(), env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-        a.reset_mask = v.mask.get();
+        HIP_TRY(h, hipMemcpyAsync(h->env.mask.get(), env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+        a.mask = h->env.mask.get();
     }
-    HIP_TRY(h, launch_restore(a, s.f64.get(), s.u32.get(), s.ent.get(), s.sc.get(), L.zoo ? s.zoo.get() : nullptr, h->stream));
-    if (L.reach.key)   // no cache in the snapshot (taken before the first npp_reachability): the restored envs start without one
-        HIP_TRY(h, launch_reach_restore(a, s.reach ? s.rkey.get() : nullptr, s.rcache.get(), L.reach.key.get(), L.reach.cache.get(),
-                                        L.reach.miss(), h->stream));
     if (h->pool.ever) {   // the pool changed levels since npp_load_levels: the snapshot's levels come back with the state
-        HIP_TRY(h, launch_pool_restore(h->n, a.reset_mask, s.level.get(), s.count.get(), s.trunc.get(), v.level.get(), v.count.get(),
-                                       v.trunc.get(), h->stream));
+        a.level_out = h->env.level.get();
         h->pool.dirty = true;
+    } else {              // levels, draw counts and the live truncation limits are as they were at npp_snapshot or set since
+        a.trunc = nullptr;
+        a.draws = nullptr;
     }
+    HIP_TRY(h, launch_archive_restore(a, h->stream));
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));
     // the restored zoo blocks carry the repositioning flags / coordinates of the snapshot (head words 3..7): the host's
     // view of them (which decides whether the zoo kernels run) is restored with them
@@ -913,11 +916,8 @@ int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_env
     if (!h->ar.n_slots) return fail(h, NPP_ERR_STATE, std::string(who) + ": no archive (npp_archive_create)");
     if (int rc = archive_refusal(h, who)) return rc;
     ON_DEVICE_JOINED(h);
-    const LevelSet &L = h->ls;
-    Archive &A = h->ar;
-    ArchiveArgs a;
-    a.lay = A.lay;
-    a.n = h->n;
+    const Archive &A = h->ar;
+    ArchiveArgs a = record_args(h, A.lay);
     a.n_slots = A.n_slots;
     a.count = count;
     a.envs = d_envs;
@@ -926,17 +926,7 @@ int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_env
     a.rec = A.rec.get();
     a.meta_f64 = A.meta_f64.get();
     a.meta_i32 = A.meta_i32.get();
-    a.f64 = h->env.f64.get();
-    a.u32 = h->env.u32.get();
-    a.ent = L.ent.get();
-    a.sc = h->env.sc.get();
-    a.zoo = A.lay.zoo_words ? L.zoo.get() : nullptr;
-    a.trunc = h->env.trunc.get();
-    a.env_level = h->env.level.get();
-    a.hdr = L.hdr.get();
-    a.reach_key = L.reach.key.get();
-    a.reach_cache = L.reach.cache.get();
-    a.reach_last_episode = L.reach.last_episode.get();
+    if (!store) a.draws = nullptr;   // (the pool is refused: a restored env keeps its draw count)
     HIP_TRY(h, store ? launch_archive_store(a, h->stream) : launch_archive_restore(a, h->stream));
     // a restored env takes the record's truncation limit on the device: the host mirror is read back where a host path needs it
     if (!store && count > 0) h->pool.dirty = true;
@@ -956,7 +946,7 @@ int npp_archive_create(npp_handle h, int n_slots) {
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_archive_create: no levels loaded");
     if (int rc = archive_refusal(h, "npp_archive_create")) return rc;
     Archive A;   // complete or not at all: a failed allocation leaves the previous archive in place
-    A.lay = archive_layout(h->ls.n_words_max, h->ls.zoo ? h->ls.zoo_words : 0);
+    A.lay = record_layout(h->ls);
     const size_t S = (size_t)n_slots;
     if (A.rec.alloc(S * A.lay.words) != hipSuccess || A.meta_f64.alloc(S * ARCHIVE_META_F64) != hipSuccess ||
         A.meta_i32.alloc(S * ARCHIVE_META_I32) != hipSuccess) {
@@ -1127,8 +1117,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     HIP_TRY(h, hipMemset(next.ent.get(), 0, next.ent.bytes()));
     h->ls = std::move(next);
     h->ar = Archive();   // the checkpoint archive's records were laid out for the old set
-    // the snapshot planes of the old set's per-env buffers go with it (the snapshot no longer matches assign_gen)
-    h->snap.zoo.reset(); h->snap.rkey.reset(); h->snap.rcache.reset(); h->snap.reach = false;
+    h->snap = Snapshot();   // likewise
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
     h->pool.w.clear();
     h->ovr.assign(h->n, 0);
@@ -1169,7 +1158,7 @@ int npp_assign_levels(npp_handle h, const int32_t *env_ids, const int32_t *level
         KernelArgs a = base_args(h);
         HIP_TRY(h, hipMemcpy(h->env.mask.get(), mask.data(), (size_t)h->n, hipMemcpyHostToDevice));
         a.reset_mask = h->env.mask.get();
-        HIP_TRY(h, launch_reach_restore(a, nullptr, nullptr, r.key.get(), r.cache.get(), r.miss(), h->stream));
+        HIP_TRY(h, launch_reach_drop(a, r.key.get(), r.miss(), h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     if (h->dyn_trunc)

@@ -157,9 +157,6 @@ inline size_t lds_bytes(uint32_t hot_cap, int n_words_max, int envs_per_block, i
 
 hipError_t launch_step(const KernelArgs &a, hipStream_t s);
 hipError_t launch_reset(const KernelArgs &a, hipStream_t s);
-// per-env copy of every state plane from `src` into the live state (a.reset_mask selects envs; NULL = all)
-hipError_t launch_restore(const KernelArgs &a, const double *src_f64, const uint32_t *src_u32, const uint32_t *src_ent,
-                          const float *src_sc, const double *src_zoo, hipStream_t s);
 // stride: bytes between the frames of consecutive envs; mirror: non-zero = each frame is also written `mirror` bytes further on
 hipError_t launch_render(const KernelArgs &a, uint8_t *d_out, int centered, hipStream_t s, uint32_t stride = 84 * 84, uint32_t mirror = 0);
 // npp_stack.hip: one frame-stack push (see npp_frame_stack_push in include/npp_amd.h)
@@ -192,9 +189,6 @@ struct PoolArgs {
     uint8_t *changed;             // [n] out: 1 = the env drew another level than it played (every other byte 0)
 };
 hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s);
-// envs selected by mask (null = all): level, draw count and truncation limit <- the snapshot's
-hipError_t launch_pool_restore(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count, const int32_t *s_trunc,
-                               int32_t *level, uint32_t *count, int32_t *trunc, hipStream_t s);
 // npp_augment.hip: one augmentation call (see npp_frame_augment in include/npp_amd.h; the draw and the pixels: npp_augment.hpp)
 struct AugArgs {
     int n, k;                     // k: player_frame entries per env (the visual stack size, or 1)
@@ -248,9 +242,8 @@ struct ReachMissDev {
 hipError_t launch_reach(const KernelArgs &a, const ReachHdr *rh, const unsigned char *rblob, uint32_t *key, float *cache,
                         const ReachMissDev &md, float *out, float *sdf_out, int32_t *status, float *sw_out, float *min_out,
                         const float *sc_rows, hipStream_t s);
-// envs selected by a.reset_mask (NULL = all): key / cache <- the snapshot's, or "no cached vector" when src_key == NULL
-hipError_t launch_reach_restore(const KernelArgs &a, const uint32_t *src_key, const float *src_cache, uint32_t *key, float *cache,
-                                const ReachMissDev &md, hipStream_t s);
+// envs selected by a.reset_mask (NULL = all) lose their cached vector and their miss dictionary (a new level)
+hipError_t launch_reach_drop(const KernelArgs &a, uint32_t *key, const ReachMissDev &md, hipStream_t s);
 hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n, const int *edge, int parts, uint8_t *phase, hipStream_t s);
 hipError_t launch_spin(long long ticks, hipStream_t s);   // a bounded idle wavefront (stream calibration)
 // order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)

@@ -1945,21 +1945,6 @@ __global__ __launch_bounds__(64) void npp_reset_kernel(KernelArgs a) {
     }
 }
 
-// npp_restore: copy the snapshot planes of the masked envs back into the live state
-__global__ __launch_bounds__(256) void npp_restore_kernel(KernelArgs a, const double *sf, const uint32_t *su, const uint32_t *se,
-                                                          const float *sc, const double *sz) {
-    const int env = blockIdx.x * 256 + threadIdx.x;
-    if (env >= a.n) return;
-    if (a.reset_mask && a.reset_mask[env] == 0) return;
-    const size_t N = (size_t)a.n;
-    for (int k = 0; k < NF64; k++) a.f64[k * N + env] = sf[k * N + env];
-    for (int k = 0; k < NU32; k++) a.u32[k * N + env] = su[k * N + env];
-    for (int k = 0; k < a.n_words_max; k++) a.ent_bits[k * N + env] = se[k * N + env];
-    for (int k = 0; k < 48; k++) a.sc_cache[(size_t)env * 48 + k] = sc[(size_t)env * 48 + k];
-    if (sz && a.zoo)
-        for (int k = 0; k < a.zoo_words; k++) a.zoo[(size_t)env * a.zoo_words + k] = sz[(size_t)env * a.zoo_words + k];
-}
-
 // This file is compiled four times (build_native.py: -DNPP_TU=0..3), each translation unit instantiating the step kernels
 // of one (ZOO, MANY) pair, so that the 56 instantiations build in parallel.  TU 0 also holds the small kernels.  The
 // diagnostic -DNPP_STAMPS build is a single translation unit with everything.
@@ -2033,12 +2018,6 @@ hipError_t launch_step(const KernelArgs &a, hipStream_t s) {
         case 2: return launch_step_tu2(a, s);
         default: return launch_step_tu3(a, s);
     }
-}
-
-hipError_t launch_restore(const KernelArgs &a, const double *src_f64, const uint32_t *src_u32, const uint32_t *src_ent,
-                          const float *src_sc, const double *src_zoo, hipStream_t s) {
-    hipLaunchKernelGGL(npp_restore_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a, src_f64, src_u32, src_ent, src_sc, src_zoo);
-    return hipGetLastError();
 }
 
 hipError_t launch_reset(const KernelArgs &a, hipStream_t s) {

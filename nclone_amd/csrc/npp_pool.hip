@@ -27,26 +27,10 @@ __global__ __launch_bounds__(256) void npp_pool_draw_kernel(PoolArgs a) {
     a.changed[env] = changed;
 }
 
-__global__ __launch_bounds__(256) void npp_pool_restore_kernel(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count,
-                                                               const int32_t *s_trunc, int32_t *level, uint32_t *count, int32_t *trunc) {
-    const int env = blockIdx.x * 256 + threadIdx.x;
-    if (env >= n || (mask && mask[env] == 0)) return;
-    level[env] = s_level[env];
-    count[env] = s_count[env];
-    trunc[env] = s_trunc[env];
-}
-
 }  // namespace
 
 hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(npp_pool_draw_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_pool_restore(int n, const uint8_t *mask, const int32_t *s_level, const uint32_t *s_count, const int32_t *s_trunc,
-                               int32_t *level, uint32_t *count, int32_t *trunc, hipStream_t s) {
-    hipLaunchKernelGGL(npp_pool_restore_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, mask, s_level, s_count, s_trunc, level, count,
-                       trunc);
     return hipGetLastError();
 }
 

@@ -174,24 +174,19 @@ __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const Reach
         }
 }
 
-__global__ __launch_bounds__(256) void npp_reach_restore_kernel(KernelArgs a, const uint32_t *src_key, const float *src_cache,
-                                                                uint32_t *key, float *cache, ReachMissDev md) {
+__global__ __launch_bounds__(256) void npp_reach_drop_kernel(KernelArgs a, uint32_t *key, ReachMissDev md) {
     const int env = blockIdx.x * 256 + threadIdx.x;
     if (env >= a.n) return;
     if (a.reset_mask && !a.reset_mask[env]) return;
-    // a restored checkpoint is "reset + replay of the action sequence" in the reference (base_environment.py:1769-1789): the path
-    // calculator's dictionary is empty afterwards; a newly assigned level starts empty as well
+    // a newly assigned level starts without a cached vector and with an empty path calculator dictionary
     if (md.stamp) md.last_episode[env] = 0xffffffffu;
-    if (!src_key) { key[env] = 0u; return; }
-    key[env] = src_key[env];
-    for (int i = 0; i <= REACH_DIM; i++) cache[(size_t)env * (REACH_DIM + 1) + i] = src_cache[(size_t)env * (REACH_DIM + 1) + i];
+    key[env] = 0u;
 }
 
 }  // namespace
 
-hipError_t launch_reach_restore(const KernelArgs &a, const uint32_t *src_key, const float *src_cache, uint32_t *key, float *cache,
-                                const ReachMissDev &md, hipStream_t s) {
-    hipLaunchKernelGGL(npp_reach_restore_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a, src_key, src_cache, key, cache, md);
+hipError_t launch_reach_drop(const KernelArgs &a, uint32_t *key, const ReachMissDev &md, hipStream_t s) {
+    hipLaunchKernelGGL(npp_reach_drop_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a, key, md);
     return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 of `--reps` single launches after a warm-up, in microseconds.
 
   restore_all_us      npp_restore(NULL), the one-slot snapshot every handle has had: the yardstick
+  snapshot_us         npp_snapshot, the store of that slot
   archive_store_us    npp_archive_store of n entries (env e -> slot e)
   archive_restore_us  npp_archive_restore of n entries under a random permutation (inside each level: a slot restores only into
                       envs of its level)
@@ -71,6 +72,7 @@ def main():
     assert not b.archive_restore(ids, d_perm, status=True).any().item()
     out = {"envs": n, "levels": len(levels), "reps": args.reps, "record_bytes": b.archive_record_bytes()}
     out["restore_all_us"] = median_us(b.stream, lambda: b.restore(), args.reps, args.warmup)
+    out["snapshot_us"] = median_us(b.stream, lambda: b.snapshot(), args.reps, args.warmup)
     out["archive_store_us"] = median_us(b.stream, lambda: b.archive_store(ids, ids), args.reps, args.warmup)
     out["archive_restore_us"] = median_us(b.stream, lambda: b.archive_restore(ids, d_perm), args.reps, args.warmup)
     out["archive_restore_256_us"] = median_us(b.stream, lambda: b.archive_restore(few, few_slots), args.reps, args.warmup)
