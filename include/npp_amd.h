@@ -373,6 +373,54 @@ int npp_archive_meta_view(npp_handle h, const double **d_f64 /* [n_slots][4] */,
 int npp_archive_num_slots(npp_handle h);
 int npp_archive_record_bytes(npp_handle h);   /* 0 without an archive */
 
+/* Cell index over the checkpoint archive: Go-Explore's "best state per cell" and its count-weighted pick, decided on the device.
+ * The reference ecosystem's rule (replay/demo_checkpoint_seeder.py): one checkpoint per cell (int(x // 24), int(y // 24)), cells
+ * kept apart by switch_activated, the highest cumulative reward wins, strictly (:283-287, :427-435); no checkpoint nearer than
+ * 72 px to the exit door once the switch is on (:30, :118-153); selection by visit count (:1-13).  The archive manager itself
+ * lives in the trainer, so the bits below are this library's own definition (csrc/npp_cells.hpp).
+ *   key       k = level * 2200 + (sw * 25 + cy) * 44 + cx, cx = (int)floor(x / 24.0), cy = (int)floor(y / 24.0), sw = the exit
+ *             switch's state != 1 (npp_dump_state column 13 != 1): the meta row's own expressions.
+ *   eligible  mask byte non-zero; ninja state (column 0) 0..5; 0 <= cx < 44, 0 <= cy < 25; the score is not NaN; and NOT (sw == 1,
+ *             the level has an exit door, sqrt(dx * dx + dy * dy) < 72.0 with dx = x - door_x, dy = y - door_y) -- f64, no FMA.
+ *   score     d_score[e], larger is better; NULL: -(float)frame (fewest frames to reach the cell).  Compared as ordered bits
+ *             ob = b ^ ((b >> 31) ? 0xffffffff : 0x80000000): -0.0 below +0.0, the infinities ordinary values.
+ *   winner    of a key in one explore call: the largest ob, ties to the lowest env; it replaces the incumbent only when strictly
+ *             larger.  The winners of keys without a slot take slots n_used, n_used + 1, ... in ascending env order; one whose
+ *             slot would be >= n_slots stays empty (status 7) and leaves only its visit count.
+ *   counts    visits[k] += 1 per eligible env of every explore call (losers too); chosen[k] += 1 per env a select call sends to k.
+ *   weight    w(k) = (uint32_t)floor(1048576.0 / sqrt((double)(visits[k] + chosen[k] + 1))) for a key that holds a slot, else 0;
+ *             64-bit sums; the counts of before the select call.
+ *   draw      env e in select call number c (0 after creation, +1 per call): u = mix(mix((e << 32) | c) ^ seed) with the level
+ *             pool's splitmix64 round, T = the weight sum of the env's level, t = (u * T) >> 64; the first key of that level, in
+ *             ascending order, whose inclusive prefix sum is > t; its slot.  T == 0: -1.
+ * npp_archive_cells_create(h, enable, seed): enable != 0 needs an archive (NPP_ERR_STATE without); allocates the tables for the
+ *   loaded level set, EMPTIES the archive (every slot's `stored` becomes 0) and owns all its slots from then on; a failed allocation
+ *   is NPP_ERR_HIP and leaves the previous state in place.  enable == 0 frees the tables and leaves the records as they are.
+ *   npp_archive_create (any argument) and npp_load_levels drop the index; npp_assign_levels keeps it.
+ * npp_archive_explore(h, d_score, d_mask, d_status): d_score device f32[n] or NULL, d_mask device u8[n] or NULL (all envs), d_status
+ *   device i32[n] or NULL.  Three launches on the handle's stream (propose, assign, the archive's store kernel) after joining an
+ *   observation overlap; no synchronisation, no host copy.  Status: 0 stored (won a new or a better cell), 1 skipped (mask), 5 not
+ *   eligible, 6 lost (the incumbent or another env of this call is at least as good), 7 archive full.
+ * npp_archive_select(h, d_mask, d_slots): d_slots device i32[n] receives the drawn slot, -1 for a mask byte 0 or an env whose level
+ *   holds no cell; feed it to npp_archive_restore.  Two launches (prefix sums per level, pick); all picks of one call see the
+ *   same weights.
+ * With an index, npp_archive_store is refused (NPP_ERR_STATE: the cell index owns the slots); npp_archive_restore, npp_snapshot
+ *   and npp_restore work as before.  Explore and select are refused without an index and for the causes npp_archive_store names.
+ * npp_archive_cells_view: device arrays cell_slot i32[K] (-1 = none), cell_score f32[K], visits / chosen u32[K], K = n_levels *
+ *   2200 in key order; slot_key i32[n_slots] (-1 = unused); n_used i32[1].  Valid while the index lives.
+ * npp_archive_cell_keys_host / npp_archive_cell_pick_host: the same rule without a GPU or a handle, for tests: the keys (-1 = not
+ *   eligible by state, cell or exit filter) of `count` rows xy f64[count][2], state / switch_state i32[count] on `level` compiled
+ *   from `map`; the slots that envs[i] draw from ONE level's 2200-entry tables in select call number `call`. */
+int npp_archive_cells_create(npp_handle h, int enable, uint64_t seed);
+int npp_archive_explore(npp_handle h, const float *d_score, const uint8_t *d_mask, int32_t *d_status);
+int npp_archive_select(npp_handle h, const uint8_t *d_mask, int32_t *d_slots);
+int npp_archive_cells_view(npp_handle h, const int32_t **d_cell_slot, const float **d_cell_score, const uint32_t **d_visits,
+                           const uint32_t **d_chosen, const int32_t **d_slot_key, const int32_t **d_n_used);
+int npp_archive_cell_keys_host(const double *map, int64_t n, int level, const double *xy, const int32_t *state, const int32_t *switch_state,
+                               int count, int32_t *keys_out);
+int npp_archive_cell_pick_host(const int32_t *cell_slot, const uint32_t *visits, const uint32_t *chosen, uint64_t seed, uint32_t call,
+                               const int32_t *envs, int count, int32_t *slots_out);
+
 /* Launch geometry: lanes_per_env wavefront lanes cooperate on one environment (power of two, 1..64; 0 = choose from
  * n_envs so that the grid fills the chip), waves_per_block wavefronts share one LDS copy of a level (1..4, 0 = auto).
  * Results are bit-identical for every geometry; only speed changes. */

@@ -39,6 +39,8 @@ EXPORTS = [
     "npp_frame_augment_apply_host",
     "npp_archive_create", "npp_archive_store", "npp_archive_restore", "npp_archive_meta_view", "npp_archive_num_slots",
     "npp_archive_record_bytes",
+    "npp_archive_cells_create", "npp_archive_explore", "npp_archive_select", "npp_archive_cells_view",
+    "npp_archive_cell_keys_host", "npp_archive_cell_pick_host",
 ]
 
 
@@ -154,6 +156,13 @@ def lib():
     L.npp_archive_meta_view.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.npp_archive_num_slots.argtypes = [H]
     L.npp_archive_record_bytes.argtypes = [H]
+    L.npp_archive_cells_create.argtypes = [H, C.c_int, C.c_uint64]
+    L.npp_archive_explore.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_archive_select.argtypes = [H, C.c_void_p, C.c_void_p]
+    L.npp_archive_cells_view.argtypes = [H] + [C.POINTER(C.c_void_p)] * 6
+    L.npp_archive_cell_keys_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p]
+    L.npp_archive_cell_pick_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

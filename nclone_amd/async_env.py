@@ -89,10 +89,10 @@ class NppAsyncVecEnvironment:
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
-                 enable_augmentation=False, checkpoint_slots=0):
+                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False):
         assert output in ("torch", "numpy")
-        if checkpoint_slots:
-            raise NotImplementedError("NppAsyncVecEnvironment has no checkpoint archive (checkpoint_slots): its sub-batches are "
+        if checkpoint_slots or checkpoint_cells:
+            raise NotImplementedError("NppAsyncVecEnvironment has no checkpoint archive (checkpoint_slots / checkpoint_cells): its sub-batches are "
                                       "separate handles, and a slot restores only into envs of the handle that stored it; "
                                       "NppVecEnvironment(checkpoint_slots=...) has it")
         if enable_augmentation:

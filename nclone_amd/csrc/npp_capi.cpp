@@ -12,6 +12,7 @@
 #include "../../include/npp_amd.h"
 #include "npp_archive.hpp"
 #include "npp_augment.hpp"
+#include "npp_cells.hpp"
 #include "npp_graph.hpp"
 #include "npp_host.hpp"
 #include "npp_internal.hpp"
@@ -242,6 +243,21 @@ struct Archive {
     DevBuf<int32_t> meta_i32;     // [n_slots][ARCHIVE_META_I32], word 0 = the slot holds a record
 };
 
+// cell index over the checkpoint archive (npp_archive_cells_create, npp_cells.hip): per-(level, switch, cell) tables; while it
+// exists it owns every slot of the archive.  Sized by the loaded level set and the archive, dropped with either.
+struct Cells {
+    bool on = false;
+    uint64_t seed = 0;
+    uint32_t call = 0;                    // select calls since npp_archive_cells_create
+    DevBuf<unsigned long long> best, cdf;   // [K], K = n_levels * NPP_CELLS_PER_LEVEL
+    DevBuf<int32_t> cell_slot;            // [K]
+    DevBuf<float> cell_score;             // [K]
+    DevBuf<uint32_t> visits, chosen;      // [K]
+    DevBuf<int32_t> slot_key;             // [n_slots]
+    DevBuf<int32_t> n_used;               // [1]
+    DevBuf<int32_t> env_key, slot_of_env, iota;   // [n]
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -275,6 +291,7 @@ struct npp_handle_s {
     Minimal mini;
     FrameAug aug;
     Archive ar;
+    Cells cells;
 };
 
 
@@ -915,6 +932,7 @@ int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_env
     if (count < 0 || (count > 0 && (!d_envs || !d_slots))) return fail(h, NPP_ERR_INVALID, std::string(who) + ": bad arguments");
     if (!h->ar.n_slots) return fail(h, NPP_ERR_STATE, std::string(who) + ": no archive (npp_archive_create)");
     if (int rc = archive_refusal(h, who)) return rc;
+    if (store && h->cells.on) return fail(h, NPP_ERR_STATE, std::string(who) + ": the cell index owns the slots (npp_archive_cells_create)");
     ON_DEVICE_JOINED(h);
     const Archive &A = h->ar;
     ArchiveArgs a = record_args(h, A.lay);
@@ -941,6 +959,7 @@ int npp_archive_create(npp_handle h, int n_slots) {
     if (n_slots == 0) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));   // queued store / restore launches still read the records
         h->ar = Archive();
+        h->cells = Cells();
         return NPP_OK;
     }
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_archive_create: no levels loaded");
@@ -960,6 +979,7 @@ int npp_archive_create(npp_handle h, int n_slots) {
     HIP_TRY(h, hipMemsetAsync(A.meta_i32.get(), 0, A.meta_i32.bytes(), h->stream));
     A.n_slots = n_slots;
     h->ar = std::move(A);
+    h->cells = Cells();   // (a cell index described the slots of the old archive)
     return NPP_OK;
 }
 
@@ -981,6 +1001,129 @@ int npp_archive_meta_view(npp_handle h, const double **d_f64, const int32_t **d_
 
 int npp_archive_num_slots(npp_handle h) { return h ? h->ar.n_slots : 0; }
 int npp_archive_record_bytes(npp_handle h) { return h && h->ar.n_slots ? h->ar.lay.words * 4 : 0; }
+
+namespace {
+// what explore and select share: the refusals, the join, the tables
+int cells_args(npp_handle h, const char *who, CellArgs &a) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->cells.on) return fail(h, NPP_ERR_STATE, std::string(who) + ": no cell index (npp_archive_cells_create)");
+    if (int rc = archive_refusal(h, who)) return rc;
+    ON_DEVICE_JOINED(h);
+    const Cells &c = h->cells;
+    a = CellArgs{};
+    a.n = h->n;
+    a.n_levels = (int)h->ls.levels.size();
+    a.n_slots = h->ar.n_slots;
+    a.f64 = h->env.f64.get();
+    a.u32 = h->env.u32.get();
+    a.ent = h->ls.ent.get();
+    a.env_level = h->env.level.get();
+    a.hdr = h->ls.hdr.get();
+    a.best = c.best.get();
+    a.cell_slot = c.cell_slot.get();
+    a.cell_score = c.cell_score.get();
+    a.visits = c.visits.get();
+    a.chosen = c.chosen.get();
+    a.slot_key = c.slot_key.get();
+    a.n_used = c.n_used.get();
+    a.env_key = c.env_key.get();
+    a.slot_of_env = c.slot_of_env.get();
+    a.cdf = c.cdf.get();
+    a.seed = c.seed;
+    a.call = c.call;
+    return NPP_OK;
+}
+}  // namespace
+
+int npp_archive_cells_create(npp_handle h, int enable, uint64_t seed) {
+    if (!h) return NPP_ERR_INVALID;
+    ON_DEVICE_JOINED(h);
+    if (!enable) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // queued explore / select launches still read the tables
+        h->cells = Cells();
+        return NPP_OK;
+    }
+    if (!h->ar.n_slots) return fail(h, NPP_ERR_STATE, "npp_archive_cells_create: no archive (npp_archive_create)");
+    if (int rc = archive_refusal(h, "npp_archive_cells_create")) return rc;
+    Cells c;   // complete or not at all: a failed allocation leaves the previous state in place
+    const size_t K = h->ls.levels.size() * (size_t)NPP_CELLS_PER_LEVEL, N = (size_t)h->n;
+    if (c.best.alloc(K) != hipSuccess || c.cdf.alloc(K) != hipSuccess || c.cell_slot.alloc(K) != hipSuccess ||
+        c.cell_score.alloc(K) != hipSuccess || c.visits.alloc(K) != hipSuccess || c.chosen.alloc(K) != hipSuccess ||
+        c.slot_key.alloc((size_t)h->ar.n_slots) != hipSuccess || c.n_used.alloc(1) != hipSuccess || c.env_key.alloc(N) != hipSuccess ||
+        c.slot_of_env.alloc(N) != hipSuccess || c.iota.alloc(N) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, NPP_ERR_HIP, "npp_archive_cells_create: hipMalloc of the tables of " + std::to_string(K) + " keys failed");
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<int32_t> iota(N);
+    for (size_t e = 0; e < N; e++) iota[e] = (int32_t)e;
+    HIP_TRY(h, hipMemcpy(c.iota.get(), iota.data(), c.iota.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemsetAsync(c.best.get(), 0, c.best.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.cdf.get(), 0, c.cdf.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.cell_slot.get(), 0xff, c.cell_slot.bytes(), h->stream));   // -1
+    HIP_TRY(h, hipMemsetAsync(c.cell_score.get(), 0, c.cell_score.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.visits.get(), 0, c.visits.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.chosen.get(), 0, c.chosen.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.slot_key.get(), 0xff, c.slot_key.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.n_used.get(), 0, c.n_used.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.env_key.get(), 0xff, c.env_key.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(c.slot_of_env.get(), 0xff, c.slot_of_env.bytes(), h->stream));
+    // the index owns every slot from now on: the archive starts empty
+    HIP_TRY(h, hipMemsetAsync(h->ar.meta_f64.get(), 0, h->ar.meta_f64.bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->ar.meta_i32.get(), 0, h->ar.meta_i32.bytes(), h->stream));
+    c.on = true;
+    c.seed = seed;
+    c.call = 0;
+    h->cells = std::move(c);
+    return NPP_OK;
+}
+
+int npp_archive_explore(npp_handle h, const float *d_score, const uint8_t *d_mask, int32_t *d_status) {
+    CellArgs a;
+    if (int rc = cells_args(h, "npp_archive_explore", a)) return rc;
+    a.score = d_score;
+    a.mask = d_mask;
+    a.status = d_status;
+    HIP_TRY(h, launch_cells_propose(a, h->stream));
+    HIP_TRY(h, launch_cells_assign(a, h->stream));
+    const Archive &A = h->ar;   // the winners' states, by the kernel that writes every record and meta row
+    ArchiveArgs s = record_args(h, A.lay);
+    s.n_slots = A.n_slots;
+    s.count = h->n;
+    s.envs = h->cells.iota.get();
+    s.slots = h->cells.slot_of_env.get();
+    s.rec = A.rec.get();
+    s.meta_f64 = A.meta_f64.get();
+    s.meta_i32 = A.meta_i32.get();
+    HIP_TRY(h, launch_archive_store(s, h->stream));
+    return NPP_OK;
+}
+
+int npp_archive_select(npp_handle h, const uint8_t *d_mask, int32_t *d_slots) {
+    if (h && !d_slots) return fail(h, NPP_ERR_INVALID, "npp_archive_select: d_slots must be non-NULL");
+    CellArgs a;
+    if (int rc = cells_args(h, "npp_archive_select", a)) return rc;
+    a.mask = d_mask;
+    a.slots_out = d_slots;
+    HIP_TRY(h, launch_cells_cdf(a, h->stream));
+    HIP_TRY(h, launch_cells_pick(a, h->stream));
+    h->cells.call++;
+    return NPP_OK;
+}
+
+int npp_archive_cells_view(npp_handle h, const int32_t **d_cell_slot, const float **d_cell_score, const uint32_t **d_visits,
+                           const uint32_t **d_chosen, const int32_t **d_slot_key, const int32_t **d_n_used) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->cells.on) return fail(h, NPP_ERR_STATE, "npp_archive_cells_view: no cell index (npp_archive_cells_create)");
+    const Cells &c = h->cells;
+    if (d_cell_slot) *d_cell_slot = c.cell_slot.get();
+    if (d_cell_score) *d_cell_score = c.cell_score.get();
+    if (d_visits) *d_visits = c.visits.get();
+    if (d_chosen) *d_chosen = c.chosen.get();
+    if (d_slot_key) *d_slot_key = c.slot_key.get();
+    if (d_n_used) *d_n_used = c.n_used.get();
+    return NPP_OK;
+}
 
 int npp_set_launch_geometry(npp_handle h, int lanes_per_env, int waves_per_block) {
     if (!h) return NPP_ERR_INVALID;
@@ -1117,6 +1260,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     HIP_TRY(h, hipMemset(next.ent.get(), 0, next.ent.bytes()));
     h->ls = std::move(next);
     h->ar = Archive();   // the checkpoint archive's records were laid out for the old set
+    h->cells = Cells();  // (the cell index goes with the archive)
     h->snap = Snapshot();   // likewise
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
     h->pool.w.clear();

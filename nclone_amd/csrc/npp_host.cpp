@@ -7,6 +7,7 @@
 
 #include "../../include/npp_amd.h"
 #include "npp_augment.hpp"
+#include "npp_cells.hpp"
 #include "npp_minimal.hpp"
 #include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
@@ -73,6 +74,36 @@ int npp_frame_augment_apply_host(const uint8_t *frames, int count, int height, i
         for (int y = 0; y < height; y++)
             for (int x = 0; x < width; x++) out[i * E + (size_t)y * width + x] = aug_pixel(frames + i * E, height, width, P, y, x);
     }
+    return NPP_OK;
+}
+
+int npp_archive_cell_keys_host(const double *map, int64_t n, int level, const double *xy, const int32_t *state, const int32_t *switch_state,
+                                int count, int32_t *keys_out) {
+    if (!map || level < 0 || count < 0 || (count > 0 && (!xy || !state || !switch_state || !keys_out)))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_archive_cell_keys_host: bad arguments");
+    CompiledLevel L;
+    std::string err;
+    if (!compile_level(map, n, L, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_archive_cell_keys_host: " + err);
+    const bool has_door = L.obs_switch >= 0 && L.obs_door >= 0;
+    const double door_x = has_door ? L.ent_x[L.obs_door] : 0.0, door_y = has_door ? L.ent_y[L.obs_door] : 0.0;
+    for (int i = 0; i < count; i++) {
+        const int k = cell_key_in_level(state[i], switch_state[i], xy[2 * i], xy[2 * i + 1], has_door, door_x, door_y);
+        keys_out[i] = k < 0 ? -1 : level * NPP_CELLS_PER_LEVEL + k;
+    }
+    return NPP_OK;
+}
+
+int npp_archive_cell_pick_host(const int32_t *cell_slot, const uint32_t *visits, const uint32_t *chosen, uint64_t seed, uint32_t call,
+                                const int32_t *envs, int count, int32_t *slots_out) {
+    if (!cell_slot || !visits || !chosen || count < 0 || (count > 0 && (!envs || !slots_out)))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_archive_cell_pick_host: bad arguments");
+    std::vector<uint64_t> cdf(NPP_CELLS_PER_LEVEL);
+    uint64_t run = 0;
+    for (int k = 0; k < NPP_CELLS_PER_LEVEL; k++) {
+        if (cell_slot[k] >= 0) run += cell_weight(visits[k], chosen[k]);
+        cdf[k] = run;
+    }
+    for (int i = 0; i < count; i++) slots_out[i] = run ? cell_slot[cell_pick(cdf.data(), seed, (uint32_t)envs[i], call)] : -1;
     return NPP_OK;
 }
 

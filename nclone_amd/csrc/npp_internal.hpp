@@ -203,6 +203,38 @@ struct AugArgs {
     int s10;                      // intensity scale * 10
 };
 hipError_t launch_frame_augment(const AugArgs &a, hipStream_t s);
+// npp_cells.hip: the cell index over the checkpoint archive (see npp_archive_cells_create in include/npp_amd.h; the rule:
+// npp_cells.hpp).  K = n_levels * NPP_CELLS_PER_LEVEL keys.
+struct CellArgs {
+    int n, n_levels, n_slots;
+    // the live state the key and the default score are read from
+    const double *f64;            // [NF64][n]
+    const uint32_t *u32;          // [NU32][n]
+    const uint32_t *ent;          // [n_words_max][n]
+    const int32_t *env_level;     // [n]
+    const LevelHdr *hdr;          // [n_levels]
+    // the caller's arrays
+    const float *score;           // [n] or null = -(float)frame
+    const uint8_t *mask;          // [n] or null = all envs
+    int32_t *status;              // explore: [n] or null
+    int32_t *slots_out;           // select: [n]
+    // the tables
+    unsigned long long *best;     // [K] high word = ordered score bits; low word 0xffffffff = incumbent, 0xfffffffe - env = proposal; 0 = empty
+    int32_t *cell_slot;           // [K] -1 = the key has no slot
+    float *cell_score;            // [K]
+    uint32_t *visits, *chosen;    // [K]
+    int32_t *slot_key;            // [n_slots]
+    int32_t *n_used;              // [1]
+    int32_t *env_key;             // [n] propose -> assign: the env's key, -1 = masked out or not eligible
+    int32_t *slot_of_env;         // [n] assign -> store: the slot the env's state goes to, -1 = none
+    unsigned long long *cdf;      // [K] select: inclusive prefix sums of the weights inside each level
+    uint64_t seed;
+    uint32_t call;                // select call number
+};
+hipError_t launch_cells_propose(const CellArgs &a, hipStream_t s);
+hipError_t launch_cells_assign(const CellArgs &a, hipStream_t s);
+hipError_t launch_cells_cdf(const CellArgs &a, hipStream_t s);
+hipError_t launch_cells_pick(const CellArgs &a, hipStream_t s);
 // npp_graph.hip: graph observation rows (see npp_graph_observation in include/npp_amd.h; tables: npp_graph.hpp)
 struct GraphHdr;
 struct GraphArgs {

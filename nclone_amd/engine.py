@@ -103,6 +103,26 @@ def check_archive_lists(envs, slots, unique, what):
     return lists
 
 
+CELLS_PER_LEVEL = 2 * 25 * 44   # keys of the cell index per level: (switch_activated, cell_y, cell_x)
+
+
+def check_cell_arg(v, dtype, n, what):
+    """The host-side checks of a per-env argument of NppBatch.archive_explore / archive_select (no device needed): one value per
+    env; a tensor must have the dtype the kernel reads (bool counts as uint8), an array is converted.  Returns the tensor (bool
+    viewed as uint8) or a contiguous numpy array of that dtype."""
+    np_dtype = {torch.float32: np.float32, torch.uint8: np.uint8}[dtype]
+    if isinstance(v, torch.Tensor):
+        if v.dtype == torch.bool and dtype == torch.uint8:
+            v = v.view(torch.uint8)
+        if v.dtype != dtype:
+            raise TypeError("%s must be a %s tensor, not %s" % (what, str(dtype).replace("torch.", ""), v.dtype))
+    else:
+        v = np.ascontiguousarray(v, dtype=np_dtype)
+    if v.ndim != 1 or len(v) != n:
+        raise ValueError("%s must be [%d] (one value per env)" % (what, n))
+    return v
+
+
 def _device_tensor(ptr, numel, dtype, device):
     """A torch tensor over `numel` elements of device memory that the native handle owns (no copy, no ownership)."""
     typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4", torch.float64: "<f8"}[dtype]
@@ -262,7 +282,7 @@ class NppBatch:
         nat.check(self.h, self.lib.npp_load_levels(
             self.h, blob.ctypes.data_as(C.POINTER(C.c_double)), offsets.ctypes.data_as(C.POINTER(C.c_int64)), len(offsets) - 1))
         self.n_levels = len(offsets) - 1
-        self._archive_meta = None   # (the checkpoint archive goes with the level set)
+        self._archive_meta = self._archive_cells = None   # (the checkpoint archive and its cell index go with the level set)
 
     def assign_levels(self, level_ids, env_ids=None):
         lv = np.ascontiguousarray(level_ids, dtype=np.int32)
@@ -538,7 +558,7 @@ class NppBatch:
         if n_slots < 0:
             raise ValueError("archive_create: n_slots must be >= 0 (0 frees the archive)")
         nat.check(self.h, self.lib.npp_archive_create(self.h, n_slots))
-        self._archive_meta = None
+        self._archive_meta = self._archive_cells = None
 
     def archive_num_slots(self):
         return int(self.lib.npp_archive_num_slots(self.h))
@@ -598,6 +618,70 @@ class NppBatch:
             meta.update({k: ti[:, c] for c, k in enumerate(("stored", "level", "frame", "cell_x", "cell_y", "switch_activated"))})
             self._archive_meta = meta
         return self._archive_meta
+
+    # ---- cell index over the archive (include/npp_amd.h npp_archive_cells_create) ------------------------
+    def archive_cells_create(self, seed=0, enable=True):
+        """Go-Explore's cell index over the checkpoint archive: empties the archive and owns its slots from then on (archive_store
+        is refused); archive_explore keeps the best state per (level, switch, 24 px cell), archive_select draws slots by visit
+        count.  enable=False frees the tables and leaves the records.  Needs archive_create first."""
+        nat.check(self.h, self.lib.npp_archive_cells_create(self.h, 1 if enable else 0, int(seed) & (2**64 - 1)))
+        self._archive_cells = None
+
+    def _cell_arg(self, v, dtype, what):
+        """A per-env argument of the cell calls as a contiguous CUDA tensor [n] (a CUDA tensor is used where it is), or None."""
+        if v is None:
+            return None
+        v = check_cell_arg(v, dtype, self.n, what)
+        with self._ctx():
+            if isinstance(v, np.ndarray):
+                v = torch.from_numpy(v).to(self.device)
+            elif not v.is_cuda:
+                v = v.to(self.device)
+            return v.contiguous()
+
+    def archive_explore(self, score=None, mask=None, status=False):
+        """Look at every env (mask: u8 / bool [n], None = all) and keep the best state per cell in slots the index allocates.
+        score: f32 [n], larger is better; None = -(frame), the fewest frames to reach the cell.  CUDA tensors are used where
+        they are, arrays are uploaded; nothing synchronises.  status=True returns the device tensor i32 [n]: 0 stored (won a new
+        or a better cell), 1 skipped, 5 not eligible, 6 lost, 7 archive full."""
+        sc = self._cell_arg(score, torch.float32, "archive_explore: score")
+        m = self._cell_arg(mask, torch.uint8, "archive_explore: mask")
+        st = None
+        if status:
+            with self._ctx():
+                st = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        nat.check(self.h, self.lib.npp_archive_explore(self.h, ptr(sc), ptr(m), ptr(st)))
+        self._keep_archive = (sc, m)   # the launches read them in stream order
+        return st
+
+    def archive_select(self, mask=None):
+        """For every env (mask: u8 / bool [n], None = all) draw a slot among the occupied cells of the env's level, weighted by
+        1 / sqrt(visits + chosen + 1); returns the int32 CUDA tensor [n] (-1: masked out, or the level holds no cell) -- the
+        `slots` argument of archive_restore."""
+        m = self._cell_arg(mask, torch.uint8, "archive_select: mask")
+        with self._ctx():
+            slots = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        nat.check(self.h, self.lib.npp_archive_select(self.h, C.c_void_p(m.data_ptr()) if m is not None else None,
+                                                      C.c_void_p(slots.data_ptr())))
+        self._keep_archive = (m,)
+        return slots
+
+    def archive_cells(self):
+        """{"cell_slot" i32 (-1 = none), "cell_score" f32, "visits", "chosen": [n_levels, 2, 25, 44] indexed (level,
+        switch_activated, cell_y, cell_x); "slot_key" i32 [n_slots] (-1 = unused); "n_used" i32 [1]}: CUDA views (no copy) of the
+        index's tables, valid while it lives.  visits / chosen are the u32 counters seen through int32."""
+        if getattr(self, "_archive_cells", None) is None:
+            p = [C.c_void_p() for _ in range(6)]
+            nat.check(self.h, self.lib.npp_archive_cells_view(self.h, *[C.byref(x) for x in p]))
+            K, shape = self.n_levels * CELLS_PER_LEVEL, (self.n_levels, 2, 25, 44)
+            dt = (torch.int32, torch.float32, torch.int32, torch.int32)
+            cells = {k: _device_tensor(p[c].value, K, dt[c], self.device).view(shape)
+                     for c, k in enumerate(("cell_slot", "cell_score", "visits", "chosen"))}
+            cells["slot_key"] = _device_tensor(p[4].value, self.archive_num_slots(), torch.int32, self.device)
+            cells["n_used"] = _device_tensor(p[5].value, 1, torch.int32, self.device)
+            self._archive_cells = cells
+        return self._archive_cells
 
     # ---- frame stacking (include/npp_amd.h npp_set_frame_stack; the reference's FrameStackWrapper) ----------------
     def set_frame_stack(self, visual_k=0, state_k=0, padding="zero"):

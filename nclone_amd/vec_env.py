@@ -119,6 +119,10 @@ class NppVecEnvironment:
     one copy instead of replaying the action sequence; archive_meta() shows each slot's position, 24 px cell, frame, level and
     switch state to a selection rule in torch.  A restored env keeps the slot's frame count (its truncation budget continues from
     the checkpoint).  Not together with level_weights (ValueError).
+    checkpoint_cells=True (needs checkpoint_slots) puts Go-Explore's cell index over the archive: archive_explore(score)
+    keeps the best state per (level, switch_activated, 24 px cell) in slots the index allocates itself, and
+    restart_from_archive(done_mask) restarts the masked envs from slots drawn by visit count among the cells of their own level
+    (checkpoint_seed seeds the draws); archive_store is refused while the index owns the slots.
 
     Minimal observation mode (the reference's EnvironmentConfig.observation_mode = MINIMAL, config.py:17-20):
     observation_mode="minimal" makes `obs` the reference's small observation (npp_environment.py:2232-2270): minimal_observation
@@ -143,10 +147,12 @@ class NppVecEnvironment:
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
-                 augmentation_seed=None, checkpoint_slots=0):
+                 augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0):
         assert output in ("torch", "numpy")
         if int(checkpoint_slots) < 0:
             raise ValueError("checkpoint_slots must be >= 0")
+        if checkpoint_cells and not checkpoint_slots:
+            raise ValueError("checkpoint_cells needs checkpoint_slots > 0 (the cell index allocates the archive's slots)")
         if checkpoint_slots and level_weights is not None:
             raise ValueError("checkpoint_slots with level_weights: with the level pool on, levels move on the device and a "
                              "checkpoint record's level can no longer be matched to its env (DESIGN.md 16)")
@@ -242,6 +248,10 @@ class NppVecEnvironment:
             with self._b._ctx():
                 self._env_ids = torch.arange(self.num_envs, dtype=torch.int32, device=self._b.device)
                 self._obs_flags = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
+        self.checkpoint_cells = bool(checkpoint_cells)
+        self.last_restart_slots = None
+        if self.checkpoint_cells:
+            self._b.archive_cells_create(seed=checkpoint_seed)
 
     # -- helpers ------------------------------------------------------------------------------------------------
     def _produce(self, reset_all=False):
@@ -459,12 +469,19 @@ class NppVecEnvironment:
         on the device, an array is checked for a slot that comes twice).  Returns the status i32 [N]: 0 stored, 1 skipped,
         4 slot out of range."""
         slots = self._slot_list(slot_ids, "archive_store")
+        if self.checkpoint_cells:
+            raise RuntimeError("archive_store: the cell index owns the slots (checkpoint_cells=True); archive_explore() stores")
         envs = self._env_ids if isinstance(slots, torch.Tensor) else np.arange(self.num_envs, dtype=np.int32)
         return self._host(self._b.archive_store(envs, slots, status=True))
 
     def archive_meta(self):
         """The archive's per-slot rows (NppBatch.archive_meta): CUDA views named by column, for a selection rule in torch."""
         return self._b.archive_meta()
+
+    def _restart_refusal(self):
+        if self._vk or self._sk or self._aug:
+            raise NotImplementedError("restart() with frame stacking / frame augmentation: the frame rings and the augmentation's "
+                                      "draw counters advance per observation; use reset(options={'checkpoint': {'slots': ...}})")
 
     def restart(self, slot_ids):
         """Between two steps: env e restarts from slot slot_ids[e] of the checkpoint archive; -1 leaves it alone.  The usual use
@@ -475,9 +492,7 @@ class NppVecEnvironment:
         Raises NotImplementedError with frame stacking or frame augmentation: the rings and the draw counters advance per
         observation, so a second observation of the untouched envs is not neutral there -- use
         reset(options={"checkpoint": {"slots": slot_ids}}), which re-pads every stack."""
-        if self._vk or self._sk or self._aug:
-            raise NotImplementedError("restart() with frame stacking / frame augmentation: the frame rings and the augmentation's "
-                                      "draw counters advance per observation; use reset(options={'checkpoint': {'slots': ...}})")
+        self._restart_refusal()
         b = self._b
         status = self._archive_restore(slot_ids)
         b.observe(flags_out=self._obs_flags)
@@ -487,6 +502,33 @@ class NppVecEnvironment:
         if self.output == "torch":
             return self._with_graph(self._obs(b.out.t))
         return self._with_graph(self._obs(b.to_host(self._obs_names)))
+
+    def _need_cells(self, what):
+        if not self.checkpoint_cells:
+            raise RuntimeError("%s: this env was created without checkpoint_cells (no cell index)" % what)
+
+    def archive_explore(self, score=None):
+        """Go-Explore's archive update (checkpoint_cells=True): every env whose state is the best seen of its (level,
+        switch_activated, 24 px cell) is stored in the cell's slot.  score [N] f32 (a CUDA tensor stays on the device), larger is
+        better; None = the fewest frames to reach the cell.  Returns the status i32 [N]: 0 stored, 5 not eligible, 6 lost,
+        7 archive full."""
+        self._need_cells("archive_explore")
+        return self._host(self._b.archive_explore(score=score, status=True))
+
+    def archive_cells(self):
+        """The cell index's tables (NppBatch.archive_cells): CUDA views [n_levels, 2, 25, 44], slot_key and n_used."""
+        self._need_cells("archive_cells")
+        return self._b.archive_cells()
+
+    def restart_from_archive(self, mask):
+        """Between two steps: every env whose mask byte is set restarts from a slot drawn among the occupied cells of its own
+        level with weight 1 / sqrt(visits + chosen + 1) (an env whose level holds no cell is left alone) -- archive_select, then
+        restart(): its observation dict, and its NotImplementedError with frame stacking / frame augmentation.  The slots used
+        ([N] int32 CUDA tensor, -1 = none) are kept as last_restart_slots."""
+        self._need_cells("restart_from_archive")
+        self._restart_refusal()   # (before a draw is spent)
+        self.last_restart_slots = self._b.archive_select(mask)
+        return self.restart(self.last_restart_slots)
 
     def action_space_sample(self):
         """uint8 [N] uniform actions from the generator reset(seed=...) seeds."""
@@ -588,14 +630,15 @@ class NppEnvironment:
     (player_frame (K, 84, 84, 1), game_state (K, 41)).  observation_mode="minimal": NppVecEnvironment's minimal mode
     (minimal_observation (40,), action_mask (6,) and the pass-through scalars; no terminal minimal observation).
     enable_augmentation / augmentation_p / augmentation_intensity / augmentation_seed: NppVecEnvironment's frame augmentation.
-    checkpoint_slots / archive_store(slot) / reset(options={"checkpoint": {"slots": [slot]}}): NppVecEnvironment's checkpoint archive."""
+    checkpoint_slots / archive_store(slot) / reset(options={"checkpoint": {"slots": [slot]}}): NppVecEnvironment's checkpoint archive;
+    checkpoint_cells / checkpoint_seed are passed through to it."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
-                 checkpoint_slots=0):
+                 checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -619,7 +662,8 @@ class NppEnvironment:
                                     enable_graph_observations=enable_graph_observations, observation_mode=observation_mode,
                                     enable_augmentation=enable_augmentation, augmentation_p=augmentation_p,
                                     augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed,
-                                    checkpoint_slots=checkpoint_slots)
+                                    checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
+                                    checkpoint_seed=checkpoint_seed)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
