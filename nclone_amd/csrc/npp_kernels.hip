@@ -806,24 +806,32 @@ struct DepenIOZ : DepenIO {
 DEV void crush_add(DepenIO &, double, double, double) {}
 DEV void crush_add(DepenIOZ &io, double dx, double dy, double len) { io.xcr += dx; io.ycr += dy; io.clen += len; }
 
+// The loop's fp64 literals are named locals of the caller (NPP_DEPEN_CONSTS: plain constants; the register fast path
+// pins them in scalar registers ahead of its loop, see collide_vs_tiles): dk_eps = 1e-7, dk_tiny = 1e-16,
+// dk_radius = NINJA_RADIUS, dk_ceil = -0.0001 and, for the key of the closest-point search, dk_bias = 0.1.
+#define NPP_DEPEN_CONSTS \
+    double dk_eps = 0.0000001, dk_tiny = 1e-16, dk_radius = NINJA_RADIUS, dk_ceil = -0.0001, dk_bias = 0.1;
 #define NPP_DEPEN_STEP(io, m, BREAK)                                                                   \
     {                                                                                                  \
         /* the reference leaves the loop at three places (ninja.py:307, 326, 331); nothing is modified \
          * before the last of them, so the three tests are folded into one exit */                     \
         const bool none = (m).idx == 0x7fffffff; /* result == 0 */                                     \
-        const bool back_facing = ((m).idx & 1) != 0; /* result = -1 (physics.py:179) */                \
         double ddx = (io).x - (m).a;                                                                   \
         double ddy = (io).y - (m).b;                                                                   \
-        if (dabs(ddx) <= 0.0000001) { /* band-aid constants of the reference (ninja.py:313-318) */     \
+        if (dabs(ddx) <= dk_eps) { /* band-aid constants of the reference (ninja.py:313-318) */        \
             ddx = 0;                                                                                   \
             if ((io).x == 50.51197510492316 || (io).x == 49.23232124849253) ddx = -0x1p-47;            \
             if ((io).x == 49.153536108584795) ddx = 0x1p-47;                                           \
         }                                                                                              \
         double dist_sq = ddx * ddx + ddy * ddy;                                                        \
-        const bool tiny = dist_sq < 1e-16;                                                             \
+        const bool tiny = dist_sq < dk_tiny;                                                           \
         double dist = sqrt_inrange(dist_sq); /* garbage when tiny: the exit below does not look at it */ \
-        double depen_len = NINJA_RADIUS - (back_facing ? -dist : dist); /* dist * result, exactly */   \
-        if (none | tiny | (depen_len < 0.0000001)) BREAK;                                              \
+        /* dist * result, exactly (result = -1 when back facing, physics.py:179: the low bit of idx):  \
+         * dist is a square root, so its sign bit is clear, and or-ing that bit in IS the negation */  \
+        const double sdist = __hiloint2double((int)((unsigned)__double2hiint(dist) | ((unsigned)(m).idx << 31)), \
+                                              __double2loint(dist));                                   \
+        double depen_len = dk_radius - sdist;                                                          \
+        if (none | tiny | (depen_len < dk_eps)) BREAK;                                                 \
         double inv_dist = rcp_inrange(dist);                                                           \
         double norm_dx = ddx * inv_dist, norm_dy = ddy * inv_dist;                                     \
         const double depen_x = norm_dx * depen_len, depen_y = norm_dy * depen_len;                     \
@@ -837,7 +845,7 @@ DEV void crush_add(DepenIOZ &io, double dx, double dy, double len) { io.xcr += d
             (io).vx = cross_product * inv_dist_sq * ddy;                                               \
             (io).vy = cross_product * inv_dist_sq * (-ddx);                                            \
         }                                                                                              \
-        if (ddy >= -0.0001) { (io).ccount += 1; (io).cnsx += norm_dx; (io).cnsy += norm_dy; }          \
+        if (ddy >= dk_ceil) { (io).ccount += 1; (io).cnsx += norm_dx; (io).cnsy += norm_dy; }          \
         else { (io).fcount += 1; (io).fnsx += norm_dx; (io).fnsy += norm_dy; }                         \
     }
 
@@ -848,6 +856,7 @@ template <int G, typename IO>
 __device__ __noinline__ void depen_generic(TileRefs lv, int r, double gx0, double gy0, double gx1, double gy1, IO *slot) {
     IO io = *slot;
     const int c0x = cell_coord(gx0, 43), c1x = cell_coord(gx1, 43), c0y = cell_coord(gy0, 24), c1y = cell_coord(gy1, 24);
+    const NPP_DEPEN_CONSTS
     for (int it = 0; it < 32; it++) {
         Best m;
         m.key = __builtin_inf(); m.idx = 0x7fffffff; m.a = 0; m.b = 0;
@@ -865,7 +874,7 @@ __device__ __noinline__ void depen_generic(TileRefs lv, int r, double gx0, doubl
                 double a, b;
                 bool back = seg_closest(s, xc, yc, io.x, io.y, a, b);
                 double distance_sq = sq(io.x - a) + sq(io.y - b);
-                if (!back) distance_sq -= 0.1;
+                if (!back) distance_sq -= dk_bias;
                 if (distance_sq < m.key) { m.key = distance_sq; m.a = a; m.b = b; m.idx = ((base + i - i0) << 8) | (r << 1) | (back ? 1 : 0); }
             }
             base += i1 - i0;
@@ -875,6 +884,46 @@ __device__ __noinline__ void depen_generic(TileRefs lv, int r, double gx0, doubl
     }
     if (r == 0) *slot = io;
 }
+
+// The loop of the register fast path of collide_vs_tiles, written once and expanded with ARCS = true / false (a macro like
+// NPP_DEPEN_STEP, not a lambda: as a lambda the same body cost the G = 1 zoo kernels 16 B of scratch).  With ARCS false
+// cand_closest_arc and everything that feeds only it do not exist.
+#ifdef NPP_STAMPS
+#define NPP_STAMP_ITER st.acc[10] += 1;   /* iteration count (register fast path) */
+#else
+#define NPP_STAMP_ITER
+#endif
+#define NPP_FAST_DEPEN_LOOP(ARCS)                                                                                          \
+    for (int it = 0; it < 32; it++) {                                                                                      \
+        NPP_STAMP_ITER                                                                                                     \
+        /* get_single_closest_point (physics.py:131-180) over the candidate registers */                                   \
+        Best m;                                                                                                            \
+        m.key = __builtin_inf(); m.idx = 0x7fffffff; m.a = 0; m.b = 0;                                                     \
+        _Pragma("unroll")                                                                                                  \
+        for (int k = 0; k < K; k++)                                                                                        \
+            if (k == 0 || (wave_more && ((gp >> k) & 1u))) { /* slot 0 is evaluated unconditionally (masked by gp below) */ \
+                /* the reference's AABB test on the rounded box x -+ 10, y -+ 10, as exact thresholds (AABB_LO) */         \
+                bool in = ((gp >> k) & 1u) & (io.x >= cd.tx0[k]) & (io.x <= cd.tx1[k]) & (io.y >= cd.ty0[k]) & (io.y <= cd.ty1[k]); \
+                double a, b;                                                                                               \
+                bool back = cand_closest_lin(cd, k, io.x, io.y, a, b);                                                     \
+                if constexpr (ARCS)                                                                                        \
+                    if (in & ((cd.s[k] & 1u) != 0)) back = cand_closest_arc(cd.s[k], cd.x1[k], cd.y1[k], cd.x2[k], cd.y2[k], io.x, io.y, a, b); \
+                double distance_sq = sq(io.x - a) + sq(io.y - b);                                                          \
+                double key = back ? distance_sq : distance_sq - dk_bias;                                                   \
+                const int code = ((k * G + r) << 8) | (r << 1) | (back ? 1 : 0);                                           \
+                if (k == 0) {                                                                                              \
+                    /* first slot: nothing to compare with yet; a lane that is not `in` keeps key = inf / idx = none and   \
+                     * can never be the winner, so its point need not be masked */                                         \
+                    m.key = in ? key : m.key; m.idx = in ? code : m.idx; m.a = a; m.b = b;                                 \
+                } else {                                                                                                   \
+                    bool take = in & (key < m.key);                                                                        \
+                    m.key = take ? key : m.key; m.a = take ? a : m.a; m.b = take ? b : m.b;                                \
+                    m.idx = take ? code : m.idx;                                                                           \
+                }                                                                                                          \
+            }                                                                                                              \
+        group_argmin<G>(m);                                                                                                \
+        NPP_DEPEN_STEP(io, m, break)                                                                                       \
+    }
 
 // Ninja.collide_vs_tiles (ninja.py:269-379).  Returns the number of depenetrations applied.
 struct Crush { double xcr, ycr, clen; };
@@ -935,44 +984,27 @@ DEV int collide_vs_tiles(const Lv &lv, int r, Nj &n, const Cand<K> &cd, double x
     crush_in(io, cr);
     STAMP(9);   // sweep + gather setup
     if (fast) {
-        // Loop-invariant, wavefront-uniform shortcuts (scalar branches instead of exec-mask regions inside the chain):
-        // does any gathered candidate of this wavefront describe an arc / sit in a slot beyond the first?
+        // Loop-invariant, wavefront-uniform facts: does any gathered candidate of this wavefront describe an arc / sit in a
+        // slot beyond the first?  The loop is UNSWITCHED on the first of them: one body (NPP_FAST_DEPEN_LOOP), expanded with
+        // ARCS as a compile-time constant, so the straight-segment copy holds nothing of the arc path (as a run-time scalar
+        // test inside the loop only the sqrt / division of cand_closest_arc ended up behind a branch; its selects and compares
+        // stayed).  Wavefront-uniform: all lanes of a group enter and leave the same copy together.  wave_more stays a
+        // run-time test: the second slot already sits behind one scalar-mask exec region that an empty mask skips.
         bool arc_here = false;
 #pragma unroll
         for (int k = 0; k < K; k++) arc_here |= ((gp >> k) & 1u) && (cd.s[k] & 1u);
         const bool wave_arcs = __any(arc_here);
         const bool wave_more = __any((gp >> 1) != 0);
-        for (int it = 0; it < 32; it++) {
-#ifdef NPP_STAMPS
-            st.acc[10] += 1;   // iteration count (register fast path)
-#endif
-            // get_single_closest_point (physics.py:131-180) over the candidate registers
-            Best m;
-            m.key = __builtin_inf(); m.idx = 0x7fffffff; m.a = 0; m.b = 0;
-#pragma unroll
-            for (int k = 0; k < K; k++)
-                if (k == 0 || (wave_more && ((gp >> k) & 1u))) {   // slot 0 is evaluated unconditionally (masked by gp below)
-                    // the reference's AABB test on the rounded box x -+ 10, y -+ 10, as exact thresholds (AABB_LO)
-                    bool in = ((gp >> k) & 1u) & (io.x >= cd.tx0[k]) & (io.x <= cd.tx1[k]) & (io.y >= cd.ty0[k]) & (io.y <= cd.ty1[k]);
-                    double a, b;
-                    bool back = cand_closest_lin(cd, k, io.x, io.y, a, b);
-                    if (wave_arcs && (in & ((cd.s[k] & 1u) != 0))) back = cand_closest_arc(cd.s[k], cd.x1[k], cd.y1[k], cd.x2[k], cd.y2[k], io.x, io.y, a, b);
-                    double distance_sq = sq(io.x - a) + sq(io.y - b);
-                    double key = back ? distance_sq : distance_sq - 0.1;
-                    const int code = ((k * G + r) << 8) | (r << 1) | (back ? 1 : 0);
-                    if (k == 0) {
-                        // first slot: nothing to compare with yet; a lane that is not `in` keeps key = inf / idx = none and
-                        // can never be the winner, so its point need not be masked
-                        m.key = in ? key : m.key; m.idx = in ? code : m.idx; m.a = a; m.b = b;
-                    } else {
-                        bool take = in & (key < m.key);
-                        m.key = take ? key : m.key; m.a = take ? a : m.a; m.b = take ? b : m.b;
-                        m.idx = take ? code : m.idx;
-                    }
-                }
-            group_argmin<G>(m);
-            NPP_DEPEN_STEP(io, m, break)
-        }
+        // the literals of the loop, pinned in scalar registers: with machine LICM off (build_native.py) each of them would
+        // otherwise be rebuilt by two s_mov_b32 in every iteration
+        NPP_DEPEN_CONSTS
+        asm volatile("" : "+s"(dk_eps));
+        asm volatile("" : "+s"(dk_tiny));
+        asm volatile("" : "+s"(dk_radius));
+        asm volatile("" : "+s"(dk_ceil));
+        asm volatile("" : "+s"(dk_bias));
+        if (wave_arcs) { NPP_FAST_DEPEN_LOOP(true) }
+        else { NPP_FAST_DEPEN_LOOP(false) }
     } else {
 #ifdef NPP_STAMPS
         st.acc[11] += 1;   // substeps that took the LDS fallback
