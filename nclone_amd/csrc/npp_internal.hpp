@@ -24,7 +24,8 @@ struct LevelHdr {
     uint32_t off_ent_meta;  // u32[n_ent]
     uint32_t off_init_words;  // u32[n_words]
     uint32_t off_tiles;   // u8[1100]
-    uint32_t off_raster;  // u16[n_ent] draw order
+    uint32_t off_raster;  // u16[n_ent + n_mov] draw order (npp_level.hpp: raster_order); read by write_spatial_context only --
+                          // the rasteriser walks off_draw_recs
     uint32_t off_doors;   // f64[5 * n_door]
     uint32_t n_door;
     uint32_t n_seg;

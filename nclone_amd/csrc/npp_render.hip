@@ -21,6 +21,10 @@ namespace {
 
 constexpr int FW = 84, FH = 84;
 constexpr int MAX_DRAW = 160;   // drawables kept per window (discs + strokes)
+// A list that overflows its cap is cut differently by each walker, and that is part of the picture, so it stays:
+//   build_draw_list (cap GV_DRAW)           keeps the head; the ninja is dropped when the list is already full
+//   frame_build (MAX_DRAW)                  keeps the head up to MAX_DRAW - 1 and puts the ninja into the last slot
+//   npp_global_view_kernel (the set's cap)  reserves the last slot for the ninja: the head is cut to cap - 1
 
 // convex polygons of tile ids 6..9 and 18..33 in units of 12 px (shared_tile_renderer.py:50-152), n vertices then xy
 __constant__ unsigned char POLY[34][9] = {
@@ -185,20 +189,20 @@ __device__ inline void draw_extent(const Draw &d, float &cx, float &cy, float &e
     }
 }
 
-// ---- the draw list, built by the whole workgroup ---------------------------------------------------------------------
-// Drawables that can touch the window [wx0, wx1] x [wy0, wy1], in the reference's draw order (later ones overwrite:
-// cairo operator SOURCE): closed door strokes (entity_renderer.py:63-97), then the active entities grouped by type
-// (:100-150: discs of RADIUS, squares of SEMI_SIDE, oriented entities as a stroke of PLATFORMWIDTH across their normal),
-// then the ninja.  Thread t of the workgroup evaluates candidate t of every chunk of blockDim.x candidates (its level
-// table reads and its entity-bit read run in parallel with everybody else's); an ordered ballot / prefix compaction keeps
-// the draw order.
+// ---- what is drawn ------------------------------------------------------------------------------------------------------
+// The entity layer in the reference's draw order (later drawables overwrite: cairo operator SOURCE): closed door strokes
+// (entity_renderer.py:63-97), then the level's draw-order records -- the active entities grouped by type (:100-150: discs of
+// RADIUS, squares of SEMI_SIDE, oriented entities as a stroke of PLATFORMWIDTH across their normal) and the movers -- then the
+// ninja.  Three walkers go through that sequence (the workgroup-wide build_draw_list, player_frame's frame_build, the
+// global_view kernel); what a door or a record looks like and where a record's entity is now are written once, here.
+
+// what door_drawable needs to know about its caller (records do not go through it: their state comes from the caller)
 struct DrawCtx {
     const KernelArgs *a;
     const LevelHdr *H;
     int env;
     float wx0, wy0, wx1, wy1;
-    bool init;   // the level as it stands right after a reset: entity states from the level's init words, no movers, nothing
-                 // repositioned (global_view's per-level static tables)
+    bool init;   // the level as it stands right after a reset: door states from the level's init words
 };
 
 __device__ inline uint32_t ent_state_of(const KernelArgs &a, int env, int slot) {
@@ -225,42 +229,19 @@ __device__ inline bool door_drawable(const DrawCtx &c, uint32_t d, Draw &out) {
     return true;
 }
 
-__device__ inline bool entity_drawable(const DrawCtx &c, uint32_t k, Draw &out) {
-    const KernelArgs &a = *c.a;
-    const LevelHdr &H = *c.H;
-    const int env = c.env;
-    const uint16_t *order = reinterpret_cast<const uint16_t *>(a.blob + H.off_raster);
-    const uint32_t ref = order[k];
-    if (ref & 0x8000u) {   // a mover: position from the env's zoo block
-        if (c.init || !(a.zoo && H.has_zoo)) return false;
-        const double *zb = a.zoo + (size_t)env * a.zoo_words + ZOO_HEAD + (a.zoo_doors + 1) / 2;
-        const uint32_t *mov_meta = reinterpret_cast<const uint32_t *>(a.blob + H.off_mov_meta);
-        const int m = (int)(ref & 0x7fffu);
-        const float x = (float)zb[ZOO_MOV_WORDS * m], y = (float)zb[ZOO_MOV_WORDS * m + 1];
-        if (x < c.wx0 || x > c.wx1 || y < c.wy0 || y > c.wy1) return false;
-        const uint32_t mk = mov_meta[m] & 7u;
-        if (mk == MK_DRONE) out = {x, y, 7.5f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};
-        else if (mk == MK_MINI) out = {x, y, 4.f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};
-        else if (mk == MK_BOUNCE) out = {x, y, 9.f, 0.f, 0.f, (float)luma(0xE3, 0xE3, 0xE5), 2};
-        else if (mk == MK_THWUMP) out = {x, y, 9.f, 0.f, 0.f, (float)luma(0x83, 0x83, 0x84), 2};
-        else if (mk == MK_BALL) out = {x, y, 5.f, 0.f, 0.f, (float)luma(0x15, 0xA7, 0xBD), 0};
+// The drawable of a draw-order record (npp_level.hpp: draw_recs; entity_renderer.py:100-150), given the entity's position and
+// 2-bit state: the ONLY place that knows the shape, size and colour of an entity kind or a mover kind.
+__device__ inline bool rec_drawable(uint32_t info, float x, float y, uint32_t st, Draw &out) {
+    const uint32_t kind = info & 15u, type = (info >> 4) & 63u;
+    if (info & 0x8000u) {   // movers (kind = MoverKind)
+        if (kind == MK_DRONE) out = {x, y, 7.5f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};
+        else if (kind == MK_MINI) out = {x, y, 4.f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};
+        else if (kind == MK_BOUNCE) out = {x, y, 9.f, 0.f, 0.f, (float)luma(0xE3, 0xE3, 0xE5), 2};
+        else if (kind == MK_THWUMP) out = {x, y, 9.f, 0.f, 0.f, (float)luma(0x83, 0x83, 0x84), 2};
+        else if (kind == MK_BALL) out = {x, y, 5.f, 0.f, 0.f, (float)luma(0x15, 0xA7, 0xBD), 0};
         else out = {x, y, 8.f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};   // shove thwump: RADIUS wins over SEMI_SIDE
         return true;
     }
-    const uint32_t *meta = reinterpret_cast<const uint32_t *>(a.blob + H.off_ent_meta);
-    const double *ex = reinterpret_cast<const double *>(a.blob + H.off_ent_x);
-    const double *ey = reinterpret_cast<const double *>(a.blob + H.off_ent_y);
-    const int slot = (int)ref;
-    float x = (float)ex[slot], y = (float)ey[slot];
-    if (!c.init && a.zoo && (slot == H.obs_switch || slot == H.obs_door)) {   // npp_set_entity_pos
-        const double *hd = a.zoo + (size_t)env * a.zoo_words;
-        const uint32_t ovr = reinterpret_cast<const uint32_t *>(hd + 3)[0];
-        if (slot == H.obs_switch && (ovr & ZOO_OVR_SWITCH)) { x = (float)hd[4]; y = (float)hd[5]; }
-        if (slot == H.obs_door && (ovr & ZOO_OVR_DOOR)) { x = (float)hd[6]; y = (float)hd[7]; }
-    }
-    if (x < c.wx0 || x > c.wx1 || y < c.wy0 || y > c.wy1) return false;
-    const uint32_t mm = meta[slot], kind = mm & 15u, type = (mm >> 24) & 63u;
-    const uint32_t st = ent_state_ctx(c, slot);
     if (kind == EK_MINE) {             // always active; radius follows the state
         out = {x, y, st == 0 ? 4.0f : (st == 1 ? 3.5f : 4.5f), 0.f, 0.f,
                type == 1 ? (float)luma(0x9E, 0x21, 0x26) : (float)luma(0xCE, 0x41, 0x46), 0};
@@ -277,7 +258,7 @@ __device__ inline bool entity_drawable(const DrawCtx &c, uint32_t k, Draw &out) 
     else if (kind == EK_BOOST) out = {x, y, 6.f, 0.f, 0.f, (float)luma(0x66, 0x66, 0x66), 0};
     else if (kind == EK_LAUNCH || kind == EK_ONEWAY) {
         // _draw_oriented_entity: angle = atan2(nx, ny) + pi/2; end points (x +- sin(angle) R, y +- cos(angle) R)
-        const uint32_t o = (mm >> 8) & 7u;
+        const uint32_t o = (info >> 10) & 7u;
         const float dg = 0.70710678f;
         const int sx = (o == 0 || o == 1 || o == 7) ? 1 : ((o >= 3 && o <= 5) ? -1 : 0);
         const int sy = (o >= 1 && o <= 3) ? 1 : ((o >= 5) ? -1 : 0);
@@ -289,6 +270,41 @@ __device__ inline bool entity_drawable(const DrawCtx &c, uint32_t k, Draw &out) 
     return true;
 }
 
+// What an env's zoo block says about where its entities are now, loaded once per env by the walker: the block itself (movers
+// follow its head), the override word and positions of npp_set_entity_pos in the head, and which slots those can move.
+struct ZooHead {
+    const double *p;   // nullptr: no zoo
+    uint32_t ovr, has_zoo;
+    int zoo_doors;
+    int32_t obs_switch, obs_door;
+};
+__device__ inline ZooHead zoo_head_of(const KernelArgs &a, int env, uint32_t has_zoo, int32_t obs_switch, int32_t obs_door) {
+    const double *p = a.zoo ? a.zoo + (size_t)env * a.zoo_words : nullptr;
+    return {p, p ? reinterpret_cast<const uint32_t *>(p + 3)[0] : 0u, has_zoo, a.zoo_doors, obs_switch, obs_door};
+}
+// Where the entity of draw record rc is now and whether it exists at all: a mover's position comes from the env's zoo block (a
+// mover of a level without zoo is dead), an exit switch or exit door repositioned through npp_set_entity_pos comes from the zoo
+// head, everything else is where the record says.  `init`: as right after a reset -- movers are dead, nothing is repositioned
+// (z is not read).  The caller's window test follows.
+__device__ inline bool rec_place(const uint4 &rc, const ZooHead &z, bool init, float &x, float &y) {
+    const uint32_t info = rc.z;
+    const int slot = (int)(info >> 16);
+    x = __uint_as_float(rc.x); y = __uint_as_float(rc.y);
+    if (info & 0x8000u) {
+        if (init || z.p == nullptr || !z.has_zoo) return false;
+        const double *zb = z.p + ZOO_HEAD + (z.zoo_doors + 1) / 2 + ZOO_MOV_WORDS * slot;
+        x = (float)zb[0]; y = (float)zb[1];
+    } else if (!init && z.ovr) {
+        if (slot == z.obs_switch && (z.ovr & ZOO_OVR_SWITCH)) { x = (float)z.p[4]; y = (float)z.p[5]; }
+        if (slot == z.obs_door && (z.ovr & ZOO_OVR_DOOR)) { x = (float)z.p[6]; y = (float)z.p[7]; }
+    }
+    return true;
+}
+
+// ---- the draw list, built by the whole workgroup ---------------------------------------------------------------------
+// Drawables that can touch the window [wx0, wx1] x [wy0, wy1].  Thread t of the workgroup evaluates candidate t of every chunk
+// of blockDim.x candidates (its 16-byte record load and its entity-bit read run in parallel with everybody else's); an ordered
+// ballot / prefix compaction keeps the draw order.
 // ordered append of one candidate per thread (thread order = list order); s_wc: one int per wavefront
 __device__ inline void append_ordered(bool keep, const Draw &d, Draw *out, int cap, int *s_n, int *s_wc) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -308,10 +324,13 @@ __device__ inline void append_ordered(bool keep, const Draw &d, Draw *out, int c
     __syncthreads();
 }
 
-// Called by every thread of the workgroup.  On return *s_n drawables sit in out[] (visible to all threads).
-__device__ void build_draw_list(const KernelArgs &a, const LevelHdr &H, int env, double px, double py, float wx0, float wy0,
-                                float wx1, float wy1, Draw *out, int cap, int *s_n, int *s_wc) {
-    DrawCtx c{&a, &H, env, wx0, wy0, wx1, wy1, false};
+// Called by every thread of the workgroup.  On return *s_n drawables sit in out[] (visible to all threads).  `init`: the level as
+// it stands right after a reset (states from the level's init words, rec_place's init mode; env is not read).
+__device__ void build_draw_list(const KernelArgs &a, const LevelHdr &H, int env, bool init, bool with_ninja, double px, double py,
+                                float wx0, float wy0, float wx1, float wy1, Draw *out, int cap, int *s_n, int *s_wc) {
+    const DrawCtx c{&a, &H, env, wx0, wy0, wx1, wy1, init};
+    const ZooHead z = init ? ZooHead{} : zoo_head_of(a, env, H.has_zoo, H.obs_switch, H.obs_door);
+    const uint4 *recs = reinterpret_cast<const uint4 *>(a.blob + H.off_draw_recs);
     if (threadIdx.x == 0) *s_n = 0;
     __syncthreads();
     for (uint32_t d0 = 0; d0 < H.n_door; d0 += blockDim.x) {
@@ -324,10 +343,16 @@ __device__ void build_draw_list(const KernelArgs &a, const LevelHdr &H, int env,
     for (uint32_t k0 = 0; k0 < n_draw; k0 += blockDim.x) {
         Draw d = {};
         const uint32_t k = k0 + threadIdx.x;
-        const bool keep = k < n_draw && entity_drawable(c, k, d);
+        bool keep = false;
+        if (k < n_draw) {
+            const uint4 rc = recs[k];
+            float x, y;
+            if (rec_place(rc, z, init, x, y) && !(x < wx0 || x > wx1 || y < wy0 || y > wy1))
+                keep = rec_drawable(rc.z, x, y, (rc.z & 0x8000u) ? 1u : ent_state_ctx(c, (int)(rc.z >> 16)), d);
+        }
         append_ordered(keep, d, out, cap, s_n, s_wc);
     }
-    if (threadIdx.x == 0 && *s_n < cap) out[(*s_n)++] = {(float)px, (float)py, 10.f, 0.f, 0.f, 0.f, 0};   // the ninja, drawn last
+    if (with_ninja && threadIdx.x == 0 && *s_n < cap) out[(*s_n)++] = {(float)px, (float)py, 10.f, 0.f, 0.f, 0.f, 0};   // drawn last
     __syncthreads();
 }
 
@@ -399,46 +424,6 @@ struct FrameLds {
 
 static_assert(sizeof(FrameLds) <= 32768, "five workgroups per CU need <= 32 KB of LDS each");
 
-// the drawable of a draw-order record (entity_renderer.py:100-150), given the entity's position and 2-bit state
-__device__ inline bool rec_drawable(uint32_t info, float x, float y, uint32_t st, Draw &out) {
-    const uint32_t kind = info & 15u, type = (info >> 4) & 63u;
-    if (info & 0x8000u) {   // movers (kind = MoverKind)
-        if (kind == MK_DRONE) out = {x, y, 7.5f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};
-        else if (kind == MK_MINI) out = {x, y, 4.f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};
-        else if (kind == MK_BOUNCE) out = {x, y, 9.f, 0.f, 0.f, (float)luma(0xE3, 0xE3, 0xE5), 2};
-        else if (kind == MK_THWUMP) out = {x, y, 9.f, 0.f, 0.f, (float)luma(0x83, 0x83, 0x84), 2};
-        else if (kind == MK_BALL) out = {x, y, 5.f, 0.f, 0.f, (float)luma(0x15, 0xA7, 0xBD), 0};
-        else out = {x, y, 8.f, 0.f, 0.f, (float)luma(0x6E, 0xC9, 0xE0), 0};   // shove thwump: RADIUS wins over SEMI_SIDE
-        return true;
-    }
-    if (kind == EK_MINE) {             // always active; radius follows the state
-        out = {x, y, st == 0 ? 4.0f : (st == 1 ? 3.5f : 4.5f), 0.f, 0.f,
-               type == 1 ? (float)luma(0x9E, 0x21, 0x26) : (float)luma(0xCE, 0x41, 0x46), 0};
-        return true;
-    }
-    if (kind == EK_EXIT) {             // always active; dark blue (0, 0, 0.5) once the switch was hit
-        out = {x, y, 12.f, 0.f, 0.f, st ? (float)luma(0, 0, 128) : (float)luma(0x83, 0x83, 0x84), 0};
-        return true;
-    }
-    if (kind == EK_DOOR_REG) return false;   // entity_renderer.py:104-105
-    if ((st & 1u) == 0) return false;        // collected gold / switches are inactive and not drawn
-    if (kind == EK_GOLD) out = {x, y, 6.f, 0.f, 0.f, (float)luma(0xDB, 0xE1, 0x49), 0};
-    else if (kind == EK_SWITCH) out = {x, y, 6.f, 0.f, 0.f, (float)luma(0x6D, 0x97, 0xC3), 0};
-    else if (kind == EK_BOOST) out = {x, y, 6.f, 0.f, 0.f, (float)luma(0x66, 0x66, 0x66), 0};
-    else if (kind == EK_LAUNCH || kind == EK_ONEWAY) {
-        // _draw_oriented_entity: angle = atan2(nx, ny) + pi/2; end points (x +- sin(angle) R, y +- cos(angle) R)
-        const uint32_t o = (info >> 10) & 7u;
-        const float dg = 0.70710678f;
-        const int sx = (o == 0 || o == 1 || o == 7) ? 1 : ((o >= 3 && o <= 5) ? -1 : 0);
-        const int sy = (o >= 1 && o <= 3) ? 1 : ((o >= 5) ? -1 : 0);
-        const float nx = (o & 1) ? sx * dg : (float)sx, ny = (o & 1) ? sy * dg : (float)sy;
-        const float R = kind == EK_LAUNCH ? 6.f : 12.f;
-        out = {x + ny * R, y - nx * R, 1.5f, x - ny * R, y + nx * R,
-               kind == EK_LAUNCH ? (float)luma(0x86, 0x87, 0x93) : (float)luma(0x66, 0x66, 0x66), 1};   // PLATFORMWIDTH 3
-    } else out = {x, y, 5.f, 0.f, 0.f, 0.f, 0};   // locked / trap door switch: black
-    return true;
-}
-
 // The window's draw list, built by ONE wavefront (lane = 0..63): lane l evaluates "virtual candidate" l (+ 64 per round) of the
 // sequence [closed door strokes | draw-order records | ninja] -- the reference's draw order -- and a ballot / prefix compaction
 // keeps that order; no workgroup barrier inside.  Measured alternative (round 2): all four wavefronts on 256 candidates per
@@ -457,8 +442,7 @@ __device__ inline void frame_build(FrameLds &L, const KernelArgs &a, const Level
     const float wx0 = wd.col0 - 16.f, wy0 = wd.row0 - 16.f, wx1 = wd.col0 + wd.w + 16.f, wy1 = wd.row0 + wd.h + 16.f;
     const uint4 *recs = reinterpret_cast<const uint4 *>(a.blob + fh.off_draw_recs);
     const uint32_t n_door = fh.n_door, n_draw = fh.n_draw, n_virt = n_door + n_draw + 1u;
-    const double *zhead = a.zoo ? a.zoo + (size_t)env * a.zoo_words : nullptr;
-    const uint32_t ovr = zhead ? reinterpret_cast<const uint32_t *>(zhead + 3)[0] : 0u;   // npp_set_entity_pos
+    const ZooHead z = zoo_head_of(a, env, fh.has_zoo, fh.obs_switch, fh.obs_door);
     const bool words_in_lanes = a.n_words_max <= 64;
     int nd = 0;   // wavefront-uniform
 #ifdef NPP_RENDER_STAMPS
@@ -482,18 +466,8 @@ __device__ inline void frame_build(FrameLds &L, const KernelArgs &a, const Level
             DrawCtx c{&a, &H, env, wx0, wy0, wx1, wy1, false};
             keep = door_drawable(c, v, d);
         } else if (is_rec) {
-            float x = __uint_as_float(rc.x), y = __uint_as_float(rc.y);
-            bool live = true;
-            if (info & 0x8000u) {   // a mover: position from the env's zoo block
-                live = zhead != nullptr && fh.has_zoo;
-                if (live) {
-                    const double *zb = zhead + ZOO_HEAD + (a.zoo_doors + 1) / 2 + ZOO_MOV_WORDS * slot;
-                    x = (float)zb[0]; y = (float)zb[1];
-                }
-            } else if (ovr) {
-                if (slot == fh.obs_switch && (ovr & ZOO_OVR_SWITCH)) { x = (float)zhead[4]; y = (float)zhead[5]; }
-                if (slot == fh.obs_door && (ovr & ZOO_OVR_DOOR)) { x = (float)zhead[6]; y = (float)zhead[7]; }
-            }
+            float x, y;
+            const bool live = rec_place(rc, z, false, x, y);
             if (live && !(x < wx0 || x > wx1 || y < wy0 || y > wy1)) {
                 uint32_t st = 1u;
                 if (!(info & 0x8000u)) st = words_in_lanes ? (sw >> ((slot & 15) * 2)) & 3u : ent_state_of(a, env, slot);
@@ -853,22 +827,7 @@ __global__ __launch_bounds__(256) void npp_gv_static_h_kernel(KernelArgs a, uint
     __shared__ unsigned char s_row[1056];
     const int y = blockIdx.x, lvl = blockIdx.y;
     const LevelHdr &H = a.hdr[lvl];
-    DrawCtx c{&a, &H, 0, -16.f, y - 16.f, 1056.f + 16.f, y + 1 + 16.f, true};
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    for (uint32_t d0 = 0; d0 < H.n_door; d0 += blockDim.x) {
-        Draw d = {};
-        const uint32_t k = d0 + threadIdx.x;
-        const bool keep = k < H.n_door && door_drawable(c, k, d);
-        append_ordered(keep, d, s_draw, GV_DRAW, &s_n, s_wc);
-    }
-    const uint32_t n_draw = H.n_ent + H.n_mov;
-    for (uint32_t k0 = 0; k0 < n_draw; k0 += blockDim.x) {
-        Draw d = {};
-        const uint32_t k = k0 + threadIdx.x;
-        const bool keep = k < n_draw && entity_drawable(c, k, d);
-        append_ordered(keep, d, s_draw, GV_DRAW, &s_n, s_wc);
-    }
+    build_draw_list(a, H, 0, true, false, 0.0, 0.0, -16.f, y - 16.f, 1056.f + 16.f, y + 1 + 16.f, s_draw, GV_DRAW, &s_n, s_wc);
     const uint8_t *canvas = a.tile_canvas + (size_t)lvl * 600 * 1056;
     uint8_t *prow = gv_p + ((size_t)lvl * 600 + y) * 1056;
     for (int x = threadIdx.x; x < 1056; x += blockDim.x) {
@@ -1243,8 +1202,7 @@ __global__ __launch_bounds__(64, 3) void npp_global_view_kernel(KernelArgs a, in
         }
     }
     {
-        const double *zhead = a.zoo ? a.zoo + (size_t)env * a.zoo_words : nullptr;
-        const uint32_t ovr = zhead ? reinterpret_cast<const uint32_t *>(zhead + 3)[0] : 0u;   // npp_set_entity_pos
+        const ZooHead z = zoo_head_of(a, env, H.has_zoo, H.obs_switch, H.obs_door);
         for (uint32_t k0 = 0; k0 < n_draw; k0 += 64) {
             const uint32_t k = k0 + lane;
             bool kc = false, ki = false;
@@ -1259,22 +1217,11 @@ __global__ __launch_bounds__(64, 3) void npp_global_view_kernel(KernelArgs a, in
                 sh_init = (uint32_t)__shfl((int)w_init, wl, 64);
             }
             if (k < n_draw) {
-                const float x0 = __uint_as_float(rc.x), y0 = __uint_as_float(rc.y);
-                float x = x0, y = y0;
                 const uint32_t info = rc.z;
                 const int slot = (int)(info >> 16);
                 const bool mover = (info & 0x8000u) != 0;
-                bool live = true;
-                if (mover) {   // position from the env's zoo block
-                    live = zhead != nullptr && H.has_zoo;
-                    if (live) {
-                        const double *zb = zhead + ZOO_HEAD + (a.zoo_doors + 1) / 2 + ZOO_MOV_WORDS * slot;
-                        x = (float)zb[0]; y = (float)zb[1];
-                    }
-                } else if (ovr) {
-                    if (slot == H.obs_switch && (ovr & ZOO_OVR_SWITCH)) { x = (float)zhead[4]; y = (float)zhead[5]; }
-                    if (slot == H.obs_door && (ovr & ZOO_OVR_DOOR)) { x = (float)zhead[6]; y = (float)zhead[7]; }
-                }
+                float x, y, x0, y0;   // where it is now, where it is right after a reset
+                const bool live = rec_place(rc, z, false, x, y), live0 = rec_place(rc, z, true, x0, y0);
                 const uint32_t st_now = mover ? 1u : (words_in_lanes ? (sh_now >> ((slot & 15) * 2)) & 3u : ent_state_of(a, env, slot));
                 const uint32_t st_init = words_in_lanes && !mover ? (sh_init >> ((slot & 15) * 2)) & 3u
                                                                   : (init_words[slot >> 4] >> ((slot & 15) * 2)) & 3u;
@@ -1282,7 +1229,7 @@ __global__ __launch_bounds__(64, 3) void npp_global_view_kernel(KernelArgs a, in
                 // the usual record: a static entity in the state and at the place it has after a reset -> the drawable IS the
                 // init drawable, no dirty box, one evaluation instead of two (most of a level's mines, all its untouched gold)
                 if (mover || st_now != st_init || x != x0 || y != y0) {
-                    if (!mover && !(x0 < wx0 || x0 > wx1 || y0 < wy0 || y0 > wy1)) ki = rec_drawable(info, x0, y0, st_init, di);
+                    if (live0 && !(x0 < wx0 || x0 > wx1 || y0 < wy0 || y0 > wy1)) ki = rec_drawable(info, x0, y0, st_init, di);
                     if (kc != ki || (kc && draw_differs(d, di))) {
                         if (kc) gv_push_box(L, d);
                         if (ki) gv_push_box(L, di);
@@ -1498,7 +1445,7 @@ __global__ __launch_bounds__(256) void npp_full_frame_kernel(KernelArgs a, int e
     const int lvl = a.env_level[env];
     const LevelHdr &H = a.hdr[lvl];
     const double px = a.f64[(size_t)F_X * a.n + env], py = a.f64[(size_t)F_Y * a.n + env];
-    build_draw_list(a, H, env, px, py, -16.f, y - 16.f, 1056.f + 16.f, y + 1 + 16.f, s_draw, GV_DRAW, &s_n, s_wc);
+    build_draw_list(a, H, env, false, true, px, py, -16.f, y - 16.f, 1056.f + 16.f, y + 1 + 16.f, s_draw, GV_DRAW, &s_n, s_wc);
     const uint8_t *canvas = a.tile_canvas + (size_t)lvl * 600 * 1056;
     uint8_t *row = out + ((size_t)e * 600 + y) * 1056;
     for (int x = threadIdx.x; x < 1056; x += blockDim.x) row[x] = (uint8_t)canvas_pixel(s_draw, s_n, canvas, x, y);
@@ -1522,7 +1469,7 @@ __global__ __launch_bounds__(256) void npp_switch_states_kernel(KernelArgs a, fl
         if (slot >= 0) {
             const double sx = ex[slot] / 1056.0, sy = ey[slot] / 600.0;
             const float fx = (float)(sx < 0.0 ? 0.0 : (sx > 1.0 ? 1.0 : sx)), fy = (float)(sy < 0.0 ? 0.0 : (sy > 1.0 ? 1.0 : sy));
-            const uint32_t st = (a.ent_bits[(size_t)(slot >> 4) * a.n + env] >> ((slot & 15) * 2)) & 3u;
+            const uint32_t st = ent_state_of(a, env, slot);
             v[0] = fx; v[1] = fy; v[2] = fx; v[3] = fy; v[4] = (st & 1u) ? 0.f : 1.f;
         }
         for (int j = 0; j < 5; j++) o[5 * k + j] = v[j];

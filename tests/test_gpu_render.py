@@ -53,9 +53,10 @@ def test_player_frame_centered(golden):
     _check(golden, centered=True)
 
 
-def _zoo_batch_and_oracles(golden, oracle_mod, centered, n_steps=60):
+def _zoo_batch_and_oracles(golden, oracle_mod, centered, n_steps=60, moved=None):
     """A few zoo + plain levels stepped with random actions on the GPU and on the oracle twin (same bits), so that the
-    oracle can tell the numpy rasteriser where every entity is."""
+    oracle can tell the numpy rasteriser where every entity is.  `moved`: {env: (switch xy, door xy)}, the exit switch and
+    exit door repositioned with set_entity_pos on the batch and on the twin before the first step."""
     from nclone_amd.engine import NppBatch
 
     c, z, r = golden.z("corpus"), golden.z("zoo"), golden.z("rollouts")
@@ -66,6 +67,10 @@ def _zoo_batch_and_oracles(golden, oracle_mod, centered, n_steps=60):
     b = NppBatch(n, autoreset=False, frame_centered=centered)
     b.load_levels(levels)
     b.assign_levels(lvl)
+    moved = moved or {}
+    for e, (sw, door) in moved.items():
+        b.set_entity_pos(e, 0, *sw)
+        b.set_entity_pos(e, 1, *door)
     rng = np.random.default_rng(31)
     acts = rng.integers(0, 6, size=(n_steps, n)).astype(np.uint8)
     d = torch.from_numpy(acts).cuda()
@@ -75,6 +80,9 @@ def _zoo_batch_and_oracles(golden, oracle_mod, centered, n_steps=60):
     for e in range(n):
         o = oracle_mod.Oracle("mul")
         o.load(levels[lvl[e]])
+        if e in moved:
+            o.set_entity_pos(0, *moved[e][0])
+            o.set_entity_pos(1, *moved[e][1])
         done = False
         for s in range(n_steps):
             if not done:
@@ -212,6 +220,61 @@ def test_full_frame_consistent_with_player_frame_and_reference_raster(golden, or
         ref, edge = render_canvas(sims[e].tiles(), sims[e].draw_list(), px, py, 0, y0, 1056, 60)
         dlt = np.abs(full[y0:y0 + 60].astype(np.int64) - ref.astype(np.int64))
         assert len(np.argwhere((dlt > 0) & ~edge)) == 0 and dlt.max(initial=0) <= 64 and dlt.mean() < 2.0, e
+
+
+def test_repositioned_switch_and_door_in_every_render_entry(golden, oracle_mod):
+    """npp_set_entity_pos in the pictures: on four envs (three zoo levels, one plain) the exit switch and the exit door are moved
+    -- a door or a switch next to the spawn, so that the 84 x 84 window sees it, the others into open space elsewhere -- then 30
+    random steps.  For every env: (a) the physics equals the oracle twin's (the helper asserts it), (b) the crop of the whole frame
+    IS the player_frame, (c) global_view IS the area reduction of the whole frame, (d) a 60-row band of the whole frame through
+    the exit switch matches the numpy rasteriser under the usual tolerance.  (b) and (c) compare kernels that share the code
+    which places a draw record, so (d) is the independent check: its positions come from the twin's draw_list(), which
+    carries the moved positions (asserted below against the arguments passed)."""
+    from tests.raster_ref import render_canvas
+
+    moved = {0: ((541.0, 470.0), (756.0, 486.0)), 1: ((436.0, 403.0), (578.0, 306.0)),
+             3: ((393.0, 183.0), (156.0, 246.0)), 4: ((504.0, 183.0), (504.0, 224.0))}
+    b, sims, f = _zoo_batch_and_oracles(golden, oracle_mod, True, n_steps=30, moved=moved)
+    pf = torch.zeros((b.n, 84, 84), dtype=torch.uint8, device="cuda")
+    b.render_player_frame(pf)
+    pf = pf.cpu().numpy()
+    gv = torch.zeros((b.n, 176, 100), dtype=torch.uint8, device="cuda")
+    b.render_global_view(gv)
+    xtab, ytab = _area_tabs(100, 1056.0 / 100, 1056), _area_tabs(176, 600.0 / 176, 600)
+    seen_in_window, seen_in_band = set(), 0
+    for e in range(b.n):
+        rows = sims[e].draw_list()
+        px, py = f[e, 0], f[e, 1]
+        sw_rows = [r for r in rows if int(r[0]) == 4]
+        door_rows = [r for r in rows if int(r[0]) == 3]
+        if e in moved:
+            assert (sw_rows[-1][1], sw_rows[-1][2]) == moved[e][0] and (door_rows[-1][1], door_rows[-1][2]) == moved[e][1], e
+        full_d = b.render_frame(e, 1)[0, :, :, 0]
+        full = full_d.cpu().numpy()
+        # (b)
+        r0, r1, c0, c1 = max(0, int(py - 42)), min(600, int(py + 42)), max(0, int(px - 42)), min(1056, int(px + 42))
+        h, w = r1 - r0, c1 - c0
+        top, left = (84 - h) // 2, (84 - w) // 2
+        assert np.array_equal(pf[e][top:top + h, left:left + w], full[r0:r1, c0:c1]), e
+        # (c)
+        ref_gv = _reduce_frame(full_d.float(), xtab, ytab)
+        assert torch.equal(gv[e], ref_gv), (e, int((gv[e] != ref_gv).sum()))
+        # (d): through the exit switch (the moved one where it was moved); a level without an exit: through the player
+        yc = sw_rows[-1][2] if sw_rows else py
+        y0 = max(0, min(600 - 60, int(yc) - 30))
+        ref, edge = render_canvas(sims[e].tiles(), rows, px, py, 0, y0, 1056, 60)
+        dlt = np.abs(full[y0:y0 + 60].astype(np.int64) - ref.astype(np.int64))
+        assert len(np.argwhere((dlt > 0) & ~edge)) == 0 and dlt.max(initial=0) <= 64 and dlt.mean() < 2.0, e
+        if e in moved:
+            for kind, (x, y) in enumerate(moved[e]):   # whole discs (radius 6 and 12) inside what was compared
+                m = 6 * (kind + 1)
+                if c0 + m <= x < c1 - m and r0 + m <= y < r1 - m:
+                    seen_in_window.add(kind)
+            seen_in_band += int(sw_rows[-1][3] != 0 and y0 + 6 <= moved[e][0][1] < y0 + 54)
+    # the checks looked at moved entities: a moved switch and a moved door inside a player window, every moved switch still
+    # uncollected (hence drawn) inside its band
+    assert seen_in_window == {0, 1} and seen_in_band == len(moved)
+    b.close()
 
 
 def test_vec_env_surface(golden):
