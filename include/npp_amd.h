@@ -421,6 +421,44 @@ int npp_archive_cell_keys_host(const double *map, int64_t n, int level, const do
 int npp_archive_cell_pick_host(const int32_t *cell_slot, const uint32_t *visits, const uint32_t *chosen, uint64_t seed, uint32_t call,
                                const int32_t *envs, int count, int32_t *slots_out);
 
+/* Action routes: the list of actions that led every env from its spawn to where it is, kept on the device.  In the reference a
+ * checkpoint IS its route: StateCheckpoint.action_sequence (state_checkpoint.py) is replayed from the spawn by ActionReplayer, and
+ * the env keeps the running list -- base_environment.py:186 creates `_action_sequence`, :517 appends per step, :1677 clears at
+ * reset, :2114 appends during a checkpoint replay; get_current_action_sequence() / get_action_sequence_length() serve it
+ * (:2332-2349).  Off by default: nothing is allocated, nothing is launched, records keep their size.  The rule
+ * (csrc/npp_route.hpp):
+ *   buffers   u8[n_envs][2][cap], one action (0..5) per byte: the route being written and the route of the episode that ended last
+ *   header    i32[n_envs][16]: words 0-5 the CURRENT route, 6-11 the FINISHED route, 12 which buffer holds the current one, 13-15 0
+ *   a route   len | bits (1 = an action was dropped at len == cap, 2 = not replayable from this record) | frame_skip (0 while empty)
+ *             | frames executed | flags byte of the last executed step | the level at the first append (-1 while empty);
+ *             empty = len == 0 and bits == 0
+ *   step row  (npp_step; npp_step_many: its n_steps rows in order) with x frames executed: x > 0 appends the action (an env that is
+ *             terminal and not auto-reset executes 0 frames and appends nothing); then, with NPP_FLAG_AUTORESET and a flags byte with
+ *             WON, DEAD or TRUNCATED, a FLIP: the current route becomes the finished one (no bytes move) and an empty one starts.
+ *             A flip of an empty route changes nothing.  The append is a launch of its own behind the step (per part of a split
+ *             step, on the part's stream); it reads the step's flags / frames rows -- rows of the handle when npp_step_out has none.
+ *   resets    npp_reset / npp_reset_ex (masked envs), npp_assign_levels (listed envs), npp_draw_levels and the level pool's redraw
+ *             (envs that changed level) flip; npp_load_levels empties both routes of every env; npp_tick sets bit 2 everywhere.
+ *   records   while routes are on, every archive / snapshot record carries the env's current route (8 header words, then the
+ *             bytes), and npp_archive_restore / npp_restore replace the env's CURRENT route with the record's (the finished route
+ *             stays); npp_archive_record_bytes grows by 32 + cap.  Store and restore move the first len bytes rounded up to 16.
+ * npp_set_routes(h, capacity): > 0 is rounded up to a multiple of 16 and allocates zeroed buffers and empty headers; 0 frees them;
+ *   < 0 is NPP_ERR_INVALID.  NPP_ERR_STATE while a checkpoint archive exists (its records' layout depends on it: call it before
+ *   npp_archive_create).  An existing snapshot is invalidated (npp_restore: NPP_ERR_STATE until the next npp_snapshot).  A failed
+ *   allocation is NPP_ERR_HIP and leaves the previous state in place.
+ * npp_route_view: device views of the buffers and headers, valid until the next npp_set_routes, rewritten in stream order.
+ * npp_archive_route_view: slot s keeps its route header at d_records + s * stride_words + hdr_offset_words and its bytes 8 words
+ *   later -- a selection rule can read route lengths (the reference's find_checkpoint_with_min_replay_cost) and an export can copy
+ *   single routes without a kernel.  NPP_ERR_STATE without an archive or without routes.
+ * npp_route_apply_host: the same rule without a GPU or a handle, for tests, on ONE env: hdr i32[16], actions u8[2][capacity]
+ *   (capacity a multiple of 16), updated in place by `count` events of 8 words each: {0, action, flags, frames, frame_skip, level}
+ *   a step row; {1} a reset; {2} raw ticks; {3, six header words, byte offset into restore_bytes} a restore from that route. */
+int npp_set_routes(npp_handle h, int capacity);
+int npp_route_view(npp_handle h, const uint8_t **d_actions, const int32_t **d_hdr, int *capacity);
+int npp_archive_route_view(npp_handle h, const uint32_t **d_records, int64_t *hdr_offset_words, int64_t *stride_words);
+int npp_route_apply_host(int32_t *hdr, uint8_t *actions, int capacity, int autoreset, const int32_t *events, int count,
+                         const uint8_t *restore_bytes);
+
 /* Launch geometry: lanes_per_env wavefront lanes cooperate on one environment (power of two, 1..64; 0 = choose from
  * n_envs so that the grid fills the chip), waves_per_block wavefronts share one LDS copy of a level (1..4, 0 = auto).
  * Results are bit-identical for every geometry; only speed changes. */

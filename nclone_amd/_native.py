@@ -41,6 +41,7 @@ EXPORTS = [
     "npp_archive_record_bytes",
     "npp_archive_cells_create", "npp_archive_explore", "npp_archive_select", "npp_archive_cells_view",
     "npp_archive_cell_keys_host", "npp_archive_cell_pick_host",
+    "npp_set_routes", "npp_route_view", "npp_archive_route_view", "npp_route_apply_host",
 ]
 
 
@@ -163,6 +164,10 @@ def lib():
     L.npp_archive_cell_keys_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_void_p]
     L.npp_archive_cell_pick_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_set_routes.argtypes = [H, C.c_int]
+    L.npp_route_view.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.npp_archive_route_view.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.npp_route_apply_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

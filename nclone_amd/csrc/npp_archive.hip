@@ -1,7 +1,7 @@
 // npp_archive.hip -- the two kernels that move one env's state between the live planes and a record (npp_archive.hpp): entry i
 // moves env envs[i] into record slots[i] (store) or back (restore); without lists entry i is env i and record i, under an optional
 // env mask (the snapshot slot).  One wavefront per entry: the strided [plane][n] planes go one plane per lane, the contiguous
-// rows (zoo block, spatial-context cache, reachability row) and the record go over consecutive lanes, so the record side of an
+// rows (zoo block, spatial-context cache, reachability row, route bytes) and the record go over consecutive lanes, so the record side of an
 // entry is one contiguous stream.  Everything that decides an entry (the two list values or the mask byte, the slot's "stored"
 // word and level) is wave-uniform; lane 0 writes the status and the meta row.  An entry whose status is not 0 reads only the list
 // values (and, restore, the slot's meta and level words once both indices are known to be in range) and writes only its status.
@@ -62,6 +62,25 @@ template <bool STORE> __global__ __launch_bounds__(256) void npp_archive_kernel(
         float *live = a.sc + e * ARCHIVE_SC + lane;
         if (STORE) rec[L.off_sc + lane] = __float_as_uint(*live);
         else *live = __uint_as_float(rec[L.off_sc + lane]);
+    }
+    if (L.route_cap) {
+        // the env's current route (npp_route.hpp): header words by the first lanes, then the first `len` bytes, rounded up to 16,
+        // 16 per lane (cap is a multiple of 16 and both sides are 16-byte aligned).  A restore leaves the env's finished route and
+        // its buffer choice (word 12) alone.
+        int32_t *hdr = a.route_hdr + e * ROUTE_HDR_WORDS;
+        const int cur = hdr[ROUTE_CUR] & 1;
+        uint4 *live = reinterpret_cast<uint4 *>(a.route_act + (e * 2 + cur) * L.route_cap);
+        uint4 *recb = reinterpret_cast<uint4 *>(rec + L.off_route + ROUTE_REC_HDR_WORDS);
+        int len = STORE ? hdr[R_LEN] : (int32_t)rec[L.off_route + R_LEN];
+        len = len < 0 ? 0 : (len > L.route_cap ? L.route_cap : len);
+        if (lane < ROUTE_REC_HDR_WORDS) {
+            if (STORE) rec[L.off_route + lane] = lane < ROUTE_WORDS ? (uint32_t)hdr[lane] : 0u;
+            else if (lane < ROUTE_WORDS) hdr[lane] = (int32_t)rec[L.off_route + lane];
+        }
+        for (int k = lane; k < (len + 15) / 16; k += WAVE) {
+            if (STORE) recb[k] = live[k];
+            else live[k] = recb[k];
+        }
     }
     if (STORE) {
         const bool reach = a.reach_key != nullptr;

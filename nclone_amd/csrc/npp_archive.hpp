@@ -8,6 +8,7 @@
 
 #include "npp_internal.hpp"
 #include "npp_reach.hpp"
+#include "npp_route.hpp"
 
 namespace npp {
 
@@ -20,13 +21,17 @@ namespace npp {
 //   sc    [48]              spatial-context cache row (floats)
 //   reach [1 + REACH_DIM+1] key, then the cache row (floats); meaningful only when tail word 2 is set
 //   tail  [4]               truncation limit, level, 1 = the record holds a reachability key / row, level pool draw count
+//   route [8 + cap / 4]     (only with action routes on, npp_set_routes) the env's CURRENT route: its six header words
+//                           (npp_route.hpp), two zero words, then the action bytes -- of which store and restore move only the
+//                           first `len`, rounded up to 16, so a record's traffic follows its route and not the capacity
 struct ArchiveLayout {
     int zoo_words = 0, n_words_max = 0;
     int off_zoo = 0, off_u32 = 0, off_ent = 0, off_sc = 0, off_reach = 0, off_tail = 0;
+    int route_cap = 0, off_route = 0;   // route_cap: bytes per route buffer, a multiple of 16; 0 = the record has no route section
     int words = 0;   // record size, a multiple of 4
 };
 constexpr int ARCHIVE_SC = 48, ARCHIVE_REACH_ROW = REACH_DIM + 1;
-inline ArchiveLayout archive_layout(int n_words_max, int zoo_words) {
+inline ArchiveLayout archive_layout(int n_words_max, int zoo_words, int route_cap = 0) {
     ArchiveLayout L;
     L.zoo_words = zoo_words;
     L.n_words_max = n_words_max;
@@ -37,6 +42,11 @@ inline ArchiveLayout archive_layout(int n_words_max, int zoo_words) {
     L.off_reach = L.off_sc + ARCHIVE_SC;
     L.off_tail = L.off_reach + 1 + ARCHIVE_REACH_ROW;
     L.words = (L.off_tail + 4 + 3) / 4 * 4;
+    if (route_cap > 0) {   // (words is a multiple of 4 and so is the section: the bytes start 16-byte aligned)
+        L.route_cap = route_cap;
+        L.off_route = L.words;
+        L.words += ROUTE_REC_HDR_WORDS + route_cap / 4;
+    }
     return L;
 }
 
@@ -68,6 +78,8 @@ struct ArchiveArgs {
     uint32_t *reach_key;           // [n]; null = the reachability buffers do not exist (yet)
     float *reach_cache;            // [n][REACH_DIM + 1]
     uint32_t *reach_last_episode;  // [n]; null = no level of the set takes the miss branch
+    int32_t *route_hdr;            // [n][ROUTE_HDR_WORDS]; with lay.route_cap only
+    uint8_t *route_act;            // [n][2][lay.route_cap]
 };
 hipError_t launch_archive_store(const ArchiveArgs &a, hipStream_t s);
 hipError_t launch_archive_restore(const ArchiveArgs &a, hipStream_t s);

@@ -258,6 +258,18 @@ struct Cells {
     DevBuf<int32_t> env_key, slot_of_env, iota;   // [n]
 };
 
+// action routes (npp_set_routes, npp_route.hip): per env a header and two action buffers; the archive's and the snapshot's records
+// carry the current route while this is on (record_layout)
+struct Routes {
+    int cap = 0;                  // bytes per buffer, a multiple of 16; 0 = off
+    DevBuf<int32_t> hdr;          // [n][ROUTE_HDR_WORDS]
+    DevBuf<uint8_t> act;          // [n][2][cap]
+    // the step's flags / frames rows when the caller asked for none (as Pool::flags), grown to the longest npp_step_many seen
+    DevBuf<uint8_t> flags;        // [rows][n]
+    DevBuf<uint16_t> frames;      // [rows][n]
+    int rows = 0;
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -292,6 +304,7 @@ struct npp_handle_s {
     FrameAug aug;
     Archive ar;
     Cells cells;
+    Routes rt;
 };
 
 
@@ -720,6 +733,68 @@ int apply_dynamic_truncation(npp_handle h, const uint8_t *mask) {
     return NPP_OK;
 }
 
+// ---- action routes (npp_set_routes; the rule: npp_route.hpp, the kernels: npp_route.hip).  Nothing below launches or allocates
+// while they are off.
+RouteArgs route_args(npp_handle h) {
+    RouteArgs r{};
+    r.n = h->n;
+    r.cap = h->rt.cap;
+    r.hdr = h->rt.hdr.get();
+    r.act = h->rt.act.get();
+    r.env_level = h->env.level.get();
+    r.autoreset = (h->flags & NPP_FLAG_AUTORESET) ? 1 : 0;
+    return r;
+}
+
+// a reset (ROUTE_EV_FLIP), raw ticks (ROUTE_EV_TICK) or a new level set (ROUTE_EV_INIT) for the envs of a device mask (null = all),
+// on the caller's stream; the caller has joined the streams
+int route_event(npp_handle h, int event, const uint8_t *d_mask) {
+    if (!h->rt.cap) return NPP_OK;
+    RouteArgs r = route_args(h);
+    r.mask = d_mask;
+    HIP_TRY(h, launch_route_event(r, event, h->stream));
+    return NPP_OK;
+}
+
+// The flags / frames rows the append reads: the caller's, or rows of the handle's own where `o` has none (as the level pool does
+// with Pool::flags)
+int route_rows(npp_handle h, npp_step_out &o, int n_steps) {
+    Routes &R = h->rt;
+    if (o.d_flags && o.d_frames) return NPP_OK;
+    if (R.rows < n_steps) {
+        DevBuf<uint8_t> f;
+        DevBuf<uint16_t> x;
+        if (f.alloc((size_t)n_steps * h->n) != hipSuccess || x.alloc((size_t)n_steps * h->n) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, NPP_ERR_HIP, "action routes: hipMalloc of " + std::to_string(n_steps) + " flags / frames rows failed");
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // a queued append may still read the old rows
+        R.flags = std::move(f);
+        R.frames = std::move(x);
+        R.rows = n_steps;
+    }
+    if (!o.d_flags) o.d_flags = R.flags.get();
+    if (!o.d_frames) o.d_frames = R.frames.get();
+    return NPP_OK;
+}
+
+// The append of one step launch, behind it: on the caller's stream, or -- after a split step -- once per part on the stream that
+// stepped the part, by the path of the observation kernels, so npp_step still does not join
+int route_append(npp_handle h, const uint8_t *d_actions, int n_steps, int frame_skip, const npp_step_out &o) {
+    RouteArgs r = route_args(h);
+    r.n_steps = n_steps;
+    r.frame_skip = frame_skip;
+    r.actions = d_actions;
+    r.flags = o.d_flags;
+    r.frames = o.d_frames;
+    return obs_launch(h, base_args(h), false, false, [&](const KernelArgs &ka, hipStream_t st) {
+        RouteArgs q = r;
+        q.phase = ka.phase;
+        q.phase_id = ka.phase_id;
+        return launch_route_append(q, st);
+    });
+}
+
 // `fresh` = the entities are created for the first time since the level was assigned (the state a replay starts from);
 // any later reset is a Simulator.reset(), after which Entity.index no longer starts at 0 (see ZOO_HEAD in npp_internal.hpp)
 int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, int automatic = 0) {
@@ -735,6 +810,7 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
         a.reset_mask = h->env.mask.get();
     }
     HIP_TRY(h, launch_reset(a, h->stream));
+    if (int rc = route_event(h, ROUTE_EV_FLIP, a.reset_mask)) return rc;   // (action routes) the episode of a reset env is over
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));  // env_mask is caller memory: finish the copy
     return NPP_OK;
 }
@@ -765,6 +841,8 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     a.reset_fresh = 1;
     a.fast_reset = 0;   // (base_args carries the auto-reset's NPP_FLAG_FAST_RESET) a new level is a Simulator.reset
     HIP_TRY(h, launch_reset(a, h->stream));
+    // (action routes) after a step the envs whose episode ended were flipped by the append: their empty route makes this a no-op
+    if (int rc = route_event(h, ROUTE_EV_FLIP, a.reset_mask)) return rc;
     if (L.reach.key) HIP_TRY(h, launch_reach_drop(a, L.reach.key.get(), L.reach.miss(), h->stream));
     if (out) {
         KernelArgs o = base_args(h);
@@ -779,7 +857,10 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     return NPP_OK;
 }
 
-ArchiveLayout record_layout(const LevelSet &L) { return archive_layout(L.n_words_max, L.zoo ? L.zoo_words : 0); }
+ArchiveLayout record_layout(npp_handle h) {
+    const LevelSet &L = h->ls;
+    return archive_layout(L.n_words_max, L.zoo ? L.zoo_words : 0, h->rt.cap);
+}
 
 // the live state the record kernels (npp_archive.hip) move, for records laid out by `lay`; the caller fills in which entries and
 // records, and nulls what a restore is to leave alone
@@ -800,6 +881,10 @@ ArchiveArgs record_args(npp_handle h, const ArchiveLayout &lay) {
     a.reach_key = L.reach.key.get();
     a.reach_cache = L.reach.cache.get();
     a.reach_last_episode = L.reach.last_episode.get();
+    if (lay.route_cap) {
+        a.route_hdr = h->rt.hdr.get();
+        a.route_act = h->rt.act.get();
+    }
     return a;
 }
 
@@ -869,8 +954,8 @@ int npp_snapshot(npp_handle h) {
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_snapshot: no levels loaded");
     ON_DEVICE_JOINED(h);
     Snapshot &s = h->snap;
-    const ArchiveLayout lay = record_layout(h->ls);
-    if (!s.rec || s.lay.n_words_max != lay.n_words_max || s.lay.zoo_words != lay.zoo_words) {
+    const ArchiveLayout lay = record_layout(h);
+    if (!s.rec || s.lay.n_words_max != lay.n_words_max || s.lay.zoo_words != lay.zoo_words || s.lay.route_cap != lay.route_cap) {
         HIP_TRY(h, s.rec.alloc((size_t)h->n * lay.words));
         s.lay = lay;
     }
@@ -965,7 +1050,7 @@ int npp_archive_create(npp_handle h, int n_slots) {
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_archive_create: no levels loaded");
     if (int rc = archive_refusal(h, "npp_archive_create")) return rc;
     Archive A;   // complete or not at all: a failed allocation leaves the previous archive in place
-    A.lay = record_layout(h->ls);
+    A.lay = record_layout(h);
     const size_t S = (size_t)n_slots;
     if (A.rec.alloc(S * A.lay.words) != hipSuccess || A.meta_f64.alloc(S * ARCHIVE_META_F64) != hipSuccess ||
         A.meta_i32.alloc(S * ARCHIVE_META_I32) != hipSuccess) {
@@ -1001,6 +1086,51 @@ int npp_archive_meta_view(npp_handle h, const double **d_f64, const int32_t **d_
 
 int npp_archive_num_slots(npp_handle h) { return h ? h->ar.n_slots : 0; }
 int npp_archive_record_bytes(npp_handle h) { return h && h->ar.n_slots ? h->ar.lay.words * 4 : 0; }
+
+int npp_set_routes(npp_handle h, int capacity) {
+    if (!h) return NPP_ERR_INVALID;
+    if (capacity < 0) return fail(h, NPP_ERR_INVALID, "npp_set_routes: capacity must be >= 0 (0 switches the routes off)");
+    if (h->ar.n_slots)
+        return fail(h, NPP_ERR_STATE, "npp_set_routes: a checkpoint archive exists and its records' layout depends on the routes "
+                                      "(call it before npp_archive_create)");
+    ON_DEVICE_JOINED(h);
+    Routes r;   // complete or not at all: a failed allocation leaves the previous state in place
+    if (capacity > 0) {
+        r.cap = route_round_cap(capacity);
+        if (r.hdr.alloc((size_t)h->n * ROUTE_HDR_WORDS) != hipSuccess || r.act.alloc((size_t)h->n * 2 * r.cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, NPP_ERR_HIP, "npp_set_routes: hipMalloc of " + std::to_string(h->n) + " x 2 routes of " + std::to_string(r.cap) +
+                                            " bytes failed");
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // queued appends / record moves still use the old buffers
+    h->rt = std::move(r);
+    h->snap = Snapshot();   // its records were laid out for the old capacity
+    if (h->rt.cap) {
+        HIP_TRY(h, hipMemsetAsync(h->rt.act.get(), 0, h->rt.act.bytes(), h->stream));
+        if (int rc = route_event(h, ROUTE_EV_INIT, nullptr)) return rc;
+    }
+    return NPP_OK;
+}
+
+int npp_route_view(npp_handle h, const uint8_t **d_actions, const int32_t **d_hdr, int *capacity) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->rt.cap) return fail(h, NPP_ERR_STATE, "npp_route_view: action routes are off (npp_set_routes)");
+    if (d_actions) *d_actions = h->rt.act.get();
+    if (d_hdr) *d_hdr = h->rt.hdr.get();
+    if (capacity) *capacity = h->rt.cap;
+    return NPP_OK;
+}
+
+int npp_archive_route_view(npp_handle h, const uint32_t **d_records, int64_t *hdr_offset_words, int64_t *stride_words) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->ar.n_slots) return fail(h, NPP_ERR_STATE, "npp_archive_route_view: no archive (npp_archive_create)");
+    if (!h->ar.lay.route_cap) return fail(h, NPP_ERR_STATE, "npp_archive_route_view: action routes are off (npp_set_routes)");
+    if (d_records) *d_records = h->ar.rec.get();
+    if (hdr_offset_words) *hdr_offset_words = h->ar.lay.off_route;
+    if (stride_words) *stride_words = h->ar.lay.words;
+    return NPP_OK;
+}
 
 namespace {
 // what explore and select share: the refusals, the join, the tables
@@ -1272,6 +1402,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     HIP_TRY(h, hipMemset(h->env.level.get(), 0, h->env.level.bytes()));
     if (h->dyn_trunc)
         if (int rc = apply_dynamic_truncation(h, nullptr)) return rc;
+    if (int rc = route_event(h, ROUTE_EV_INIT, nullptr)) return rc;   // (action routes) level ids lost their meaning: both routes empty
     return reset_impl(h, nullptr, 1);
 }
 
@@ -1614,13 +1745,23 @@ extern "C" {
 int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
-    if (!h->pool.on || !(h->flags & NPP_FLAG_AUTORESET)) return step_impl(h, d_actions, frame_skip, out);
-    // level pool: the step as without it, then (joined) the draw for the envs whose episode ended -- read from the step's flags
+    const bool pool = h->pool.on && (h->flags & NPP_FLAG_AUTORESET);
+    if (!pool && !h->rt.cap) return step_impl(h, d_actions, frame_skip, out);
     npp_step_out o;
     std::memset(&o, 0, sizeof(o));
     if (out) o = *out;
-    if (!o.d_flags) o.d_flags = h->pool.flags.get();
+    if (h->rt.cap) {   // action routes: the append behind the step reads the step's flags and frames rows
+        ON_DEVICE_JOINED(h);
+        if (int rc = route_rows(h, o, 1)) return rc;
+    }
+    if (pool && !o.d_flags) o.d_flags = h->pool.flags.get();
     if (int rc = step_impl(h, d_actions, frame_skip, &o)) return rc;
+    if (h->rt.cap) {
+        ON_DEVICE(h);
+        if (int rc = route_append(h, d_actions, 1, frame_skip, o)) return rc;
+    }
+    if (!pool) return NPP_OK;
+    // level pool: the step as without it, then (joined) the draw for the envs whose episode ended -- read from the step's flags
     ON_DEVICE_JOINED(h);
     return pool_redraw(h, o.d_flags, NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED, &o);
 }
@@ -1634,9 +1775,17 @@ int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame
     a.n_ticks = frame_skip;
     a.n_steps = n_steps;
     a.mode = 0;
+    npp_step_out o;
+    if (h->rt.cap) {   // action routes: the append walks the launch's n_steps flags / frames rows
+        std::memset(&o, 0, sizeof(o));
+        if (out) o = *out;
+        if (int rc = route_rows(h, o, n_steps)) return rc;
+        out = &o;
+    }
     if (int rc = fill_obs_out(h, a, out)) return rc;
     a.out.terminal_state = nullptr;   // pre-reset observations exist for single steps only
     HIP_TRY(h, launch_step(a, h->stream));
+    if (h->rt.cap) return route_append(h, d_actions, n_steps, frame_skip, o);
     return NPP_OK;
 }
 
@@ -1650,7 +1799,7 @@ int npp_tick(npp_handle h, const uint8_t *d_inputs, int n_ticks) {
     a.mode = 1;
     a.autoreset = 0;
     HIP_TRY(h, launch_step(a, h->stream));
-    return NPP_OK;
+    return route_event(h, ROUTE_EV_TICK, nullptr);   // (action routes) raw input bytes: the current routes no longer lead here
 }
 
 int npp_observe(npp_handle h, const npp_step_out *out) {

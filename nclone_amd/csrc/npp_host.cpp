@@ -11,6 +11,7 @@
 #include "npp_minimal.hpp"
 #include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
+#include "npp_route.hpp"
 
 using namespace npp;
 
@@ -104,6 +105,29 @@ int npp_archive_cell_pick_host(const int32_t *cell_slot, const uint32_t *visits,
         cdf[k] = run;
     }
     for (int i = 0; i < count; i++) slots_out[i] = run ? cell_slot[cell_pick(cdf.data(), seed, (uint32_t)envs[i], call)] : -1;
+    return NPP_OK;
+}
+
+int npp_route_apply_host(int32_t *hdr, uint8_t *actions, int capacity, int autoreset, const int32_t *events, int count,
+                         const uint8_t *restore_bytes) {
+    if (!hdr || !actions || capacity <= 0 || capacity % 16 || count < 0 || (count > 0 && !events))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_route_apply_host: bad arguments (capacity must be a positive multiple of 16)");
+    if ((hdr[ROUTE_CUR] != 0 && hdr[ROUTE_CUR] != 1) || hdr[R_LEN] < 0 || hdr[R_LEN] > capacity)
+        return fail(nullptr, NPP_ERR_INVALID, "npp_route_apply_host: header word 12 must be 0 or 1 and word 0 within the capacity");
+    for (int i = 0; i < count; i++) {
+        const int32_t *ev = events + (size_t)i * 8;
+        switch (ev[0]) {
+        case 0: route_step(hdr, actions, capacity, ev[1], ev[2], ev[3], ev[4], ev[5], autoreset != 0); break;
+        case 1: route_flip(hdr); break;
+        case 2: route_tick(hdr); break;
+        case 3:
+            if (ev[1 + R_LEN] < 0 || ev[1 + R_LEN] > capacity || (ev[1 + R_LEN] > 0 && (!restore_bytes || ev[7] < 0)))
+                return fail(nullptr, NPP_ERR_INVALID, "npp_route_apply_host: event " + std::to_string(i) + ": bad route to restore from");
+            route_restore(hdr, actions, capacity, ev + 1, restore_bytes ? restore_bytes + ev[7] : nullptr);
+            break;
+        default: return fail(nullptr, NPP_ERR_INVALID, "npp_route_apply_host: event " + std::to_string(i) + ": unknown kind");
+        }
+    }
     return NPP_OK;
 }
 

@@ -236,6 +236,25 @@ hipError_t launch_cells_propose(const CellArgs &a, hipStream_t s);
 hipError_t launch_cells_assign(const CellArgs &a, hipStream_t s);
 hipError_t launch_cells_cdf(const CellArgs &a, hipStream_t s);
 hipError_t launch_cells_pick(const CellArgs &a, hipStream_t s);
+// npp_route.hip: action routes (see npp_set_routes in include/npp_amd.h; the rule: npp_route.hpp)
+struct RouteArgs {
+    int n, cap;
+    int32_t *hdr;                 // [n][ROUTE_HDR_WORDS]
+    uint8_t *act;                 // [n][2][cap]
+    // append: the rows of one step launch
+    int n_steps, frame_skip, autoreset;
+    const uint8_t *actions;       // [n_steps][n]
+    const uint8_t *flags;         // [n_steps][n]
+    const uint16_t *frames;       // [n_steps][n]
+    const int32_t *env_level;     // [n]
+    const uint8_t *phase;         // observation overlap: only the envs of part phase_id (null = all)
+    int phase_id;
+    // event: one of ROUTE_EV_* for the envs with a non-zero mask byte (null = all)
+    const uint8_t *mask;
+};
+enum RouteEvent { ROUTE_EV_FLIP = 0, ROUTE_EV_TICK = 1, ROUTE_EV_INIT = 2 };
+hipError_t launch_route_append(const RouteArgs &a, hipStream_t s);
+hipError_t launch_route_event(const RouteArgs &a, int event, hipStream_t s);
 // npp_graph.hip: graph observation rows (see npp_graph_observation in include/npp_amd.h; tables: npp_graph.hpp)
 struct GraphHdr;
 struct GraphArgs {

@@ -282,7 +282,7 @@ class NppBatch:
         nat.check(self.h, self.lib.npp_load_levels(
             self.h, blob.ctypes.data_as(C.POINTER(C.c_double)), offsets.ctypes.data_as(C.POINTER(C.c_int64)), len(offsets) - 1))
         self.n_levels = len(offsets) - 1
-        self._archive_meta = self._archive_cells = None   # (the checkpoint archive and its cell index go with the level set)
+        self._archive_meta = self._archive_cells = self._archive_route_views = None   # (the checkpoint archive and its cell index go with the level set)
 
     def assign_levels(self, level_ids, env_ids=None):
         lv = np.ascontiguousarray(level_ids, dtype=np.int32)
@@ -558,7 +558,7 @@ class NppBatch:
         if n_slots < 0:
             raise ValueError("archive_create: n_slots must be >= 0 (0 frees the archive)")
         nat.check(self.h, self.lib.npp_archive_create(self.h, n_slots))
-        self._archive_meta = self._archive_cells = None
+        self._archive_meta = self._archive_cells = self._archive_route_views = None
 
     def archive_num_slots(self):
         return int(self.lib.npp_archive_num_slots(self.h))
@@ -618,6 +618,42 @@ class NppBatch:
             meta.update({k: ti[:, c] for c, k in enumerate(("stored", "level", "frame", "cell_x", "cell_y", "switch_activated"))})
             self._archive_meta = meta
         return self._archive_meta
+
+    # ---- action routes (include/npp_amd.h npp_set_routes; the reference's _action_sequence) ---------------
+    def set_routes(self, capacity):
+        """Record every env's action route on the device: `capacity` actions per route (rounded up to a multiple of 16; 0
+        switches it off and frees the buffers).  Before archive_create: the archive's records then carry each slot's route.
+        Invalidates the snapshot."""
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("set_routes: capacity must be >= 0 (0 switches the routes off)")
+        nat.check(self.h, self.lib.npp_set_routes(self.h, capacity))
+        self._route_views = self._archive_route_views = None
+
+    def route_views(self):
+        """(actions u8 [N, 2, cap], header i32 [N, 16]): CUDA views (no copy) of the handle's route buffers and headers,
+        rewritten in stream order.  Header words 0-5 describe the current route (len, bits, frame_skip, frames, last flags, level),
+        6-11 the finished one, word 12 says which of the two buffers holds the current route."""
+        if getattr(self, "_route_views", None) is None:
+            a, hd, cap = C.c_void_p(), C.c_void_p(), C.c_int(0)
+            nat.check(self.h, self.lib.npp_route_view(self.h, C.byref(a), C.byref(hd), C.byref(cap)))
+            self._route_views = (_device_tensor(a.value, self.n * 2 * cap.value, torch.uint8, self.device).view(self.n, 2, cap.value),
+                                 _device_tensor(hd.value, self.n * 16, torch.int32, self.device).view(self.n, 16))
+        return self._route_views
+
+    def archive_route_views(self):
+        """(actions u8 [n_slots, cap], header i32 [n_slots, 8]): strided CUDA views (no copy) over the archive's records of
+        each slot's route -- header words as in route_views (0-5; 6-7 are 0)."""
+        if getattr(self, "_archive_route_views", None) is None:
+            rec, off, stride = C.c_void_p(), C.c_int64(), C.c_int64()
+            nat.check(self.h, self.lib.npp_archive_route_view(self.h, C.byref(rec), C.byref(off), C.byref(stride)))
+            ns, off, stride = self.archive_num_slots(), off.value, stride.value
+            cap = self.archive_record_bytes() - (off + 8) * 4
+            words = _device_tensor(rec.value, ns * stride, torch.int32, self.device)
+            raw = _device_tensor(rec.value, ns * stride * 4, torch.uint8, self.device)
+            self._archive_route_views = (torch.as_strided(raw, (ns, cap), (stride * 4, 1), (off + 8) * 4),
+                                         torch.as_strided(words, (ns, 8), (stride, 1), off))
+        return self._archive_route_views
 
     # ---- cell index over the archive (include/npp_amd.h npp_archive_cells_create; DESIGN.md 17) ------------------------
     def archive_cells_create(self, seed=0, enable=True):

@@ -49,6 +49,29 @@ def decode_input_to_controls(input_byte):
     return ((b >> 1) & 1) - ((b >> 2) & 1), b & 1
 
 
+def route_to_replay(map_data, actions, frame_skip, success):
+    """An action route (NppVecEnvironment.finished_routes / archive_routes: "actions", "frame_skip") as a CompactReplay of the
+    level it was played on: every action becomes its input byte, frame_skip times, as the env holds an action's controls for
+    frame_skip ticks (base_environment.py:524-609).  The last action of an episode may have run fewer ticks; a replay stops at
+    won / died anyway.  map_data: the level's raw bytes (or values 0..255)."""
+    from .vec_env import ACTION_TABLE, controls_to_input_byte
+
+    if isinstance(map_data, (bytes, bytearray)):
+        m = bytes(map_data)
+    else:
+        m = np.asarray(map_data)
+        m = m.astype(np.uint8).tobytes()
+    frame_skip = int(frame_skip)
+    if frame_skip <= 0:
+        raise ValueError("route_to_replay: frame_skip must be > 0 (an empty route has none)")
+    inputs = []
+    for a in np.asarray(actions, dtype=np.int64).ravel():
+        if not 0 <= a < len(ACTION_TABLE):
+            raise ValueError("route_to_replay: action %d is not in 0..5" % a)
+        inputs += [controls_to_input_byte(*ACTION_TABLE[a])] * frame_skip
+    return CompactReplay(m, inputs, success=bool(success), version=1)
+
+
 def validate_replays(replays, device=0):
     """Run all replays at once (one env per replay).  Returns a list of dicts: ticks run until termination
     (or all inputs), won, died, final position."""

@@ -52,6 +52,22 @@ def expand_category_weights(category_weights, level_categories):
     return np.array([float(category_weights.get(c, 0.0)) / count[c] for c in cats], dtype=np.float64)
 
 
+def route_capacity_for(record_routes, route_capacity, frame_skip, truncation_limit):
+    """The `capacity` NppVecEnvironment hands to NppBatch.set_routes (0 = routes off); needs no device.  The default is the longest
+    episode the env can have: its largest truncation limit ("dynamic": MAX_TIME_IN_FRAMES) divided by frame_skip, rounded up -- 2500
+    actions at 10 000 frames and frame_skip 4."""
+    if not record_routes:
+        if route_capacity is not None:
+            raise ValueError("route_capacity without record_routes=True")
+        return 0
+    if route_capacity is not None:
+        if int(route_capacity) != route_capacity or int(route_capacity) <= 0:
+            raise ValueError("route_capacity must be a positive number of actions")
+        return int(route_capacity)
+    limit = MAX_TIME_IN_FRAMES if isinstance(truncation_limit, str) else int(np.max(truncation_limit))
+    return max(1, -(-limit // int(frame_skip)))
+
+
 def controls_to_input_byte(hor, jump):
     """(hor, jump) -> replay input byte (bit0 jump, bit1 right, bit2 left; replay/replay_executor.py:61-84)."""
     return (1 if jump else 0) | (2 if hor > 0 else 0) | (4 if hor < 0 else 0)
@@ -124,6 +140,17 @@ class NppVecEnvironment:
     restart_from_archive(done_mask) restarts the masked envs from slots drawn by visit count among the cells of their own level
     (checkpoint_seed seeds the draws); archive_store is refused while the index owns the slots.
 
+    Action routes (the reference's `_action_sequence`, base_environment.py:186 / :517 / :1677 / :2114, and what a StateCheckpoint
+    is made of, state_checkpoint.py): record_routes=True keeps, on the device, the actions that led every env from
+    its spawn to where it is, and the route of the episode that ended last.  get_action_sequence_length() / get_current_action_sequence(env)
+    are the reference's two accessors (:2332-2349); finished_routes(mask) returns the last finished episodes (a won episode's
+    solution outlives the auto-reset); with checkpoint_slots, every slot carries the route of its state: archive_routes(slot_ids)
+    exports them with the StateCheckpoint fields the device knows, and restart() / reset(options={"checkpoint": {"slots": ...}})
+    leave the slot's route as the env's own, as reset(options={"checkpoint": seq}) leaves seq.  route_capacity: actions per route
+    (default: the longest episode the env can have, route_capacity_for; about 5 KB per env at 10 000 frames and frame_skip 4);
+    longer episodes set bit 1 of the route's "bits" and drop the actions past the capacity.  replay.route_to_replay() writes a
+    route as a replay file.  Off by default: nothing is allocated or launched.
+
     Minimal observation mode (the reference's EnvironmentConfig.observation_mode = MINIMAL, config.py:17-20):
     observation_mode="minimal" makes `obs` the reference's small observation (npp_environment.py:2232-2270): minimal_observation
     [N, 40] f32 (compute_minimal_observation, observation_processor.py:505-567: 12 physics, 8 path guidance, 4 mines x 4, 4
@@ -147,10 +174,12 @@ class NppVecEnvironment:
                  enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False, state_stack_size=4,
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
-                 augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0):
+                 augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False,
+                 route_capacity=None):
         assert output in ("torch", "numpy")
         if int(checkpoint_slots) < 0:
             raise ValueError("checkpoint_slots must be >= 0")
+        self.route_capacity = route_capacity_for(record_routes, route_capacity, frame_skip, truncation_limit)
         if checkpoint_cells and not checkpoint_slots:
             raise ValueError("checkpoint_cells needs checkpoint_slots > 0 (the cell index allocates the archive's slots)")
         if checkpoint_slots and level_weights is not None:
@@ -243,6 +272,8 @@ class NppVecEnvironment:
             if not hasattr(self, "_host_stack"):
                 self._host_stack = {}
         self.checkpoint_slots = int(checkpoint_slots)
+        if self.route_capacity:   # (before the archive: its records then carry each slot's route)
+            self._b.set_routes(self.route_capacity)
         if self.checkpoint_slots:
             self._b.archive_create(self.checkpoint_slots)
             with self._b._ctx():
@@ -530,6 +561,92 @@ class NppVecEnvironment:
         self.last_restart_slots = self._b.archive_select(mask)
         return self.restart(self.last_restart_slots)
 
+    # -- action routes (DESIGN.md 18) -------------------------------------------------------------------------------
+    def _need_routes(self, what):
+        if not self.route_capacity:
+            raise RuntimeError("%s: this env was created without record_routes (no action routes)" % what)
+
+    def get_action_sequence_length(self):
+        """[N] int32: the number of actions on every env's current route (base_environment.py:2341-2349, batched).  A device
+        view for output="torch" (rewritten by the next step), a host copy for "numpy"."""
+        self._need_routes("get_action_sequence_length")
+        lens = self._b.route_views()[1][:, 0]
+        if self.output == "torch":
+            return lens
+        self._b.join()
+        with self._b._ctx():
+            return lens.cpu().numpy()
+
+    def get_current_action_sequence(self, env):
+        """u8 array: the actions that led env `env` from its spawn to its current state (base_environment.py:2332-2339); after
+        reset(options={"checkpoint": seq}) that is seq, after a restart from the archive the slot's route.  Synchronises."""
+        self._need_routes("get_current_action_sequence")
+        act, hdr = self._b.route_views()
+        self._b.join()
+        with self._b._ctx():
+            h = hdr[int(env)].cpu().numpy()
+            return act[int(env), int(h[12]), :int(h[0])].cpu().numpy()
+
+    @staticmethod
+    def _route_dict(hdr, actions):
+        return {"actions": np.array(actions[:int(hdr[0])], dtype=np.uint8), "frame_count": int(hdr[3]), "level": int(hdr[5]),
+                "frame_skip": int(hdr[2]), "bits": int(hdr[1])}
+
+    def finished_routes(self, mask=None):
+        """The route of the episode that ended last, for every env (or those with a non-zero mask byte) that has one: a list of
+        dicts {"env", "actions" u8 array, "frame_count", "level", "frame_skip", "bits" (1 = actions were dropped at the capacity,
+        2 = not replayable), "flags" (the flags byte of the episode's last step: 1 won, 2 dead, 8 truncated)} -- the keys of
+        StateCheckpoint.get_compact_representation() the device knows.  The bytes stay valid on the device until the env's next
+        episode ends.  Synchronises."""
+        self._need_routes("finished_routes")
+        act, hdr = self._b.route_views()
+        self._b.join()
+        with self._b._ctx():
+            h = hdr.cpu().numpy()
+            envs = np.flatnonzero((h[:, 6] > 0) | (h[:, 7] != 0))
+            if mask is not None:
+                m = mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+                envs = envs[m[envs] != 0]
+            if not len(envs):
+                return []
+            idx = torch.from_numpy(envs).to(self._b.device)
+            a = act[idx, torch.from_numpy(1 - h[envs, 12]).to(self._b.device).long()].cpu().numpy()
+        out = []
+        for k, e in enumerate(envs):
+            d = self._route_dict(h[e, 6:12], a[k])
+            d.update(env=int(e), flags=int(h[e, 10]))
+            out.append(d)
+        return out
+
+    def archive_routes(self, slot_ids):
+        """The routes of archive slots, for export: a list (one per slot id, None for an empty slot) of dicts with the keys of
+        StateCheckpoint.get_compact_representation() the device knows -- "cell" (x, y) 24 px cell, "actions" u8 array,
+        "frame_count", "position", "velocity", "switch" (from the archive's meta rows) -- and "slot", "level", "frame_skip",
+        "bits".  Synchronises."""
+        if not self.checkpoint_slots:
+            raise RuntimeError("archive_routes: this env was created without checkpoint_slots (no checkpoint archive)")
+        self._need_routes("archive_routes")
+        slots = np.asarray(slot_ids.cpu() if isinstance(slot_ids, torch.Tensor) else slot_ids, dtype=np.int64).ravel()
+        if len(slots) and (slots.min() < 0 or slots.max() >= self.checkpoint_slots):
+            raise ValueError("archive_routes: slot ids must be in [0, checkpoint_slots)")
+        act, hdr = self._b.archive_route_views()
+        meta = self._b.archive_meta()
+        self._b.join()
+        with self._b._ctx():
+            idx = torch.from_numpy(slots).to(self._b.device)
+            h, a = hdr[idx].cpu().numpy(), act[idx].cpu().numpy()
+            m = {k: v[idx].cpu().numpy() for k, v in meta.items()}
+        out = []
+        for k, s in enumerate(slots):
+            if not m["stored"][k]:
+                out.append(None)
+                continue
+            d = self._route_dict(h[k], a[k])
+            d.update(slot=int(s), cell=(int(m["cell_x"][k]), int(m["cell_y"][k])), position=(float(m["x"][k]), float(m["y"][k])),
+                     velocity=(float(m["vx"][k]), float(m["vy"][k])), switch=bool(m["switch_activated"][k]))
+            out.append(d)
+        return out
+
     def action_space_sample(self):
         """uint8 [N] uniform actions from the generator reset(seed=...) seeds."""
         return self._rng.integers(0, 6, size=self.num_envs).astype(np.uint8)
@@ -638,7 +755,7 @@ class NppEnvironment:
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
-                 checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0):
+                 checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -663,7 +780,7 @@ class NppEnvironment:
                                     enable_augmentation=enable_augmentation, augmentation_p=augmentation_p,
                                     augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed,
                                     checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
-                                    checkpoint_seed=checkpoint_seed)
+                                    checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -688,6 +805,14 @@ class NppEnvironment:
         """Store the current state in slot `slot` of the checkpoint archive (checkpoint_slots > 0); returns the status (0 =
         stored).  reset(options={"checkpoint": {"slots": [slot]}}) restarts from it."""
         return int(self._v.archive_store(np.array([int(slot)], dtype=np.int32))[0])
+
+    def get_current_action_sequence(self):
+        """The actions taken since the last reset, as a list of ints (base_environment.py:2332-2339); record_routes=True."""
+        return [int(a) for a in self._v.get_current_action_sequence(0)]
+
+    def get_action_sequence_length(self):
+        """len(get_current_action_sequence()) without the copy of the bytes (base_environment.py:2341-2349)."""
+        return int(self._v.get_action_sequence_length()[0])
 
     def step(self, action):
         obs, rew, term, trunc, info = self._v.step(np.array([int(action)], dtype=np.uint8))
