@@ -230,6 +230,52 @@ int npp_set_minimal_observation(npp_handle h, int enable);
 int npp_minimal_encode_host(const uint32_t *state_a, const double *planes, int count, float *out);
 int npp_minimal_observation(npp_handle h, float *d_out /* [N,40] */, int32_t *d_status /* [N] or NULL */);
 
+/* Path-direction action masking: the mask the reference's ENV returns.  Its observation does not carry
+ * Ninja.get_valid_action_mask() as it stands: _get_action_mask_with_path_update (gym_environment/base_environment.py:3050,
+ * 3075-3107) first runs _detect_straight_path_direction (:3109-3253) -- the ninja's graph node, the level cache's multi-hop
+ * direction to the current goal (the exit switch, the exit door once the switch is activated), classified as left / right / down /
+ * none -- and in masking mode "hard" (the default, nsim.py:48; the annealing schedule hard -> soft -> none of
+ * reward_config.py:815-865) the last stage of get_valid_action_mask (ninja.py:743-800) removes what a straight path makes pointless:
+ * left keeps NOOP and LEFT, right keeps NOOP and RIGHT, down removes the three jump actions.  d_action_mask of npp_step_out is that
+ * function with the stage inert; these entry points add the stage, from the reachability tables of npp_reachability (built at the
+ * first call, the graph of the spawn: graph updates inside an episode are not modelled) and the exact fp64 position, in a launch of
+ * its own behind the step / observe / reset launch that produced the observation.  The rule is one function, npp_pathmask.hpp,
+ * compiled for the device and for npp_path_direction_host.  Off by default: nothing is allocated or launched, every output is as
+ * before.
+ * npp_set_action_masking(h, mode): 0 off, 1 hard, 2 soft; may change between any two steps.  The first non-zero mode allocates the
+ *   counters (17 bytes per env); mode 0 frees nothing and launches nothing.  < 0 or > 2: NPP_ERR_INVALID.
+ * npp_path_action_mask(h, d_action_mask, d_direction, d_status): the launch, on the handle's stream, after joining an observation
+ *   overlap.  Call it once per observation, after the npp_step / npp_observe / npp_reset that produced it.  d_direction (i8[n_envs],
+ *   may be NULL): 0 none, 1 left, 2 right, 3 down.  Hard mode: the six bytes of every env in d_action_mask (i8[n_envs][6], the
+ *   step's output) are filtered in place (NULL: NPP_ERR_INVALID); soft mode: d_action_mask is not touched (may be NULL) -- the
+ *   direction is what a trainer's logit bias needs.  d_status (i32[n_envs], may be NULL): 1 where the direction was classified from
+ *   the graph (the reference's `_deterministic_mask_applied_count += 1`), 0 where it is none or the near-goal line-of-sight hint.
+ *   NPP_ERR_STATE in mode 0 and without levels; NULL handle: NPP_ERR_INVALID; NPP_ERR_UNSUPPORTED exactly where npp_reachability is
+ *   (several exit switches; an entity repositioned with npp_set_entity_pos) -- the mask is then left unfiltered.
+ * Counters, per env (the project's own definition; the reference also counts its terminal observation, which an auto-resetting
+ *   device env never sees: parity of the two info numbers is unpinned): `observed` = calls of npp_path_action_mask since the env's last
+ *   reset, `applied` = those with d_status 1.  When the npp_step before the call ended the env's episode and auto-reset it (its flags
+ *   byte; without NPP_FLAG_AUTORESET never), both are latched into last_observed / last_applied and restart at this observation;
+ *   npp_reset restarts the live ones, and so does switching the mode from 0 to 1 or 2 (observations went by uncounted).  They count
+ *   CALLS: a second call for the same state (a caller that observes again between two steps, as NppVecEnvironment.restart does
+ *   for the envs it leaves alone) counts again.  The handle remembers the flags row of the last npp_step: a caller's d_flags must stay allocated
+ *   until this call (with d_flags NULL a row of the handle's is used).  After npp_step_many nothing is latched.  The counters are NOT
+ *   part of archive / snapshot records: a restore leaves them as they are.
+ * npp_path_mask_stats_view: device views u32[n_envs] of the four (any pointer may be NULL), valid until npp_destroy;
+ *   NPP_ERR_STATE before the first non-zero mode. */
+int npp_set_action_masking(npp_handle h, int mode);
+int npp_path_action_mask(npp_handle h, int8_t *d_action_mask /* [N,6] in/out or NULL */, int8_t *d_direction /* [N] or NULL */,
+                         int32_t *d_status /* [N] or NULL */);
+int npp_path_mask_stats_view(npp_handle h, const uint32_t **d_observed, const uint32_t **d_applied, const uint32_t **d_last_observed,
+                             const uint32_t **d_last_applied);
+/* Host-only: the detector the device kernel runs (npp_pathmask.hpp compiles for both; base_environment.py:3109-3253 with
+ * find_ninja_node, pathfinding_utils.py:1331-1496, and get_multi_hop_direction, path_distance_cache.py:162-185) on `count` positions
+ * (f64[count][2]) of one level with switch_activated u8[count].  direction_out i8[count]: 0 none, 1 left, 2 right, 3 down;
+ * from_graph_out u8[count] (may be NULL): npp_path_action_mask's d_status; status (one i32, may be NULL): bit 1 = level unsupported
+ * (npp_reachability refuses it). */
+int npp_path_direction_host(const double *map, int64_t n, const double *pos, const uint8_t *switch_activated, int count,
+                            int8_t *direction_out, uint8_t *from_graph_out, int32_t *status);
+
 /* The whole gray frame of envs [env0, env0 + count): what NPlayHeadless.render() returns in grayscale mode
  * (nplay_headless.py:144-156, nsim_renderer.py:71-134).  d_out: u8[count][600][1056]. */
 int npp_render_frame(npp_handle h, int env0, int count, uint8_t *d_out);

@@ -42,6 +42,7 @@ EXPORTS = [
     "npp_archive_cells_create", "npp_archive_explore", "npp_archive_select", "npp_archive_cells_view",
     "npp_archive_cell_keys_host", "npp_archive_cell_pick_host",
     "npp_set_routes", "npp_route_view", "npp_archive_route_view", "npp_route_apply_host",
+    "npp_set_action_masking", "npp_path_action_mask", "npp_path_mask_stats_view", "npp_path_direction_host",
 ]
 
 
@@ -168,6 +169,11 @@ def lib():
     L.npp_route_view.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.npp_archive_route_view.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.npp_route_apply_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_set_action_masking.argtypes = [H, C.c_int]
+    L.npp_path_action_mask.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_path_mask_stats_view.argtypes = [H] + [C.POINTER(C.c_void_p)] * 4
+    L.npp_path_direction_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
     L.npp_num_envs.argtypes = [H]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:

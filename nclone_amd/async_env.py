@@ -85,12 +85,17 @@ class NppAsyncVecEnvironment:
     (NppVecEnvironment(enable_graph_observations=True) has them), and no minimal observation mode: observation_mode other than
     "full" is refused (NppVecEnvironment(observation_mode="minimal") has it).  No frame augmentation (there are no visual
     observations here): enable_augmentation is refused likewise (NppVecEnvironment(enable_augmentation=True) has it).
+    No path-direction action masking: action_masking_mode other than None / "none" raises ValueError
+    (NppVecEnvironment(action_masking_mode="hard") has it).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
-                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False):
+                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None):
         assert output in ("torch", "numpy")
+        if action_masking_mode not in (None, "none"):
+            raise ValueError("NppAsyncVecEnvironment has no path-direction action masking (action_masking_mode=%r): "
+                             "NppVecEnvironment(action_masking_mode=...) has it" % (action_masking_mode,))
         if checkpoint_slots or checkpoint_cells:
             raise NotImplementedError("NppAsyncVecEnvironment has no checkpoint archive (checkpoint_slots / checkpoint_cells): its sub-batches are "
                                       "separate handles, and a slot restores only into envs of the handle that stored it; "

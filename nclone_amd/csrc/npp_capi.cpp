@@ -270,6 +270,16 @@ struct Routes {
     int rows = 0;
 };
 
+// path-direction action masking (npp_set_action_masking / npp_path_action_mask, npp_pathmask.hip): the mode, the per-env counters
+// and where the last step wrote its flags row.  Allocated by the first call that switches a mode on, kept for the handle's life.
+struct PathMask {
+    int mode = 0;                        // 0 off, 1 hard, 2 soft
+    DevBuf<uint32_t> counters;           // [4][n] observed | applied | last_observed | last_applied
+    DevBuf<uint8_t> flagbuf;             // [n] the step's flags row when the caller asked for none (as Pool::flags)
+    const uint8_t *flags = nullptr;      // flags row of the last npp_step not yet consumed by npp_path_action_mask
+    uint32_t *plane(int k, int n) const { return counters.get() + (size_t)k * n; }
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -305,6 +315,7 @@ struct npp_handle_s {
     Archive ar;
     Cells cells;
     Routes rt;
+    PathMask pm;
 };
 
 
@@ -811,6 +822,10 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
     }
     HIP_TRY(h, launch_reset(a, h->stream));
     if (int rc = route_event(h, ROUTE_EV_FLIP, a.reset_mask)) return rc;   // (action routes) the episode of a reset env is over
+    if (h->pm.mode) {   // (action masking) the counters count observations since the env's last reset
+        HIP_TRY(h, launch_path_mask_restart(h->n, a.reset_mask, h->pm.plane(0, h->n), h->pm.plane(1, h->n), h->stream));
+        h->pm.flags = nullptr;
+    }
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));  // env_mask is caller memory: finish the copy
     return NPP_OK;
 }
@@ -1746,10 +1761,14 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
     if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
     const bool pool = h->pool.on && (h->flags & NPP_FLAG_AUTORESET);
-    if (!pool && !h->rt.cap) return step_impl(h, d_actions, frame_skip, out);
+    if (!pool && !h->rt.cap && !h->pm.mode) return step_impl(h, d_actions, frame_skip, out);
     npp_step_out o;
     std::memset(&o, 0, sizeof(o));
     if (out) o = *out;
+    if (h->pm.mode) {   // action masking: npp_path_action_mask reads the step's flags row (the counters' latch)
+        if (!o.d_flags) o.d_flags = h->pm.flagbuf.get();
+        h->pm.flags = o.d_flags;
+    }
     if (h->rt.cap) {   // action routes: the append behind the step reads the step's flags and frames rows
         ON_DEVICE_JOINED(h);
         if (int rc = route_rows(h, o, 1)) return rc;
@@ -1775,6 +1794,7 @@ int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame
     a.n_ticks = frame_skip;
     a.n_steps = n_steps;
     a.mode = 0;
+    h->pm.flags = nullptr;   // (action masking) several steps: no single flags row describes the observation
     npp_step_out o;
     if (h->rt.cap) {   // action routes: the append walks the launch's n_steps flags / frames rows
         std::memset(&o, 0, sizeof(o));
@@ -2090,6 +2110,73 @@ int npp_minimal_observation(npp_handle h, float *d_out, int32_t *d_status) {
     return obs_launch(h, a, false, tables, [&](const KernelArgs &ka, hipStream_t st) {
         return launch_reach(ka, r.hdr.get(), r.blob.get(), r.key.get(), r.cache.get(), r.miss(), nullptr, nullptr, d_status, nullptr, d_out, rows, st);
     });
+}
+
+int npp_set_action_masking(npp_handle h, int mode) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_action_masking: NULL handle");
+    if (mode < 0 || mode > 2) return fail(h, NPP_ERR_INVALID, "npp_set_action_masking: mode must be 0 (off), 1 (hard) or 2 (soft)");
+    PathMask &pm = h->pm;
+    if (mode && !pm.counters) {
+        ON_DEVICE(h);
+        DevBuf<uint32_t> c;
+        DevBuf<uint8_t> f;
+        if (c.alloc(4 * (size_t)h->n) != hipSuccess || f.alloc((size_t)h->n) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, NPP_ERR_HIP, "npp_set_action_masking: hipMalloc of the counters failed");
+        }
+        HIP_TRY(h, hipMemsetAsync(c.get(), 0, c.bytes(), h->stream));
+        HIP_TRY(h, hipMemsetAsync(f.get(), 0, f.bytes(), h->stream));
+        pm.counters = std::move(c);
+        pm.flagbuf = std::move(f);
+    }
+    if (!mode || !pm.mode) pm.flags = nullptr;   // off, or on again: no step of this mode has run
+    if (mode && !pm.mode) {   // off -> on: observations went by uncounted, so the live counters restart (the latched ones stay)
+        ON_DEVICE(h);
+        HIP_TRY(h, hipMemsetAsync(pm.plane(0, h->n), 0, 2 * (size_t)h->n * sizeof(uint32_t), h->stream));
+    }
+    pm.mode = mode;
+    return NPP_OK;
+}
+
+int npp_path_action_mask(npp_handle h, int8_t *d_action_mask, int8_t *d_direction, int32_t *d_status) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_path_action_mask: NULL handle");
+    PathMask &pm = h->pm;
+    if (!pm.mode) return fail(h, NPP_ERR_STATE, "npp_path_action_mask: action masking is off (npp_set_action_masking)");
+    if (pm.mode == 1 && !d_action_mask) return fail(h, NPP_ERR_INVALID, "npp_path_action_mask: hard mode needs d_action_mask");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_path_action_mask: no levels loaded");
+    if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_path_action_mask: exit switch / door repositioned with npp_set_entity_pos");
+    ON_DEVICE_JOINED(h);
+    if (int rc = ensure_reach(h)) return rc;   // (refuses what npp_reachability refuses, with its message; built on the first call)
+    const LevelSet &L = h->ls;
+    PathMaskArgs a{};
+    a.n = h->n;
+    a.f64 = h->env.f64.get();
+    a.ent_bits = L.ent.get();
+    a.env_level = h->env.level.get();
+    a.hdr = L.hdr.get();
+    a.rh = L.reach.hdr.get();
+    a.rblob = L.reach.blob.get();
+    a.flags = pm.flags;
+    a.end_bits = (h->flags & NPP_FLAG_AUTORESET) ? (int)(NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED) : 0;
+    a.mask = pm.mode == 1 ? d_action_mask : nullptr;
+    a.dir = d_direction;
+    a.status = d_status;
+    a.observed = pm.plane(0, h->n); a.applied = pm.plane(1, h->n);
+    a.last_observed = pm.plane(2, h->n); a.last_applied = pm.plane(3, h->n);
+    HIP_TRY(h, launch_path_mask(a, h->stream));
+    pm.flags = nullptr;   // consumed: a second call before the next step latches nothing
+    return NPP_OK;
+}
+
+int npp_path_mask_stats_view(npp_handle h, const uint32_t **d_observed, const uint32_t **d_applied, const uint32_t **d_last_observed,
+                             const uint32_t **d_last_applied) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_path_mask_stats_view: NULL handle");
+    if (!h->pm.counters) return fail(h, NPP_ERR_STATE, "npp_path_mask_stats_view: action masking was never switched on (npp_set_action_masking)");
+    if (d_observed) *d_observed = h->pm.plane(0, h->n);
+    if (d_applied) *d_applied = h->pm.plane(1, h->n);
+    if (d_last_observed) *d_last_observed = h->pm.plane(2, h->n);
+    if (d_last_applied) *d_last_applied = h->pm.plane(3, h->n);
+    return NPP_OK;
 }
 
 int npp_graph_observation(npp_handle h, float *d_node_feats, uint16_t *d_edge_index, uint8_t *d_node_mask, uint8_t *d_edge_mask, int flags) {

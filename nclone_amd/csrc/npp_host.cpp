@@ -9,6 +9,7 @@
 #include "npp_augment.hpp"
 #include "npp_cells.hpp"
 #include "npp_minimal.hpp"
+#include "npp_pathmask.hpp"
 #include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
 #include "npp_route.hpp"
@@ -128,6 +129,26 @@ int npp_route_apply_host(int32_t *hdr, uint8_t *actions, int capacity, int autor
         default: return fail(nullptr, NPP_ERR_INVALID, "npp_route_apply_host: event " + std::to_string(i) + ": unknown kind");
         }
     }
+    return NPP_OK;
+}
+
+int npp_path_direction_host(const double *map, int64_t n, const double *pos, const uint8_t *switch_activated, int count,
+                            int8_t *direction_out, uint8_t *from_graph_out, int32_t *status) {
+    if (!map || count < 0 || (count > 0 && (!pos || !switch_activated || !direction_out)))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_path_direction_host: bad arguments");
+    ReachBuilt R;
+    std::string err;
+    if (!build_reach(map, n, R, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_path_direction_host: " + err);
+    ReachHdr H;
+    std::vector<unsigned char> blob;
+    pack_reach(R, H, blob);
+    const ReachTabs T{&H, blob.data() + H.base};
+    for (int k = 0; k < count; k++) {
+        int from_graph = 0;
+        direction_out[k] = (int8_t)reach_path_direction(T, pos[2 * k], pos[2 * k + 1], switch_activated[k] != 0, &from_graph);
+        if (from_graph_out) from_graph_out[k] = (uint8_t)from_graph;
+    }
+    if (status) *status = H.supported ? 0 : 2;
     return NPP_OK;
 }
 

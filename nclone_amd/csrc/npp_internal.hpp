@@ -296,6 +296,24 @@ hipError_t launch_reach(const KernelArgs &a, const ReachHdr *rh, const unsigned 
                         const float *sc_rows, hipStream_t s);
 // envs selected by a.reset_mask (NULL = all) lose their cached vector and their miss dictionary (a new level)
 hipError_t launch_reach_drop(const KernelArgs &a, uint32_t *key, const ReachMissDev &md, hipStream_t s);
+// npp_pathmask.hip: path-direction action masking (see npp_set_action_masking in include/npp_amd.h; the rule: npp_pathmask.hpp)
+struct PathMaskArgs {
+    int n;
+    const double *f64;            // [NF64][n]
+    const uint32_t *ent_bits;     // [n_words_max][n]
+    const int32_t *env_level;     // [n]
+    const LevelHdr *hdr;          // [n_levels]
+    const ReachHdr *rh;           // [n_levels] the reachability tables (npp_reach.hpp)
+    const unsigned char *rblob;
+    const uint8_t *flags;         // [n] flags row of the step that produced this observation; null = no step did
+    int end_bits;                 // flags bits after which the step kernel auto-reset the env (0 without auto-reset)
+    int8_t *mask;                 // [n][6] in / out, null = leave the mask alone (soft mode)
+    int8_t *dir;                  // [n] or null
+    int32_t *status;              // [n] or null: 1 = classified from the graph
+    uint32_t *observed, *applied, *last_observed, *last_applied;   // [n] each
+};
+hipError_t launch_path_mask(const PathMaskArgs &a, hipStream_t s);
+hipError_t launch_path_mask_restart(int n, const uint8_t *mask, uint32_t *observed, uint32_t *applied, hipStream_t s);
 hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n, const int *edge, int parts, uint8_t *phase, hipStream_t s);
 hipError_t launch_spin(long long ticks, hipStream_t s);   // a bounded idle wavefront (stream calibration)
 // order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)

@@ -62,6 +62,7 @@ _FIELDS = {
     "mine_sdf_features": ((3,), torch.float32),
     "reach_status": ((), torch.int32),
     "minimal_observation": ((40,), torch.float32),
+    "path_direction": ((), torch.int8),
 }
 # graph observations (NppBatch.graph_observation): shape per env and dtype; kept out of the packed output block, which numpy-mode
 # environments copy to the host every step
@@ -70,7 +71,7 @@ GRAPH_KEYS = {"graph_node_feats": ((2500, 6), torch.float32), "graph_edge_index"
 _ALWAYS = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags", "terminal_state")
 _PACKED = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags")
 _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_frame", "global_view", "reachability_features",
-             "mine_sdf_features", "reach_status", "minimal_observation")
+             "mine_sdf_features", "reach_status", "minimal_observation", "path_direction")
 
 
 AUG_SCALES = {"light": 0.7, "medium": 1.0, "strong": 1.3}   # frame_augmentation.py:57
@@ -216,6 +217,8 @@ class NppBatch:
             self.stream = stream if stream is not None else torch.cuda.current_stream()
             nat.check(self.h, self.lib.npp_set_stream(self.h, C.c_void_p(self.stream.cuda_stream)))
         self._enabled = set(_ALWAYS)
+        self._masking = 0         # action masking mode (set_action_masking)
+        self._mask_stats = None   # views of the handle's counters (path_mask_stats): the handle's own buffers, alive as long as it is
         for k in outputs:
             if k not in _OPTIONAL:
                 raise ValueError("unknown output %r (optional outputs: %s)" % (k, ", ".join(_OPTIONAL)))
@@ -247,7 +250,7 @@ class NppBatch:
             nat.check(self.h, self.lib.npp_set_minimal_observation(self.h, 1))
 
     def enable_outputs(self, *names):
-        """Add optional outputs (spatial_context, positions, work, switch_states, player_frame, global_view, reachability_features, mine_sdf_features, reach_status, minimal_observation); the output
+        """Add optional outputs (spatial_context, positions, work, switch_states, player_frame, global_view, reachability_features, mine_sdf_features, reach_status, minimal_observation, path_direction); the output
         block is re-allocated, so tensors obtained earlier are stale."""
         new = [k for k in names if k not in self._enabled]
         for k in new:
@@ -405,8 +408,12 @@ class NppBatch:
         """actions: uint8 CUDA tensor [K, N].  K Gymnasium steps in one launch (open-loop sequences: checkpoint replay, fixed
         plans).  Returns (flags u8 [K, N], reward f32 [K, N], frames i16 [K, N]); observations of the last step land in
         self.game_state etc.; with auto-reset, envs that terminate mid-sequence restart on the spot.  Nothing is pushed onto
-        the frame stacks (NppVecEnvironment re-pads them from the observation after a checkpoint replay)."""
+        the frame stacks (NppVecEnvironment re-pads them from the observation after a checkpoint replay).
+        Raises ValueError while action masking is on (set_action_masking): its counters need every observation."""
         assert actions.dtype == torch.uint8 and actions.is_cuda and actions.dim() == 2 and actions.shape[1] == self.n
+        if self._masking:
+            raise ValueError("step_many with action masking on: the detector runs once per observation and the launch's inner "
+                             "steps have none (set_action_masking(0) first)")
         K = int(actions.shape[0])
         with self._ctx():   # allocations, the launch and the copies below are all ordered on the handle's stream
             actions = actions.contiguous()
@@ -491,6 +498,44 @@ class NppBatch:
         st = C.c_void_p(t["reach_status"].data_ptr()) if "reach_status" in t else None
         nat.check(self.h, self.lib.npp_minimal_observation(self.h, C.c_void_p(out.data_ptr()), st))
         return out
+
+    # ---- path-direction action masking (include/npp_amd.h npp_set_action_masking) ---------------------
+    MASKING_MODES = {None: 0, "none": 0, "off": 0, "hard": 1, "soft": 2, 0: 0, 1: 1, 2: 2}
+
+    def set_action_masking(self, mode):
+        """The reference env's action-masking mode (reward_config.py:815-865): "hard" -- path_action_mask() filters the block's
+        action_mask by the straight-path direction, "soft" -- it writes the direction only, None / "none" -- off (default: nothing
+        is launched).  May change between any two steps."""
+        if mode not in self.MASKING_MODES:
+            raise ValueError('action masking mode must be None, "none", "hard" or "soft", not %r' % (mode,))
+        self._masking = self.MASKING_MODES[mode]
+        nat.check(self.h, self.lib.npp_set_action_masking(self.h, self._masking))
+
+    def path_action_mask(self, status_out=None):
+        """One call per observation, after step() / observe() / reset(): the reference's _detect_straight_path_direction for every
+        env, into the block's path_direction (i8 [N]: 0 none, 1 left, 2 right, 3 down; enable_outputs("path_direction")), and in
+        hard mode its mask stage applied to the block's action_mask in place.  status_out: optional int32 CUDA tensor [N], 1 where
+        the direction came from the graph.  Enqueued on the handle's stream, so to_host() after it stages the filtered mask."""
+        t = self.out.t
+        d = C.c_void_p(t["path_direction"].data_ptr()) if "path_direction" in t else None
+        st = None
+        if status_out is not None:
+            assert status_out.dtype == torch.int32 and status_out.is_cuda and status_out.numel() == self.n and status_out.is_contiguous()
+            st = C.c_void_p(status_out.data_ptr())
+        nat.check(self.h, self.lib.npp_path_action_mask(self.h, C.c_void_p(self.action_mask.data_ptr()), d, st))
+
+    def path_mask_stats(self):
+        """{"observed", "applied", "last_observed", "last_applied"}: int32 CUDA views [N] of the handle's counters (no copy; the
+        device holds them as u32) -- detector calls since the env's last reset, those classified from the graph, and both as
+        latched when the env's last episode ended in an auto-reset.  They count calls of path_action_mask(): a second call for the
+        same state counts again.  reset() and switching the mode from off to on restart the live ones.  Not part of archive /
+        snapshot records."""
+        if self._mask_stats is None:
+            p = [C.c_void_p() for _ in range(4)]
+            nat.check(self.h, self.lib.npp_path_mask_stats_view(self.h, *[C.byref(x) for x in p]))
+            self._mask_stats = {k: _device_tensor(x.value, self.n, torch.int32, self.device)
+                                for k, x in zip(("observed", "applied", "last_observed", "last_applied"), p)}
+        return self._mask_stats
 
     def graph_observation(self, node_feats=None, edge_index=None, node_mask=None, edge_mask=None, rewrite_all=False):
         """The graph observations of every env (include/npp_amd.h npp_graph_observation): graph_node_feats f32 [N, 2500, 6],

@@ -164,6 +164,20 @@ class NppVecEnvironment:
     in this mode (visual observations, either frame stacking, graph observations, enable_spatial_context / enable_reachability /
     enable_switch_states) raise ValueError, as does any other mode string; levels npp_reachability refuses (several exit switches)
     are refused at the first reset().  "full" (default): everything above, unchanged.
+
+    Path-direction action masking (the reference env's _get_action_mask_with_path_update, base_environment.py:3075-3107, and the last
+    stage of Ninja.get_valid_action_mask, ninja.py:743-800): action_masking_mode="hard" returns the action_mask the
+    reference ENV returns in its default masking mode -- where the level cache's multi-hop direction from the ninja's graph node
+    to the current goal is a straight path, "left" keeps NOOP and LEFT, "right" keeps NOOP and RIGHT, "down" removes the three jump
+    actions -- in every observation path (reset, step, minimal mode, restart / restart_from_archive, the checkpoint options of
+    reset; with frame stacking the mask is not stacked).  "soft" returns the unfiltered mask.  Both add info["path_direction"] (i8
+    [N]: 0 none, 1 left, 2 right, 3 down; what a trainer's logit bias needs; not an observation key, the reference's space has
+    none) to reset() and step(), and at episode end info["deterministic_mask_applied_count"] / info["deterministic_mask_rate"]
+    (base_environment.py:1280-1290; [N], 0 for envs whose episode goes on): detector calls of the episode that classified from the
+    graph, and their share of the episode's observations -- the project's own count, which leaves out the terminal observation an
+    auto-resetting env never shows (parity of the two numbers is unpinned).  None / "none" (default): today's mask, nothing is
+    launched.  set_action_masking_mode(mode) changes it between steps (the reference's annealing schedule hard -> soft -> none).
+    Levels npp_reachability refuses (several exit switches) raise at the first observation with the mode on.
     """
 
     metadata = {"render_modes": []}
@@ -175,8 +189,11 @@ class NppVecEnvironment:
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
                  augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False,
-                 route_capacity=None):
+                 route_capacity=None, action_masking_mode=None):
         assert output in ("torch", "numpy")
+        if action_masking_mode not in (None, "none", "hard", "soft"):
+            raise ValueError('action_masking_mode must be None, "none", "hard" or "soft", not %r' % (action_masking_mode,))
+        self._mask_on = action_masking_mode in ("hard", "soft")
         if int(checkpoint_slots) < 0:
             raise ValueError("checkpoint_slots must be >= 0")
         self.route_capacity = route_capacity_for(record_routes, route_capacity, frame_skip, truncation_limit)
@@ -220,6 +237,8 @@ class NppVecEnvironment:
             outputs += ["global_view"] if self._vk else ["player_frame", "global_view"]
         if enable_reachability:   # reachability_features + mine_sdf_features (npp_environment.py observation keys)
             outputs += ["reachability_features", "mine_sdf_features"]
+        if self._mask_on:
+            outputs.append("path_direction")
         # same-level resets are Simulator.fast_reset in the reference's env (npp_environment.py:541-557): the default here
         self._b = NppBatch(self.num_envs, device=device, autoreset=autoreset, outputs=outputs, fast_reset=fast_reset,
                            stream=stream)
@@ -251,7 +270,10 @@ class NppVecEnvironment:
         self._reset_bits = 11 if autoreset else 0
         self._obs_names = ["game_state", "action_mask", "entity_pos", "positions", "flags"] + outputs[1:]
         if self._minimal:   # (the packed block keeps game_state and entity_pos in front; they are neither returned nor copied)
-            self._obs_names = ["action_mask", "positions", "flags", "minimal_observation"]
+            self._obs_names = ["action_mask", "positions", "flags", "minimal_observation"] + (["path_direction"] if self._mask_on else [])
+        self._autoreset = bool(autoreset)
+        if self._mask_on:
+            self._b.set_action_masking(action_masking_mode)
         self._term_stack = None
         if self._vk or self._sk:
             self._b.set_frame_stack(self._vk, self._sk, frame_stack_padding_type)
@@ -309,6 +331,8 @@ class NppVecEnvironment:
             b.frame_stack_push(self._reset_bits, reset_all, None if reset_all else self._term_stack)
         if self._aug:   # (after the push: the padding of reset envs is in the ring)
             b.frame_augment()
+        if self._mask_on:   # the detector, and in hard mode the filter on the block's action_mask, ahead of any host copy
+            b.path_action_mask()
 
     def _stacked(self, src, with_terminal=False):
         """src with the stacked windows in place of player_frame / game_state (+ terminal_game_state_stack).  Device views for
@@ -426,7 +450,14 @@ class NppVecEnvironment:
                     fs = self.frame_skip if fs is None else int(fs)
                     with self._b._ctx():
                         acts = torch.from_numpy(np.ascontiguousarray(seq.T)).to(self._b.device)
-                    flags, _rew, frames = self._b.step_many(acts, fs)
+                    mode = self._b._masking   # (action masking) the replay's inner steps have no observation: the detector
+                    if mode:                  # runs once, in _produce() below, on the state the replay ends in
+                        self._b.set_action_masking(0)
+                    try:
+                        flags, _rew, frames = self._b.step_many(acts, fs)
+                    finally:
+                        if mode:
+                            self._b.set_action_masking(mode)
                     info = {"checkpoint_replay": True, "replay_frames": frames.to(torch.int64).sum(dim=0),
                             "replay_terminated": (flags & 3).ne(0).any(dim=0)}
                 else:
@@ -434,11 +465,47 @@ class NppVecEnvironment:
         self._b.observe()
         self._produce(reset_all=True)
         if self.output == "torch":
+            if self._mask_on:
+                info["path_direction"] = self._b.out.t["path_direction"]
             return self._with_graph(self._obs(self._stacked(self._b.out.t))), info
         stk = self._stacked({})
         src = self._b.to_host(self._obs_names)
         src.update(stk)
+        if self._mask_on:
+            info["path_direction"] = src["path_direction"]
         return self._with_graph(self._obs(src)), info
+
+    def set_action_masking_mode(self, mode):
+        """None / "none", "hard" or "soft" (the constructor's action_masking_mode), from the next observation on.  The first
+        switch to "hard" / "soft" of an env created without it re-allocates the output block: tensors returned earlier are stale."""
+        if mode not in (None, "none", "hard", "soft"):
+            raise ValueError('action_masking_mode must be None, "none", "hard" or "soft", not %r' % (mode,))
+        on = mode in ("hard", "soft")
+        if on and "path_direction" not in self._b.out.t:
+            self._b.enable_outputs("path_direction")
+            self._obs_names.append("path_direction")
+        self._b.set_action_masking(mode)
+        self._mask_on = on
+
+    def _mask_info(self, src, done):
+        """info keys of the action masking: the direction, and for envs whose episode ended the two counters' numbers."""
+        numpy = self.output == "numpy"
+        out = {"path_direction": src["path_direction"]}
+        if numpy and not done.any():
+            out["deterministic_mask_applied_count"] = np.zeros(self.num_envs, dtype=np.int64)
+            out["deterministic_mask_rate"] = np.zeros(self.num_envs, dtype=np.float64)
+            return out
+        st = self._b.path_mask_stats()
+        with self._b._ctx():
+            # with auto-reset the kernel latched both at this observation; without, the episode's terminal observation is the last counted
+            cnt, tot = (st["last_applied"], st["last_observed"]) if self._autoreset else (st["applied"], st["observed"])
+            d = torch.as_tensor(done, device=self._b.device) if numpy else done
+            cnt = torch.where(d, cnt, torch.zeros_like(cnt)).to(torch.int64)
+            rate = torch.where(d, cnt.to(torch.float64) / tot.clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=self._b.device))
+            if numpy:
+                cnt, rate = cnt.cpu().numpy(), rate.cpu().numpy()
+        out["deterministic_mask_applied_count"], out["deterministic_mask_rate"] = cnt, rate
+        return out
 
     @property
     def _level_weights_now(self):
@@ -522,7 +589,9 @@ class NppVecEnvironment:
         step's reward, terminated, truncated and info stay as they were returned.
         Raises NotImplementedError with frame stacking or frame augmentation: the rings and the draw counters advance per
         observation, so a second observation of the untouched envs is not neutral there -- use
-        reset(options={"checkpoint": {"slots": slot_ids}}), which re-pads every stack."""
+        reset(options={"checkpoint": {"slots": slot_ids}}), which re-pads every stack.
+        With action masking on, this second observation of the step runs the detector again for every env, so the masking
+        counters (info["deterministic_mask_rate"]) count the untouched envs' observation twice."""
         self._restart_refusal()
         b = self._b
         status = self._archive_restore(slot_ids)
@@ -686,6 +755,8 @@ class NppVecEnvironment:
         if "terminal_game_state_stack" in src:
             info["terminal_game_state_stack"] = src["terminal_game_state_stack"]
         info["level_id"] = self._level_id(self.output == "numpy")
+        if self._mask_on:
+            info.update(self._mask_info(src, (flags & 11) != 0))
         return self._with_graph(self._obs(src), info["level_id"]), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
@@ -748,14 +819,17 @@ class NppEnvironment:
     (minimal_observation (40,), action_mask (6,) and the pass-through scalars; no terminal minimal observation).
     enable_augmentation / augmentation_p / augmentation_intensity / augmentation_seed: NppVecEnvironment's frame augmentation.
     checkpoint_slots / archive_store(slot) / reset(options={"checkpoint": {"slots": [slot]}}): NppVecEnvironment's checkpoint archive;
-    checkpoint_cells / checkpoint_seed are passed through to it."""
+    checkpoint_cells / checkpoint_seed are passed through to it.
+    action_masking_mode / set_action_masking_mode(mode): NppVecEnvironment's path-direction action masking; info["path_direction"] is
+    an int, and the step that ends the episode adds info["deterministic_mask_applied_count"] / info["deterministic_mask_rate"]."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
                  enable_reachability=False, enable_visual_frame_stacking=False, visual_stack_size=4, enable_state_stacking=False,
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
-                 checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None):
+                 checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None,
+                 action_masking_mode=None):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -780,7 +854,8 @@ class NppEnvironment:
                                     enable_augmentation=enable_augmentation, augmentation_p=augmentation_p,
                                     augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed,
                                     checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
-                                    checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity)
+                                    checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity,
+                                    action_masking_mode=action_masking_mode)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -799,7 +874,12 @@ class NppEnvironment:
 
     def reset(self, seed=None, options=None):
         obs, info = self._v.reset(seed=seed, options=options)
+        if "path_direction" in info:
+            info["path_direction"] = int(info["path_direction"][0])
         return self._unbatch(obs), info
+
+    def set_action_masking_mode(self, mode):
+        self._v.set_action_masking_mode(mode)
 
     def archive_store(self, slot):
         """Store the current state in slot `slot` of the checkpoint archive (checkpoint_slots > 0); returns the status (0 =
@@ -824,6 +904,11 @@ class NppEnvironment:
             "death_cause": cause,
             "frame_skip_stats": {"skip_value": self.frame_skip, "frames_executed": int(info["frames_executed"][0])},
         }
+        if "path_direction" in info:
+            out_info["path_direction"] = int(info["path_direction"][0])
+            if bool(term[0]) or bool(trunc[0]):
+                out_info["deterministic_mask_applied_count"] = int(info["deterministic_mask_applied_count"][0])
+                out_info["deterministic_mask_rate"] = float(info["deterministic_mask_rate"][0])
         return self._unbatch(obs), float(rew[0]), bool(term[0]), bool(trunc[0]), out_info
 
     def close(self):
