@@ -224,9 +224,8 @@ int npp_reachability_ex(npp_handle h, float *d_features, float *d_mine_sdf, int3
  *   npp_set_entity_pos.  There is no terminal minimal observation (the reference defines none). */
 int npp_set_minimal_observation(npp_handle h, int enable);
 /* Host-only: the state encodings the device kernel runs (npp_minimal.hpp compiles for both) -- columns 0-11 and 36-39 of `count` rows
- * out f32[count][40] (the other columns are left alone) from state_a u32[count] (state word A: state bits 0-3, airborn 4, walled 6,
- * wall normal + 1 bits 7-8, jump / floor / wall / launch pad buffer + 1 at bits 15, 18, 21, 24, three bits each) and planes
- * f64[count][4] = xspeed, yspeed, floor_normalized_x, floor_normalized_y. */
+ * out f32[count][40] (the other columns are left alone) from state_a u32[count] (state word A; its bit layout: DESIGN.md section 3,
+ * "packed state layout") and planes f64[count][4] = xspeed, yspeed, floor_normalized_x, floor_normalized_y. */
 int npp_minimal_encode_host(const uint32_t *state_a, const double *planes, int count, float *out);
 int npp_minimal_observation(npp_handle h, float *d_out /* [N,40] */, int32_t *d_status /* [N] or NULL */);
 
@@ -290,6 +289,9 @@ int npp_render_global_view(npp_handle h, uint8_t *d_out);
  *                            applied_gravity applied_drag
  * i32 [count][NPP_DUMP_I32]: see DESIGN.md ("state dump layout"). */
 int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *i32_out);
+/* Host-only: npp_dump_state's own decode of one env's five packed state words (planes A..E, DESIGN.md "packed state layout") into
+ * its i32 row.  Columns 13 and 27 are not in the words: 2 (no exit switch) and level 0. */
+int npp_state_decode_host(const uint32_t words[5], int32_t *out /* NPP_DUMP_I32 */);
 
 /* Parity hook: per-entity dynamic state of one env in level (map) order:
  * mines -> state 0/1/2, exit door -> switch_hit, others -> active.  Returns count via *n_out. */

@@ -96,15 +96,13 @@ template <bool STORE> __global__ __launch_bounds__(256) void npp_archive_kernel(
                 const double x = a.f64[F_X * N + e], y = a.f64[F_Y * N + e];
                 double *mf = a.meta_f64 + (size_t)slot * ARCHIVE_META_F64;
                 mf[0] = x; mf[1] = y; mf[2] = a.f64[F_VX * N + e]; mf[3] = a.f64[F_VY * N + e];
-                const int sw = a.hdr[level].obs_switch;
-                int sw_state = 2;
-                if (sw >= 0) sw_state = (a.ent[(size_t)(sw >> 4) * N + e] >> ((sw & 15) * 2)) & 3;
+                const int sw_state = exit_switch_state(a.ent, N, e, a.hdr[level].obs_switch);
                 int32_t *mi = a.meta_i32 + (size_t)slot * ARCHIVE_META_I32;
                 mi[1] = level;
-                mi[2] = (int32_t)(a.u32[U_D * N + e] & 0xffffu);
+                mi[2] = state_load(a.u32, N, e, S_FRAME);
                 mi[3] = (int32_t)floor(x / 24.0);
                 mi[4] = (int32_t)floor(y / 24.0);
-                mi[5] = sw_state != 1;
+                mi[5] = exit_switch_activated(sw_state);
                 mi[0] = 1;
             }
         }

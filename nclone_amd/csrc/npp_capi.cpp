@@ -1463,7 +1463,7 @@ int npp_reset_ex(npp_handle h, const uint8_t *env_mask, int mode) {
     if (mode < 0 || mode > 2) return fail(h, NPP_ERR_INVALID, "npp_reset_ex: mode must be 0, 1 or 2");
     const int fast = mode == 2 || (mode == 0 && (h->flags & NPP_FLAG_FAST_RESET));
     // mode 0 follows NppEnvironment.reset: the first reset after a level assignment reloads the map (Simulator.reset), later ones
-    // are fast resets; the per-env "no reset yet" bit lives in the state planes (npp_kernels.hip: Nj::fastord bit 1)
+    // are fast resets; the per-env "no reset yet" bit lives in the state planes (npp_state.hpp: S_FRESH)
     return reset_impl(h, env_mask, 0, fast ? 1 : 0, mode == 0 ? 1 : 0);
 }
 
@@ -2258,9 +2258,9 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
         HIP_TRY(h, hipMemcpy(w.data() + (size_t)k * count, h->ls.ent.get() + k * N + env0, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) {
         auto F = [&](int k) { return f[(size_t)k * count + i]; };
-        uint32_t A = u[(size_t)U_A * count + i], B = u[(size_t)U_B * count + i], C = u[(size_t)U_C * count + i],
-                 D = u[(size_t)U_D * count + i], E = u[(size_t)U_E * count + i];
-        int gjump = (A >> 13) & 1, dslow = (A >> 14) & 1;
+        uint32_t words[NU32];
+        for (int k = 0; k < NU32; k++) words[k] = state_word(u.data(), count, i, k);
+        const int gjump = state_get(words, S_GJUMP), dslow = state_get(words, S_DSLOW);
         if (f64_out) {
             double *o = f64_out + (size_t)i * NPP_DUMP_F64;
             o[0] = F(F_X); o[1] = F(F_Y); o[2] = F(F_VX); o[3] = F(F_VY);
@@ -2270,20 +2270,8 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
             o[11] = dslow ? 0.8617738760127536 : 0.9933221725495059;
         }
         if (i32_out) {
-            int32_t *o = i32_out + (size_t)i * NPP_DUMP_I32;
-            std::memset(o, 0, sizeof(int32_t) * NPP_DUMP_I32);
-            int lvl = h->env_level[env0 + i];
-            const CompiledLevel &L = h->ls.levels[lvl];
-            int sw_active = 2;
-            if (L.obs_switch >= 0) sw_active = (w[(size_t)(L.obs_switch >> 4) * count + i] >> ((L.obs_switch & 15) * 2)) & 3;
-            o[0] = A & 15; o[1] = (A >> 4) & 1; o[2] = (A >> 6) & 1; o[3] = (A >> 7) & 3;
-            o[4] = (A >> 15) & 7; o[5] = (A >> 18) & 7; o[6] = (A >> 21) & 7; o[7] = (A >> 24) & 7;
-            o[8] = (B >> 6) & 255; o[9] = (B >> 14) & 255; o[10] = B & 63;
-            o[11] = !gjump; o[12] = !dslow; o[13] = sw_active;
-            o[14] = (D >> 16) & 255; o[15] = D >> 24; o[16] = C & 0xffff; o[17] = C >> 16;
-            o[18] = (A >> 5) & 1; o[19] = (A >> 9) & 1; o[20] = (A >> 27) & 3; o[21] = (A >> 29) & 1;
-            o[22] = D & 0xffff; o[23] = (int)((A >> 10) & 3) - 1; o[24] = (A >> 12) & 1; o[25] = (B >> 22) & 15;
-            o[26] = E & 0xffff; o[27] = lvl;
+            const int lvl = h->env_level[env0 + i];
+            state_decode_row(words, exit_switch_state(w.data(), count, i, h->ls.levels[lvl].obs_switch), lvl, i32_out + (size_t)i * NPP_DUMP_I32);
         }
     }
     return NPP_OK;
@@ -2303,7 +2291,7 @@ int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out) 
     if (n > max) n = max;
     for (int i = 0; i < n; i++) {
         int slot = L.ent_map_order[i];
-        out[i] = (w[slot >> 4] >> ((slot & 15) * 2)) & 3;
+        out[i] = ent_state(w.data(), 1, 0, slot);
     }
     *n_out = n;
     return NPP_OK;
@@ -2351,7 +2339,7 @@ int npp_entity_checksum(npp_handle h, int env0, int count, double *out) {
             } else {
                 int s = (int)ref;
                 uint32_t kind = L.ent_meta[s] & 15u;
-                uint32_t st = (w[(size_t)(s >> 4) * count + i] >> ((s & 15) * 2)) & 3u;
+                uint32_t st = ent_state(w.data(), count, i, s);
                 if (blk && s == L.obs_switch && (ovr & ZOO_OVR_SWITCH)) { sx += blk[4]; sy += blk[5]; }
                 else if (blk && s == L.obs_door && (ovr & ZOO_OVR_DOOR)) { sx += blk[6]; sy += blk[7]; }
                 else { sx += L.ent_x[s]; sy += L.ent_y[s]; }

@@ -30,11 +30,10 @@ __global__ __launch_bounds__(256) void npp_cells_propose_kernel(CellArgs a) {
         const size_t N = (size_t)a.n;
         const int level = a.env_level[e];
         const LevelHdr &H = a.hdr[level];
-        int sw_state = 2;   // npp_dump_state's decode of the exit switch
-        if (H.obs_switch >= 0) sw_state = (a.ent[(size_t)(H.obs_switch >> 4) * N + e] >> ((H.obs_switch & 15) * 2)) & 3;
-        const int k = cell_key_in_level((int)(a.u32[U_A * N + e] & 15u), sw_state, a.f64[F_X * N + e], a.f64[F_Y * N + e],
+        const int sw_state = exit_switch_state(a.ent, N, e, H.obs_switch);
+        const int k = cell_key_in_level(state_load(a.u32, N, e, S_STATE), sw_state, a.f64[F_X * N + e], a.f64[F_Y * N + e],
                                         H.obs_door >= 0, H.door_x, H.door_y);
-        const uint32_t bits = __float_as_uint(a.score ? a.score[e] : -(float)(a.u32[U_D * N + e] & 0xffffu));
+        const uint32_t bits = __float_as_uint(a.score ? a.score[e] : -(float)state_load(a.u32, N, e, S_FRAME));
         if (k >= 0 && !cell_bits_nan(bits)) {
             key = level * NPP_CELLS_PER_LEVEL + k;
             st = CELL_LOST;

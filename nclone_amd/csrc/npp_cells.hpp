@@ -7,7 +7,8 @@
 #include <cstdint>
 #include <cstring>
 
-#include "npp_pool.hpp"   // NPP_HD, pool_mix
+#include "npp_pool.hpp"   // pool_mix
+#include "npp_state.hpp"
 
 namespace npp {
 
@@ -16,7 +17,7 @@ constexpr int NPP_CELLS_PER_LEVEL = 2 * CELL_GRID_W * CELL_GRID_H;      // (swit
 enum CellStatus { CELL_NOT_ELIGIBLE = 5, CELL_LOST = 6, CELL_FULL = 7 };   // extend ArchiveStatus (0 stored, 1 skipped)
 
 // The key of a state inside its level, or -1 when the state is not eligible.  ninja_state: dump column 0 (0..5 are the live
-// states); sw_state: the exit switch's 2-bit state, dump column 13 (switch_activated = it is not 1); has_door: the level has an
+// states); sw_state: exit_switch_state (npp_state.hpp), dump column 13; has_door: the level has an
 // exit door (LevelHdr::obs_door >= 0) at (door_x, door_y).  The last test is the seeder's exit filter
 // (replay/demo_checkpoint_seeder.py:30, :118-153): no checkpoint nearer than 72 px to the door once the switch is on.
 NPP_HD inline int cell_key_in_level(int ninja_state, int sw_state, double x, double y, bool has_door, double door_x, double door_y) {
@@ -24,7 +25,7 @@ NPP_HD inline int cell_key_in_level(int ninja_state, int sw_state, double x, dou
     const double qx = x / 24.0, qy = y / 24.0;
     if (!(qx >= 0.0 && qx < (double)CELL_GRID_W && qy >= 0.0 && qy < (double)CELL_GRID_H)) return -1;   // (NaN fails too)
     const int cx = (int)floor(qx), cy = (int)floor(qy);
-    const int sw = sw_state != 1;
+    const int sw = exit_switch_activated(sw_state);
     if (sw && has_door) {
         const double dx = x - door_x, dy = y - door_y;
         if (sqrt(dx * dx + dy * dy) < 72.0) return -1;

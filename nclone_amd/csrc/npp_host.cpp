@@ -39,6 +39,13 @@ int npp_minimal_encode_host(const uint32_t *state_a, const double *planes, int c
     return NPP_OK;
 }
 
+int npp_state_decode_host(const uint32_t words[5], int32_t *out) {
+    static_assert(STATE_DUMP_I32 == NPP_DUMP_I32 && NU32 == 5, "the row npp_dump_state documents");
+    if (!words || !out) return fail(nullptr, NPP_ERR_INVALID, "npp_state_decode_host: bad arguments");
+    state_decode_row(words, EXIT_SWITCH_NONE, 0, out);
+    return NPP_OK;
+}
+
 int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed, const int32_t *envs, const uint32_t *counts, int count,
                              int32_t *out) {
     if (count < 0 || (count > 0 && (!envs || !counts || !out))) return fail(nullptr, NPP_ERR_INVALID, "npp_level_pool_draw_host: bad arguments");

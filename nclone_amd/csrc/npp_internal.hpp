@@ -4,14 +4,14 @@
 
 #include <cstdint>
 
+#include "npp_state.hpp"
 #include "npp_zoo_layout.hpp"
 
 namespace npp {
 
 // ---- SoA ninja state: f64 plane k of env e lives at d_f64[k * n_envs + e] (coalesced per wave) -------------------
 enum F64Plane { F_X = 0, F_Y, F_VX, F_VY, F_VXO, F_VYO, F_FNX, F_FNY, F_CNX, F_CNY, F_SCX, F_SCY, NF64 };  // F_SC*: position of the cached mine overlay
-// u32 planes, bit layout in npp_kernels.hip (pack_state / unpack_state)
-enum U32Plane { U_A = 0, U_B, U_C, U_D, U_E, NU32 };
+// u32 planes U_A .. U_E: npp_state.hpp has the planes and their bit layout
 
 // Per-level header (device copy); offsets are bytes into the level blob.
 // The "hot" region [off_hot, off_hot + hot_bytes) = seg_start | ent_start | cell_bounds | segs is what a
@@ -113,8 +113,8 @@ struct KernelArgs {
     int zoo_active;       // 1: some env currently plays a level with zoo entities -> the zoo step kernel runs
     int reset_fresh;      // reset kernel: 1 = this reset is the first creation after a (re)assignment of levels
     int fast_reset;       // reset kernel: this reset is a Simulator.fast_reset; step kernels: auto-resets are fast resets
-    int reset_auto;       // reset kernel, with fast_reset: envs without a Simulator.reset since their level assignment (state word E
-                          // bit 18) get a full reset instead -- the reference env's first reset() (npp_environment.py:518-557)
+    int reset_auto;       // reset kernel, with fast_reset: envs without a Simulator.reset since their level assignment (S_FRESH,
+                          // npp_state.hpp) get a full reset instead -- the reference env's first reset() (npp_environment.py:518-557)
     // npp_step only (null elsewhere): heavy-first launch order of the workgroups -- wg_order[blockIdx.x] is the block of envs this
     // workgroup steps, wg_cost[block] the shader clocks its last launch took (launch_cost_order rebuilds the order from the costs)
     const uint32_t *wg_order;
@@ -287,7 +287,7 @@ struct ReachMissDev {
     uint32_t *stamp;   // [n][REACH_CELLS]
     double *raw;       // [n][REACH_CELLS]
     uint32_t *epoch;   // [n] current epoch of the env's entries (stamp == epoch: live); 0 = never called
-    uint32_t *last_episode;   // [n] episode counter (state word E bits 19-31) seen at the last call
+    uint32_t *last_episode;   // [n] episode counter (S_EPISODE, npp_state.hpp) seen at the last call
 };
 // min_out (f32[n][40], may be NULL): the minimal observation rows, assembled by the same launch; sc_rows (f32[n][112], needed with
 // min_out): the spatial_context rows the step kernel wrote for this observation

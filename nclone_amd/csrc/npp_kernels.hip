@@ -82,17 +82,21 @@ struct Nj {
     // per SIMD ("Registers and occupancy"), and these fields are dead weight inside the collision loops.
     int fcount, ccount, fair, scf, frame, gold, doors;
     int work;   // depenetration iterations applied since the step began (npp_step_out.d_work; not part of the state)
-    int fastord;   // bit 0: set after a Simulator.fast_reset -- the cell lists are in entity_dic order (nsim.py:124-140);
-                   // bit 1: the level was assigned and no Simulator.reset has run since (the state of a fresh NppEnvironment after
+    int fastord;   // S_FASTORD (npp_state.hpp) as one value; its parts are FO_* below.  FO_FAST: set after a Simulator.fast_reset --
+                   // the cell lists are in entity_dic order (nsim.py:124-140);
+                   // FO_FRESH: the level was assigned and no Simulator.reset has run since (the state of a fresh NppEnvironment after
                    // __init__'s load_map, base_environment.py:318): the next automatic reset is a FULL one, as in the reference, whose
                    // first reset() finds _last_reset_map_name None and reloads the map (npp_environment.py:518-557);
-                   // bits 2-14: episode counter mod 8192, bumped by every reset (the reachability kernel drops the env's per-episode
+                   // FO_EPISODE: episode counter mod 8192, bumped by every reset (the reachability kernel drops the env's per-episode
                    // path-distance cache when it changes: reachability_mixin.py:67-70 clears the calculator at every reset)
     unsigned state : 4, airborn : 1, airborn_old : 1, walled : 1, jio : 1, jump : 1, gjump : 1, dslow : 1;
     int wn : 2, hor : 2, jbuf : 4, fbuf : 4, wbuf : 4, lbuf : 4;            // wn, hor in {-1, 0, 1}; buffers in -1 .. 5
-    unsigned cause : 2, timpact : 1, jdur : 7, pstate : 4, scvalid : 1, pcell : 11;   // jdur <= 46, pcell < 1100
+    unsigned cause : 2, timpact : 1, jdur : 7, pstate : 4, scvalid : 1, pcell : 11;   // jdur <= 46 (S_JDUR, one bit narrower, saturates
+                                                                                      // at 63 when stored), pcell < 1100
 };
-DEV int next_episode(int fastord) { return (((fastord >> 2) + 1) & 0x1fff) << 2; }
+constexpr StateField FO_FAST = fastord_part(S_FAST_ORDERED), FO_FRESH = fastord_part(S_FRESH), FO_EPISODE = fastord_part(S_EPISODE);
+constexpr int FO_FAST_BIT = (int)field_bits(FO_FAST, 1), FO_FRESH_BIT = (int)field_bits(FO_FRESH, 1);
+DEV int next_episode(int fastord) { return (((fastord >> FO_EPISODE.shift) + 1) & (int)field_max(FO_EPISODE)) << FO_EPISODE.shift; }
 
 struct Lv {
     const uint16_t *seg_start;
@@ -158,23 +162,18 @@ DEV void load_state(const KernelArgs &a, int e, Nj &n) {
     n.vxo = a.f64[F_VXO * N + e]; n.vyo = a.f64[F_VYO * N + e];
     n.fnx = a.f64[F_FNX * N + e]; n.fny = a.f64[F_FNY * N + e];
     n.cnx = a.f64[F_CNX * N + e]; n.cny = a.f64[F_CNY * N + e];
-    uint32_t A = a.u32[U_A * N + e], B = a.u32[U_B * N + e], C = a.u32[U_C * N + e], D = a.u32[U_D * N + e],
-             E = a.u32[U_E * N + e];
-    n.state = A & 15; n.airborn = (A >> 4) & 1; n.airborn_old = (A >> 5) & 1; n.walled = (A >> 6) & 1;
-    n.wn = (int)((A >> 7) & 3) - 1; n.jio = (A >> 9) & 1; n.hor = (int)((A >> 10) & 3) - 1; n.jump = (A >> 12) & 1;
-    n.gjump = (A >> 13) & 1; n.dslow = (A >> 14) & 1;
-    n.jbuf = (int)((A >> 15) & 7) - 1; n.fbuf = (int)((A >> 18) & 7) - 1; n.wbuf = (int)((A >> 21) & 7) - 1;
-    n.lbuf = (int)((A >> 24) & 7) - 1; n.cause = (A >> 27) & 3; n.timpact = (A >> 29) & 1;
-    n.jdur = B & 63; n.fcount = (B >> 6) & 255; n.ccount = (B >> 14) & 255; n.pstate = (B >> 22) & 15;
-    n.fair = C & 0xffff; n.scf = C >> 16;
-    n.frame = D & 0xffff; n.gold = (D >> 16) & 255; n.doors = D >> 24;
-    n.pcell = E & 0xffff;
-    n.scvalid = (E >> 16) & 1;
-    n.fastord = (E >> 17) & 0x7fff;
+    const uint32_t w[NU32] = {a.u32[U_A * N + e], a.u32[U_B * N + e], a.u32[U_C * N + e], a.u32[U_D * N + e], a.u32[U_E * N + e]};
+    n.state = state_get(w, S_STATE); n.airborn = state_get(w, S_AIRBORN); n.airborn_old = state_get(w, S_AIRBORN_OLD);
+    n.walled = state_get(w, S_WALLED); n.wn = state_get(w, S_WN); n.jio = state_get(w, S_JIO); n.hor = state_get(w, S_HOR);
+    n.jump = state_get(w, S_JUMP); n.gjump = state_get(w, S_GJUMP); n.dslow = state_get(w, S_DSLOW);
+    n.jbuf = state_get(w, S_JBUF); n.fbuf = state_get(w, S_FBUF); n.wbuf = state_get(w, S_WBUF); n.lbuf = state_get(w, S_LBUF);
+    n.cause = state_get(w, S_CAUSE); n.timpact = state_get(w, S_TIMPACT);
+    n.jdur = state_get(w, S_JDUR); n.fcount = state_get(w, S_FCOUNT); n.ccount = state_get(w, S_CCOUNT); n.pstate = state_get(w, S_PSTATE);
+    n.fair = state_get(w, S_FAIR); n.scf = state_get(w, S_SCF);
+    n.frame = state_get(w, S_FRAME); n.gold = state_get(w, S_GOLD); n.doors = state_get(w, S_DOORS);
+    n.pcell = state_get(w, S_PCELL); n.scvalid = state_get(w, S_SCVALID); n.fastord = state_get(w, S_FASTORD);
     n.work = 0;
 }
-
-DEV int sat(int v, int hi) { return v > hi ? hi : v; }
 
 DEV void store_state(const KernelArgs &a, int e, const Nj &n) {
     const size_t N = (size_t)a.n;
@@ -183,16 +182,18 @@ DEV void store_state(const KernelArgs &a, int e, const Nj &n) {
     a.f64[F_VXO * N + e] = n.vxo; a.f64[F_VYO * N + e] = n.vyo;
     a.f64[F_FNX * N + e] = n.fnx; a.f64[F_FNY * N + e] = n.fny;
     a.f64[F_CNX * N + e] = n.cnx; a.f64[F_CNY * N + e] = n.cny;
-    uint32_t A = (uint32_t)n.state | (n.airborn << 4) | (n.airborn_old << 5) | (n.walled << 6) | ((n.wn + 1) << 7) |
-                 (n.jio << 9) | ((n.hor + 1) << 10) | (n.jump << 12) | (n.gjump << 13) | (n.dslow << 14) |
-                 ((n.jbuf + 1) << 15) | ((n.fbuf + 1) << 18) | ((n.wbuf + 1) << 21) | ((n.lbuf + 1) << 24) |
-                 (n.cause << 27) | (n.timpact << 29);
-    uint32_t B = (uint32_t)sat(n.jdur, 63) | (sat(n.fcount, 255) << 6) | (sat(n.ccount, 255) << 14) | (n.pstate << 22);
-    uint32_t C = (uint32_t)sat(n.fair, 0xffff) | ((uint32_t)sat(n.scf, 0xffff) << 16);
-    uint32_t D = (uint32_t)sat(n.frame, 0xffff) | (sat(n.gold, 255) << 16) | ((uint32_t)sat(n.doors, 255) << 24);
-    uint32_t E = (uint32_t)n.pcell | ((uint32_t)n.scvalid << 16) | ((uint32_t)n.fastord << 17);
-    a.u32[U_A * N + e] = A; a.u32[U_B * N + e] = B; a.u32[U_C * N + e] = C; a.u32[U_D * N + e] = D;
-    a.u32[U_E * N + e] = E;
+    uint32_t w[NU32] = {0u, 0u, 0u, 0u, 0u};
+    state_put(w, S_STATE, n.state); state_put(w, S_AIRBORN, n.airborn); state_put(w, S_AIRBORN_OLD, n.airborn_old);
+    state_put(w, S_WALLED, n.walled); state_put(w, S_WN, n.wn); state_put(w, S_JIO, n.jio); state_put(w, S_HOR, n.hor);
+    state_put(w, S_JUMP, n.jump); state_put(w, S_GJUMP, n.gjump); state_put(w, S_DSLOW, n.dslow);
+    state_put(w, S_JBUF, n.jbuf); state_put(w, S_FBUF, n.fbuf); state_put(w, S_WBUF, n.wbuf); state_put(w, S_LBUF, n.lbuf);
+    state_put(w, S_CAUSE, n.cause); state_put(w, S_TIMPACT, n.timpact);
+    state_put(w, S_JDUR, n.jdur); state_put(w, S_FCOUNT, n.fcount); state_put(w, S_CCOUNT, n.ccount); state_put(w, S_PSTATE, n.pstate);
+    state_put(w, S_FAIR, n.fair); state_put(w, S_SCF, n.scf);
+    state_put(w, S_FRAME, n.frame); state_put(w, S_GOLD, n.gold); state_put(w, S_DOORS, n.doors);
+    state_put(w, S_PCELL, n.pcell); state_put(w, S_SCVALID, n.scvalid); state_put(w, S_FASTORD, n.fastord);
+    a.u32[U_A * N + e] = w[U_A]; a.u32[U_B * N + e] = w[U_B]; a.u32[U_C * N + e] = w[U_C]; a.u32[U_D * N + e] = w[U_D];
+    a.u32[U_E * N + e] = w[U_E];
 }
 
 // Ninja.__init__ / reset_state (ninja.py:80-196,1288-1394)
@@ -212,11 +213,10 @@ struct EntBits {
     uint32_t *w;
     int stride;
 };
-DEV uint32_t ent_get(EntBits eb, int slot) { return (eb.w[(slot >> 4) * eb.stride] >> ((slot & 15) * 2)) & 3u; }
+DEV uint32_t ent_get(EntBits eb, int slot) { return ent_field(eb.w[ent_word(slot) * eb.stride], slot); }
 DEV void ent_set(EntBits eb, int slot, uint32_t v) {
-    uint32_t *p = &eb.w[(slot >> 4) * eb.stride];
-    int sh = (slot & 15) * 2;
-    *p = (*p & ~(3u << sh)) | (v << sh);
+    uint32_t *p = &eb.w[ent_word(slot) * eb.stride];
+    *p = (*p & ~ent_bits_at(3u, slot)) | ent_bits_at(v, slot);
 }
 
 // ---- time-of-intersection primitives (physics.py:247-314) -----------------------------------------------------
@@ -1625,13 +1625,13 @@ DEV void block_store_rows(const uint32_t *stage, uint32_t *dst_block, int width,
 // Executed by all lanes of the env's group on identical data (the LDS updates are idempotent).
 template <bool ZOO>
 DEV void episode_reset(const KernelArgs &a, const LevelHdr &H, Lv &lv, Zoo &z, Nj &n, EntBits eb, int nw, int r, int G) {
-    const bool fast = a.fast_reset && !(n.fastord & 2);   // the first reset after a level assignment is a Simulator.reset
+    const bool fast = a.fast_reset && !(n.fastord & FO_FRESH_BIT);   // the first reset after a level assignment is a Simulator.reset
     const int episode = next_episode(n.fastord);
     lv.spawn_x = H.spawn_x; lv.spawn_y = H.spawn_y;
     spawn_state(lv, n);
     n.fastord = episode;
     if (fast) {
-        n.fastord |= 1;
+        n.fastord |= FO_FAST_BIT;
         lv.perm = reinterpret_cast<const uint16_t *>(a.blob + H.off_ent_perm);
         const uint32_t *keep = reinterpret_cast<const uint32_t *>(a.blob + H.off_keep_words);
         for (int w = 0; w < nw; w++) {
@@ -1762,9 +1762,9 @@ DEV void run(const KernelArgs &a, unsigned char *smem) {
     Nj n;
     load_state(a, e, n);
     // list order inside a cell: map order after Simulator.reset, entity_dic order after a fast reset
-    lv.perm = reinterpret_cast<const uint16_t *>(a.blob + ((n.fastord & 1) ? H.off_ent_perm : H.off_ent_ident));
+    lv.perm = reinterpret_cast<const uint16_t *>(a.blob + ((n.fastord & FO_FAST_BIT) ? H.off_ent_perm : H.off_ent_ident));
     if constexpr (ZOO) {
-        if (n.fastord & 1) z.ent_ord = reinterpret_cast<const uint16_t *>(a.blob + H.off_ent_rank);
+        if (n.fastord & FO_FAST_BIT) z.ent_ord = reinterpret_cast<const uint16_t *>(a.blob + H.off_ent_rank);
     }
     const int nw = (int)lv.n_words;
     if (r == 0)
@@ -1948,9 +1948,9 @@ __global__ __launch_bounds__(64) void npp_reset_kernel(KernelArgs a) {
     // Simulator.fast_reset (nsim.py:78-140).  a.reset_auto (npp_reset / npp_reset_ex mode 0 under NPP_FLAG_FAST_RESET): envs that
     // have not had a Simulator.reset since their level was assigned get a full one, like the reference env's first reset()
     const uint32_t oldE = a.u32[U_E * (size_t)a.n + env];
-    const bool first = ((oldE >> 18) & 1u) != 0;
+    const bool first = field_raw(oldE, S_FRESH) != 0u;
     const bool fast = a.fast_reset != 0 && !(a.reset_auto && first);
-    n.fastord = next_episode((int)((oldE >> 17) & 0x7fff)) | (a.reset_fresh ? 2 : (fast ? (1 | (first ? 2 : 0)) : 0));
+    n.fastord = next_episode(field_get(oldE, S_FASTORD)) | (a.reset_fresh ? FO_FRESH_BIT : (fast ? (FO_FAST_BIT | (first ? FO_FRESH_BIT : 0)) : 0));
     store_state(a, env, n);
     const uint32_t *init = reinterpret_cast<const uint32_t *>(a.blob + H.off_init_words);
     const uint32_t *keep = reinterpret_cast<const uint32_t *>(a.blob + H.off_keep_words);

@@ -6,6 +6,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "npp_state.hpp"   // the entity state words
+
 namespace npp {
 namespace {
 
@@ -321,7 +323,7 @@ bool compile_level(const double *map, int64_t n, CompiledLevel &L, std::string &
         L.ent_meta[s] = r.kind | (r.init << 4) | (link << 8) | (r.type << 24);
         L.ent_seq[s] = (uint16_t)r.seq;
         L.ent_cell[s] = (uint16_t)r.cell;
-        L.ent_init_words[s >> 4] |= r.init << ((s & 15) * 2);
+        L.ent_init_words[ent_word(s)] |= ent_bits_at(r.init, s);
         count[r.cell]++;
     }
     for (size_t i = 0; i < ne; i++) L.ent_map_order[i] = (uint16_t)slot_of[i];
@@ -436,7 +438,7 @@ bool compile_level(const double *map, int64_t n, CompiledLevel &L, std::string &
         L.ent_keep_words.assign((ne + 15) / 16, 0);
         for (size_t s2 = 0; s2 < ne; s2++) {
             const uint32_t kind = L.ent_meta[s2] & 15u;
-            if (kind == EK_BOOST || kind == EK_DOOR_REG) L.ent_keep_words[s2 >> 4] |= 2u << ((s2 & 15) * 2);
+            if (kind == EK_BOOST || kind == EK_DOOR_REG) L.ent_keep_words[ent_word(s2)] |= ent_bits_at(2u, s2);
         }
     }
     {

@@ -34,9 +34,7 @@ __global__ __launch_bounds__(256) void npp_path_mask_kernel(PathMaskArgs a) {
     const ReachHdr &H = a.rh[lvl];
     const int obs_switch = L.obs_switch;
     const ReachTabs T{&H, a.rblob + H.base};
-    // exit_switch_activated (nplay_headless.py:566-576): not switch.active
-    int sw = 1;
-    if (obs_switch >= 0) sw = ((a.ent_bits[(size_t)(obs_switch >> 4) * N + e] >> ((obs_switch & 15) * 2)) & 3u) == 0 ? 1 : 0;
+    const int sw = exit_switch_activated(exit_switch_state(a.ent_bits, N, e, obs_switch));
     int from_graph = 0;
     const int dir = reach_path_direction(T, px, py, sw, &from_graph);
     if (a.dir) a.dir[e] = (int8_t)dir;

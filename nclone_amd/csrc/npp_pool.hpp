@@ -3,11 +3,7 @@
 #pragma once
 #include <cstdint>
 
-#if defined(__HIPCC__) || defined(__HIP__)
-#define NPP_HD __host__ __device__
-#else
-#define NPP_HD
-#endif
+#include "npp_state.hpp"   // NPP_HD
 
 namespace npp {
 

@@ -537,8 +537,8 @@ void build_reach(const CompiledLevel &L, ReachBuilt &R) {
     H.ex_valid = dr >= 0 && !(L.ent_x[dr] == 0.0 && L.ent_y[dr] == 0.0);
     H.n_mines = (int)(mines1.size() + mines21.size());
     R.mine_mask.assign((L.ent_meta.size() + 15) / 16, 0u);
-    for (int s : mines1) R.mine_mask[s >> 4] |= 1u << ((s & 15) * 2);
-    for (int s : mines21) R.mine_mask[s >> 4] |= 1u << ((s & 15) * 2);
+    for (int s : mines1) R.mine_mask[ent_word(s)] |= ent_bits_at(1u, s);
+    for (int s : mines21) R.mine_mask[ent_word(s)] |= ent_bits_at(1u, s);
     if (R.mine_mask.empty()) R.mine_mask.push_back(0u);
     // ---- base graph, physics, entity mask, flood fill from the spawn
     build_adjacency(L, R);

@@ -75,24 +75,12 @@ __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const Reach
         if (l < n_here) minobs_encode_state(pa, pv[0], pv[1], pv[2], pv[3], mins + l * MINOBS_DIM);
     }
     __syncthreads();
-    // switch_states (npp_switch_states_kernel's arithmetic, npp_render.hip) by the env's second lane, which has nothing else to do:
+    // switch_states (the row npp_switch_states_kernel writes, npp_render.hip) by the env's second lane, which has nothing else to do:
     // npp_reachability_ex saves the launch of that 8-us kernel
     if (sw_out && (l & 3) == 1 && el < n_here) {
         const LevelHdr &L = a.hdr[a.env_level[env]];
-        const double *ex = reinterpret_cast<const double *>(a.blob + L.off_ent_x);
-        const double *ey = reinterpret_cast<const double *>(a.blob + L.off_ent_y);
-        float *o = sw_out + (size_t)env * 25;
-        for (int k = 0; k < 5; k++) {
-            const int slot = L.locked_slots[k];
-            float v0 = 0.f, v1 = 0.f, v4 = 0.f;
-            if (slot >= 0) {
-                const double sx = ex[slot] / 1056.0, sy = ey[slot] / 600.0;
-                v0 = (float)(sx < 0.0 ? 0.0 : (sx > 1.0 ? 1.0 : sx)); v1 = (float)(sy < 0.0 ? 0.0 : (sy > 1.0 ? 1.0 : sy));
-                const uint32_t st = (a.ent_bits[(size_t)(slot >> 4) * a.n + env] >> ((slot & 15) * 2)) & 3u;
-                v4 = (st & 1u) ? 0.f : 1.f;
-            }
-            o[5 * k] = v0; o[5 * k + 1] = v1; o[5 * k + 2] = v0; o[5 * k + 3] = v1; o[5 * k + 4] = v4;
-        }
+        switch_states_row(L.locked_slots, reinterpret_cast<const double *>(a.blob + L.off_ent_x),
+                          reinterpret_cast<const double *>(a.blob + L.off_ent_y), a.ent_bits, a.n, env, sw_out + (size_t)env * 25);
     }
     if ((l & 3) == 0 && el < n_here) {
         const int lvl = a.env_level[env];
@@ -100,16 +88,14 @@ __global__ __launch_bounds__(64) void npp_reach_kernel(KernelArgs a, const Reach
         const ReachHdr &H = rh[lvl];
         const ReachTabs T{&H, rblob + H.base};
         const double px = a.f64[(size_t)F_X * a.n + env], py = a.f64[(size_t)F_Y * a.n + env];
-        // exit_switch_activated (nplay_headless.py:566-576): not switch.active
-        bool sw = true;
-        if (L.obs_switch >= 0) sw = ((a.ent_bits[(size_t)(L.obs_switch >> 4) * a.n + env] >> ((L.obs_switch & 15) * 2)) & 3u) == 0;
+        const bool sw = exit_switch_activated(exit_switch_state(a.ent_bits, a.n, env, L.obs_switch));
         const int cx = reach_cell24(px), cy = reach_cell24(py);
         const uint32_t k = 0x80000000u | ((uint32_t)(cx & 0x3fff)) | ((uint32_t)(cy & 0x3fff) << 14) | ((uint32_t)sw << 28);
         // per-episode dictionary of the path calculator (ReachMiss): a reset of the env since the last call empties it.  The episode
-        // counter lives in state word E (npp_kernels.hip: Nj::fastord bits 2-14)
+        // counter is S_EPISODE (npp_state.hpp)
         ReachMiss M{nullptr, nullptr, 1u};
         if (md.stamp) {
-            const uint32_t ep = (a.u32[(size_t)U_E * a.n + env] >> 19) & 0x1fffu;
+            const uint32_t ep = (uint32_t)state_load(a.u32, a.n, env, S_EPISODE);
             uint32_t epoch = md.epoch[env];   // 0 = never called (stamps are 0 too: nothing may match)
             if (epoch == 0u || md.last_episode[env] != ep) {
                 epoch++;

@@ -205,11 +205,9 @@ struct DrawCtx {
     bool init;   // the level as it stands right after a reset: door states from the level's init words
 };
 
-__device__ inline uint32_t ent_state_of(const KernelArgs &a, int env, int slot) {
-    return (a.ent_bits[(size_t)(slot >> 4) * a.n + env] >> ((slot & 15) * 2)) & 3u;
-}
+__device__ inline uint32_t ent_state_of(const KernelArgs &a, int env, int slot) { return ent_state(a.ent_bits, a.n, env, slot); }
 __device__ inline uint32_t ent_state_ctx(const DrawCtx &c, int slot) {
-    if (c.init) return (reinterpret_cast<const uint32_t *>(c.a->blob + c.H->off_init_words)[slot >> 4] >> ((slot & 15) * 2)) & 3u;
+    if (c.init) return ent_state(reinterpret_cast<const uint32_t *>(c.a->blob + c.H->off_init_words), 1, 0, slot);
     return ent_state_of(*c.a, c.env, slot);
 }
 
@@ -458,7 +456,7 @@ __device__ inline void frame_build(FrameLds &L, const KernelArgs &a, const Level
         const uint32_t info = rc.z;
         const int slot = (int)(info >> 16);
         uint32_t sw = 0;   // the state word of the candidate's slot: every lane takes part in the cross-lane read
-        if (words_in_lanes) sw = (uint32_t)__shfl((int)entw, (slot >> 4) & 63, 64);
+        if (words_in_lanes) sw = (uint32_t)__shfl((int)entw, ent_word(slot) & 63, 64);
 #ifdef NPP_RENDER_STAMPS
         if (lane == 0 && v0 == 0) L.bst[1] = __builtin_amdgcn_s_memtime() + (sw & 0) + (rc.x & 0);
 #endif
@@ -470,7 +468,7 @@ __device__ inline void frame_build(FrameLds &L, const KernelArgs &a, const Level
             const bool live = rec_place(rc, z, false, x, y);
             if (live && !(x < wx0 || x > wx1 || y < wy0 || y > wy1)) {
                 uint32_t st = 1u;
-                if (!(info & 0x8000u)) st = words_in_lanes ? (sw >> ((slot & 15) * 2)) & 3u : ent_state_of(a, env, slot);
+                if (!(info & 0x8000u)) st = words_in_lanes ? ent_field(sw, slot) : ent_state_of(a, env, slot);
                 keep = rec_drawable(info, x, y, st, d);
             }
         } else if (v == n_door + n_draw) {   // the ninja, drawn last
@@ -1212,7 +1210,8 @@ __global__ __launch_bounds__(64, 3) void npp_global_view_kernel(KernelArgs a, in
             // both state codes of the record's slot through cross-lane reads of the word lanes (every lane takes part)
             uint32_t sh_now = 0u, sh_init = 0u;
             if (words_in_lanes) {
-                const int wl = (k < n_draw && !(rc.z & 0x8000u)) ? (int)((rc.z >> 16) >> 4) : 0;
+                const int rec_word = ent_word((int)(rc.z >> 16));   // (ahead of the condition: a select, not a branch)
+                const int wl = (k < n_draw && !(rc.z & 0x8000u)) ? rec_word : 0;
                 sh_now = (uint32_t)__shfl((int)w_now, wl, 64);
                 sh_init = (uint32_t)__shfl((int)w_init, wl, 64);
             }
@@ -1222,9 +1221,8 @@ __global__ __launch_bounds__(64, 3) void npp_global_view_kernel(KernelArgs a, in
                 const bool mover = (info & 0x8000u) != 0;
                 float x, y, x0, y0;   // where it is now, where it is right after a reset
                 const bool live = rec_place(rc, z, false, x, y), live0 = rec_place(rc, z, true, x0, y0);
-                const uint32_t st_now = mover ? 1u : (words_in_lanes ? (sh_now >> ((slot & 15) * 2)) & 3u : ent_state_of(a, env, slot));
-                const uint32_t st_init = words_in_lanes && !mover ? (sh_init >> ((slot & 15) * 2)) & 3u
-                                                                  : (init_words[slot >> 4] >> ((slot & 15) * 2)) & 3u;
+                const uint32_t st_now = mover ? 1u : (words_in_lanes ? ent_field(sh_now, slot) : ent_state_of(a, env, slot));
+                const uint32_t st_init = words_in_lanes && !mover ? ent_field(sh_init, slot) : ent_state(init_words, 1, 0, slot);
                 if (live && !(x < wx0 || x > wx1 || y < wy0 || y > wy1)) kc = rec_drawable(info, x, y, st_now, d);
                 // the usual record: a static entity in the state and at the place it has after a reset -> the drawable IS the
                 // init drawable, no dirty box, one evaluation instead of two (most of a level's mines, all its untouched gold)
@@ -1451,29 +1449,14 @@ __global__ __launch_bounds__(256) void npp_full_frame_kernel(KernelArgs a, int e
     for (int x = threadIdx.x; x < 1056; x += blockDim.x) row[x] = (uint8_t)canvas_pixel(s_draw, s_n, canvas, x, y);
 }
 
-// switch_states (gym_environment/npp_environment.py:1782-1847): up to MAX_LOCKED_DOORS = 5 locked doors x [switch x, switch y,
-// door x, door y, collected].  _extract_locked_door_positions looks for `segment.p1`, which GridSegmentLinear does not have
-// (entities.py: x1, y1, x2, y2), so the "door" position falls back to the entity's xpos / ypos -- the switch position
-// (entity_door_base.py:94-97).  Reproduced as is.
+// switch_states: one lane per env writes switch_states_row (npp_state.hpp)
 __global__ __launch_bounds__(256) void npp_switch_states_kernel(KernelArgs a, float *out) {
     const int env = blockIdx.x * 256 + threadIdx.x;
     if (env >= a.n) return;
     if (a.phase && a.phase_id >= 0 && a.phase[env] != (uint8_t)a.phase_id) return;
     const LevelHdr &H = a.hdr[a.env_level[env]];
-    const double *ex = reinterpret_cast<const double *>(a.blob + H.off_ent_x);
-    const double *ey = reinterpret_cast<const double *>(a.blob + H.off_ent_y);
-    float *o = out + (size_t)env * 25;
-    for (int k = 0; k < 5; k++) {
-        const int slot = H.locked_slots[k];
-        float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (slot >= 0) {
-            const double sx = ex[slot] / 1056.0, sy = ey[slot] / 600.0;
-            const float fx = (float)(sx < 0.0 ? 0.0 : (sx > 1.0 ? 1.0 : sx)), fy = (float)(sy < 0.0 ? 0.0 : (sy > 1.0 ? 1.0 : sy));
-            const uint32_t st = ent_state_of(a, env, slot);
-            v[0] = fx; v[1] = fy; v[2] = fx; v[3] = fy; v[4] = (st & 1u) ? 0.f : 1.f;
-        }
-        for (int j = 0; j < 5; j++) o[5 * k + j] = v[j];
-    }
+    switch_states_row(H.locked_slots, reinterpret_cast<const double *>(a.blob + H.off_ent_x),
+                      reinterpret_cast<const double *>(a.blob + H.off_ent_y), a.ent_bits, a.n, env, out + (size_t)env * 25);
 }
 
 }  // namespace

@@ -21,7 +21,7 @@
 #pragma once
 #include <cstdint>
 
-#include "npp_pool.hpp"   // NPP_HD
+#include "npp_state.hpp"   // NPP_HD
 
 namespace npp {
 
