@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libnpp_amd.so")
 SOURCES = ["npp_kernels.hip", "npp_render.hip", "npp_stack.hip", "npp_pool.hip", "npp_augment.hip", "npp_reach_kernel.hip", "npp_graph.hip", "npp_archive.hip", "npp_cells.hip", "npp_route.hip", "npp_pathmask.hip", "npp_capi.cpp", "npp_level.cpp", "npp_reach.cpp",
            "npp_graph.cpp", "npp_host.cpp"]
-HEADERS = ["npp_internal.hpp", "npp_level.hpp", "npp_zoo.hpp", "npp_reach.hpp", "npp_reach_build.hpp", "npp_reach_features.hpp",
+HEADERS = ["npp_internal.hpp", "npp_level.hpp", "npp_tilequery.hpp", "npp_zoo.hpp", "npp_reach.hpp", "npp_reach_build.hpp", "npp_reach_features.hpp",
            "npp_host.hpp", "npp_zoo_layout.hpp", "npp_pool.hpp", "npp_augment.hpp", "npp_graph.hpp", "npp_minimal.hpp", "npp_archive.hpp", "npp_cells.hpp", "npp_route.hpp", "npp_pathmask.hpp", "npp_state.hpp",
            "npp_reach_tables.inc", os.path.join("..", "..", "include", "npp_amd.h")]
 

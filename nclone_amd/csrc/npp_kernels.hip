@@ -283,187 +283,8 @@ DEV double toi_circle_arc(double px, double py, double vx, double vy, double vel
     return 1;
 }
 
-// GridSegment*.intersect_with_ray (entities.py:82-96,180-203)
-DEV double seg_toi(uint32_t s, int xc, int yc, double px, double py, double dx, double dy, double vel_sq, double radius) {
-    double ox = 24.0 * xc, oy = 24.0 * yc;
-    double t1, t2, t3;
-    if ((s & 1u) == 0) {
-        int ax = (s >> 2) & 3, ay = (s >> 4) & 3, bx = (s >> 6) & 3, by = (s >> 8) & 3;
-        double x1 = ox + 12.0 * ax, y1 = oy + 12.0 * ay, x2 = ox + 12.0 * bx, y2 = oy + 12.0 * by;
-        t1 = toi_circle_point(px, py, dx, dy, vel_sq, x1, y1, radius);
-        t2 = toi_circle_point(px, py, dx, dy, vel_sq, x2, y2, radius);
-        t3 = toi_circle_lineseg(px, py, dx, dy, x1, y1, bx - ax, by - ay, radius);
-    } else {
-        double cx = ox + 12.0 * ((s >> 2) & 3), cy = oy + 12.0 * ((s >> 4) & 3);
-        double hor = ((s >> 6) & 1) ? 1.0 : -1.0, ver = ((s >> 7) & 1) ? 1.0 : -1.0;
-        t1 = toi_circle_point(px, py, dx, dy, vel_sq, cx + 24.0 * hor, cy, radius);
-        t2 = toi_circle_point(px, py, dx, dy, vel_sq, cx, cy + 24.0 * ver, radius);
-        t3 = toi_circle_arc(px, py, dx, dy, vel_sq, cx, cy, hor, ver, radius);
-    }
-    double r = t1;
-    if (t2 < r) r = t2;
-    if (t3 < r) r = t3;
-    return r;
-}
+#include "npp_tilequery.hpp"
 
-// GridSegment*.get_closest_point (entities.py:43-59,127-157); returns is_back_facing; also yields the
-// segment's AABB (entities.py:36-41,119-125)
-DEV bool seg_closest(uint32_t s, int xc, int yc, double px, double py, double &a, double &b) {
-    double ox = 24.0 * xc, oy = 24.0 * yc;
-    if ((s & 1u) == 0) {
-        int ax = (s >> 2) & 3, ay = (s >> 4) & 3, bx = (s >> 6) & 3, by = (s >> 8) & 3;
-        double x1 = ox + 12.0 * ax, y1 = oy + 12.0 * ay;
-        double wx = 12.0 * (bx - ax), wy = 12.0 * (by - ay);
-        double dx = px - x1, dy = py - y1;
-        // seg_lensq is 144 (axis aligned), 1152 (45 degrees) or 720 (the two gentle/steep slopes)
-        int aw = (bx - ax) * (bx - ax) + (by - ay) * (by - ay);   // 1, 8 or 5 in units of 144
-        double num = dx * wx + dy * wy;
-        double u = aw == 1 ? div_const(num, 144.0, 1.0 / 144.0)
-                 : (aw == 8 ? div_const(num, 1152.0, 1.0 / 1152.0)
-                 : (aw == 5 ? div_const(num, 720.0, 1.0 / 720.0) : num / (sq(wx) + sq(wy))));
-        u = pymax(u, 0.0);
-        u = pymin(u, 1.0);
-        a = x1 + u * wx;
-        b = y1 + u * wy;
-        return dy * wx - dx * wy < 0;   // tile segments are always oriented
-    }
-    double cx = ox + 12.0 * ((s >> 2) & 3), cy = oy + 12.0 * ((s >> 4) & 3);
-    double hor = ((s >> 6) & 1) ? 1.0 : -1.0, ver = ((s >> 7) & 1) ? 1.0 : -1.0;
-    bool convex = (s >> 8) & 1;
-    double dx = px - cx, dy = py - cy;
-    bool back = false;
-    if (dx * hor > 0 && dy * ver > 0) {
-        double dist = dsqrt(sq(dx) + sq(dy));
-        if (dist == 0) {
-            if (dx * hor > dy * ver) { a = cx + 24.0 * hor; b = cy; }
-            else { a = cx; b = cy + 24.0 * ver; }
-            return false;
-        }
-        a = cx + 24.0 * dx / dist;
-        b = cy + 24.0 * dy / dist;
-        back = convex ? (dist < 24.0) : (dist > 24.0);
-    } else {
-        if (dx * hor > dy * ver) { a = cx + 24.0 * hor; b = cy; }
-        else { a = cx; b = cy + 24.0 * ver; }
-    }
-    return back;
-}
-
-DEV void seg_aabb(uint32_t s, int xc, int yc, double &x0, double &y0, double &x1, double &y1) {
-    int ux0, uy0, ux1, uy1;
-    if ((s & 1u) == 0) {
-        int ax = (s >> 2) & 3, ay = (s >> 4) & 3, bx = (s >> 6) & 3, by = (s >> 8) & 3;
-        ux0 = ax < bx ? ax : bx; ux1 = ax < bx ? bx : ax;
-        uy0 = ay < by ? ay : by; uy1 = ay < by ? by : ay;
-    } else {
-        int cx = (s >> 2) & 3, cy = (s >> 4) & 3;
-        int hx = cx + (((s >> 6) & 1) ? 2 : -2), vy = cy + (((s >> 7) & 1) ? 2 : -2);
-        ux0 = cx < hx ? cx : hx; ux1 = cx < hx ? hx : cx;
-        uy0 = cy < vy ? cy : vy; uy1 = cy < vy ? vy : cy;
-    }
-    x0 = 24.0 * xc + 12.0 * ux0; x1 = 24.0 * xc + 12.0 * ux1;
-    y0 = 24.0 * yc + 12.0 * uy0; y1 = 24.0 * yc + 12.0 * uy1;
-}
-
-// ---- cooperative groups of G lanes per environment -------------------------------------------------------------
-// All G lanes of a group hold the same ninja state and execute the same scalar code redundantly; they split up only
-// the per-segment work of a region query (lane r takes segments r, r+G, ... of the query's flat order) and combine
-// with DPP butterflies.  Order-dependent semantics of the reference are preserved exactly: minima are
-// order-independent, "first wins" ties (physics.py:176 strict <) are broken by the flat query index, and the wall
-// probe's sum (ninja.py:441) is accumulated in query order.
-// The butterfly partner always lies in the same lane group, whose lanes execute together, so it is always active:
-// bound_ctrl lets the compiler fold the move into the consuming instruction instead of keeping a copy for `old`.
-template <int CTRL> DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-template <int CTRL> DEV double dpp_d(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = dpp_i<CTRL>(lo);
-    hi = dpp_i<CTRL>(hi);
-    return __hiloint2double(hi, lo);
-}
-// value held by the butterfly partner at distance STEP (1,2: quad_perm; 4: row_half_mirror; 8: row_mirror)
-template <int STEP> DEV int partner_i(int v) {
-    if constexpr (STEP == 1) return dpp_i<0xB1>(v);
-    else if constexpr (STEP == 2) return dpp_i<0x4E>(v);
-    else if constexpr (STEP == 4) return dpp_i<0x141>(v);
-    else if constexpr (STEP == 8) return dpp_i<0x140>(v);
-    else return __shfl_xor(v, STEP, 64);
-}
-template <int STEP> DEV double partner_d(double v) {
-    if constexpr (STEP == 1) return dpp_d<0xB1>(v);
-    else if constexpr (STEP == 2) return dpp_d<0x4E>(v);
-    else if constexpr (STEP == 4) return dpp_d<0x141>(v);
-    else if constexpr (STEP == 8) return dpp_d<0x140>(v);
-    else return __shfl_xor(v, STEP, 64);
-}
-
-// v_min_f64 without the canonicalising v_max_f64 x, x, x that llvm.minnum puts in front of every operand it cannot prove
-// quiet (anything that went through a select or a DPP move): the operands here are never NaN (+inf / 1 mark "none"), and each
-// such instruction is ~7 cycles of the single wavefront's issue cadence inside the depenetration loop (five per iteration).
-DEV double min_nonan(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-template <int G, int STEP = 1> DEV double group_min(double t) {
-    if constexpr (STEP < G) {
-        t = min_nonan(t, partner_d<STEP>(t));
-        return group_min<G, STEP * 2>(t);
-    } else {
-        return t;
-    }
-}
-
-struct Best {
-    double key;   // biased squared distance (physics.py:171-176)
-    int idx;      // flat query index << 8 | evaluating lane's rank in its group << 1 | is_back_facing
-    double a, b;  // closest point
-};
-
-template <int G, int STEP = 1> DEV int group_min_i(int v) {
-    if constexpr (STEP < G) {
-        int o = partner_i<STEP>(v);
-        v = o < v ? o : v;
-        return group_min_i<G, STEP * 2>(v);
-    } else {
-        return v;
-    }
-}
-
-// Group-wide "first wins" argmin (physics.py:176 strict <): smallest key, ties broken by the smallest flat query
-// index.  Two cheap butterflies (key, then index among the lanes holding the minimum key) and one cross-lane fetch
-// of the winner's closest point; every lane of the group ends up with the same m.
-template <int G> DEV void group_argmin(Best &m) {
-    if constexpr (G > 1) {
-        const double kmin = group_min<G>(m.key);
-        const int cand = (m.idx != 0x7fffffff && m.key == kmin) ? m.idx : 0x7fffffff;
-        const int imin = group_min_i<G>(cand);
-        const int src = (((threadIdx.x & 63) & ~(G - 1)) + ((imin >> 1) & 63)) << 2;   // winner lane, byte address
-        int alo = __builtin_amdgcn_ds_bpermute(src, __double2loint(m.a)), ahi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(m.a));
-        int blo = __builtin_amdgcn_ds_bpermute(src, __double2loint(m.b)), bhi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(m.b));
-        m.key = kmin;
-        m.idx = imin;
-        m.a = __hiloint2double(ahi, alo);
-        m.b = __hiloint2double(bhi, blo);
-    }
-}
-
-// SpatialSegmentIndex.query_region cell filter (utils/spatial_segment_index.py:140-156, inclusive test :186-188)
-DEV bool cell_passes(uint32_t cb, int xc, int yc, double qx0, double qy0, double qx1, double qy1) {
-    double bx0 = 24.0 * xc + 12.0 * (cb & 3), by0 = 24.0 * yc + 12.0 * ((cb >> 2) & 3);
-    double bx1 = 24.0 * xc + 12.0 * ((cb >> 4) & 3), by1 = 24.0 * yc + 12.0 * ((cb >> 6) & 3);
-    return !(qx1 < bx0 || qx0 > bx1 || qy1 < by0 || qy0 > by1);
-}
-
-// ---- per-tick candidate registers (fast path) ------------------------------------------------------------------
-// Once per tick every lane group gathers ALL segments of the cells around the ninja's path (old position -> new
-// position, inflated by the largest query radius) and keeps them decoded in registers: lane r holds candidates
-// r, r + G, ... of the region's x-major order (K slots per lane).  A region query of the reference (sweep box,
-// depenetration gather box, wall-probe box) whose clamped cell range lies inside the gathered range is then
-// answered from registers by applying the reference's own filters per candidate (cell range, inclusive cell-bounds
-// test, per-segment AABB test) -- the surviving candidates in flat order are exactly the reference's list.  A query
-// that leaves the region (or a region with more segments than lanes x slots) falls back to the LDS walk below.
-// All filters are evaluated in doubles on exact quantities (multiples of 12 px), so no integer cell arithmetic is
-// needed on the fast path.
 template <int G> struct KSlots { static constexpr int value = G >= 32 ? 1 : (G >= 16 ? 2 : 4); };
 // Build variants of the G = 16 plain (non-zoo) step kernels, chosen per handle by npp_step's autotuner (npp_capi.cpp) because no
 // one of them wins everywhere (8192 envs, MI355X, end of round 2):
@@ -475,297 +296,6 @@ template <int G> struct KSlots { static constexpr int value = G >= 32 ? 1 : (G >
 //                                                               fastest single chain wins)
 // All variants give the same bits (tests/test_gpu_parity.py).  Other G and the zoo kernels exist as V = 0 only.
 template <int G, bool ZOO, int V> struct VariantK { static constexpr int value = (G == 16 && !ZOO && V == 1) ? 1 : KSlots<G>::value; };
-
-DEV double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// A query box plus copies clamped to the map: clamp(floor(q / 24), 0, 43) == floor(clamp(q, 0, 1032) / 24) and
-// likewise with 576 for y (utils/spatial_segment_index.py:131-134), so "cell xc is inside the query's clamped cell
-// range" is 24 xc <= clamp(qx1) && 24 (xc + 1) > clamp(qx0).
-struct QBox {
-    double x0, y0, x1, y1;
-    double cx0, cy0, cx1, cy1;
-};
-DEV QBox make_qbox(double x0, double y0, double x1, double y1) {
-    QBox q;
-    q.x0 = x0; q.y0 = y0; q.x1 = x1; q.y1 = y1;
-    q.cx0 = clampd(x0, 0.0, 1032.0); q.cx1 = clampd(x1, 0.0, 1032.0);
-    q.cy0 = clampd(y0, 0.0, 576.0); q.cy1 = clampd(y1, 0.0, 576.0);
-    return q;
-}
-
-// The per-segment AABB test of get_single_closest_point (physics.py:150-167) against the ninja's box [x - 10, x + 10] x [y - 10, y + 10],
-// as exact thresholds on x and y: segment bounds are multiples of 12 in [0, 1056], the reference rounds x - 10 and x + 10 before it
-// compares, and rounding is monotone, so "not (b1 < fl(x - 10))" is "x <= b1 + 10" (b1 + 10 is exact and its ulp is at least b1's) and
-// "not (b0 > fl(x + 10))" is "x >= AABB_LO[b0 / 12]", the smallest double whose rounded sum reaches b0 (it lies below b0 - 10 where b0 - 10
-// sits in a lower binade than b0: 8 of the 89 entries).  Generated and checked against the rounded sums on 40 doubles either side of every
-// threshold (tests/test_host_cpu.py repeats the check on the table below); saves the four fp64 additions per candidate and iteration.
-__constant__ double AABB_LO[89] = {
-    -0x1.4000000000000p+3 /* 0: fl(x + 10) >= 0 */,
-    0x1.ffffffffffffcp+0 /* 1: fl(x + 10) >= 12 */,
-    0x1.bffffffffffffp+3 /* 2: fl(x + 10) >= 24 */,
-    0x1.9ffffffffffffp+4 /* 3: fl(x + 10) >= 36 */,
-    0x1.3000000000000p+5 /* 4: fl(x + 10) >= 48 */,
-    0x1.9000000000000p+5 /* 5: fl(x + 10) >= 60 */,
-    0x1.effffffffffffp+5 /* 6: fl(x + 10) >= 72 */,
-    0x1.2800000000000p+6 /* 7: fl(x + 10) >= 84 */,
-    0x1.5800000000000p+6 /* 8: fl(x + 10) >= 96 */,
-    0x1.8800000000000p+6 /* 9: fl(x + 10) >= 108 */,
-    0x1.b800000000000p+6 /* 10: fl(x + 10) >= 120 */,
-    0x1.e7fffffffffffp+6 /* 11: fl(x + 10) >= 132 */,
-    0x1.0c00000000000p+7 /* 12: fl(x + 10) >= 144 */,
-    0x1.2400000000000p+7 /* 13: fl(x + 10) >= 156 */,
-    0x1.3c00000000000p+7 /* 14: fl(x + 10) >= 168 */,
-    0x1.5400000000000p+7 /* 15: fl(x + 10) >= 180 */,
-    0x1.6c00000000000p+7 /* 16: fl(x + 10) >= 192 */,
-    0x1.8400000000000p+7 /* 17: fl(x + 10) >= 204 */,
-    0x1.9c00000000000p+7 /* 18: fl(x + 10) >= 216 */,
-    0x1.b400000000000p+7 /* 19: fl(x + 10) >= 228 */,
-    0x1.cc00000000000p+7 /* 20: fl(x + 10) >= 240 */,
-    0x1.e400000000000p+7 /* 21: fl(x + 10) >= 252 */,
-    0x1.fbfffffffffffp+7 /* 22: fl(x + 10) >= 264 */,
-    0x1.0a00000000000p+8 /* 23: fl(x + 10) >= 276 */,
-    0x1.1600000000000p+8 /* 24: fl(x + 10) >= 288 */,
-    0x1.2200000000000p+8 /* 25: fl(x + 10) >= 300 */,
-    0x1.2e00000000000p+8 /* 26: fl(x + 10) >= 312 */,
-    0x1.3a00000000000p+8 /* 27: fl(x + 10) >= 324 */,
-    0x1.4600000000000p+8 /* 28: fl(x + 10) >= 336 */,
-    0x1.5200000000000p+8 /* 29: fl(x + 10) >= 348 */,
-    0x1.5e00000000000p+8 /* 30: fl(x + 10) >= 360 */,
-    0x1.6a00000000000p+8 /* 31: fl(x + 10) >= 372 */,
-    0x1.7600000000000p+8 /* 32: fl(x + 10) >= 384 */,
-    0x1.8200000000000p+8 /* 33: fl(x + 10) >= 396 */,
-    0x1.8e00000000000p+8 /* 34: fl(x + 10) >= 408 */,
-    0x1.9a00000000000p+8 /* 35: fl(x + 10) >= 420 */,
-    0x1.a600000000000p+8 /* 36: fl(x + 10) >= 432 */,
-    0x1.b200000000000p+8 /* 37: fl(x + 10) >= 444 */,
-    0x1.be00000000000p+8 /* 38: fl(x + 10) >= 456 */,
-    0x1.ca00000000000p+8 /* 39: fl(x + 10) >= 468 */,
-    0x1.d600000000000p+8 /* 40: fl(x + 10) >= 480 */,
-    0x1.e200000000000p+8 /* 41: fl(x + 10) >= 492 */,
-    0x1.ee00000000000p+8 /* 42: fl(x + 10) >= 504 */,
-    0x1.f9fffffffffffp+8 /* 43: fl(x + 10) >= 516 */,
-    0x1.0300000000000p+9 /* 44: fl(x + 10) >= 528 */,
-    0x1.0900000000000p+9 /* 45: fl(x + 10) >= 540 */,
-    0x1.0f00000000000p+9 /* 46: fl(x + 10) >= 552 */,
-    0x1.1500000000000p+9 /* 47: fl(x + 10) >= 564 */,
-    0x1.1b00000000000p+9 /* 48: fl(x + 10) >= 576 */,
-    0x1.2100000000000p+9 /* 49: fl(x + 10) >= 588 */,
-    0x1.2700000000000p+9 /* 50: fl(x + 10) >= 600 */,
-    0x1.2d00000000000p+9 /* 51: fl(x + 10) >= 612 */,
-    0x1.3300000000000p+9 /* 52: fl(x + 10) >= 624 */,
-    0x1.3900000000000p+9 /* 53: fl(x + 10) >= 636 */,
-    0x1.3f00000000000p+9 /* 54: fl(x + 10) >= 648 */,
-    0x1.4500000000000p+9 /* 55: fl(x + 10) >= 660 */,
-    0x1.4b00000000000p+9 /* 56: fl(x + 10) >= 672 */,
-    0x1.5100000000000p+9 /* 57: fl(x + 10) >= 684 */,
-    0x1.5700000000000p+9 /* 58: fl(x + 10) >= 696 */,
-    0x1.5d00000000000p+9 /* 59: fl(x + 10) >= 708 */,
-    0x1.6300000000000p+9 /* 60: fl(x + 10) >= 720 */,
-    0x1.6900000000000p+9 /* 61: fl(x + 10) >= 732 */,
-    0x1.6f00000000000p+9 /* 62: fl(x + 10) >= 744 */,
-    0x1.7500000000000p+9 /* 63: fl(x + 10) >= 756 */,
-    0x1.7b00000000000p+9 /* 64: fl(x + 10) >= 768 */,
-    0x1.8100000000000p+9 /* 65: fl(x + 10) >= 780 */,
-    0x1.8700000000000p+9 /* 66: fl(x + 10) >= 792 */,
-    0x1.8d00000000000p+9 /* 67: fl(x + 10) >= 804 */,
-    0x1.9300000000000p+9 /* 68: fl(x + 10) >= 816 */,
-    0x1.9900000000000p+9 /* 69: fl(x + 10) >= 828 */,
-    0x1.9f00000000000p+9 /* 70: fl(x + 10) >= 840 */,
-    0x1.a500000000000p+9 /* 71: fl(x + 10) >= 852 */,
-    0x1.ab00000000000p+9 /* 72: fl(x + 10) >= 864 */,
-    0x1.b100000000000p+9 /* 73: fl(x + 10) >= 876 */,
-    0x1.b700000000000p+9 /* 74: fl(x + 10) >= 888 */,
-    0x1.bd00000000000p+9 /* 75: fl(x + 10) >= 900 */,
-    0x1.c300000000000p+9 /* 76: fl(x + 10) >= 912 */,
-    0x1.c900000000000p+9 /* 77: fl(x + 10) >= 924 */,
-    0x1.cf00000000000p+9 /* 78: fl(x + 10) >= 936 */,
-    0x1.d500000000000p+9 /* 79: fl(x + 10) >= 948 */,
-    0x1.db00000000000p+9 /* 80: fl(x + 10) >= 960 */,
-    0x1.e100000000000p+9 /* 81: fl(x + 10) >= 972 */,
-    0x1.e700000000000p+9 /* 82: fl(x + 10) >= 984 */,
-    0x1.ed00000000000p+9 /* 83: fl(x + 10) >= 996 */,
-    0x1.f300000000000p+9 /* 84: fl(x + 10) >= 1008 */,
-    0x1.f900000000000p+9 /* 85: fl(x + 10) >= 1020 */,
-    0x1.fefffffffffffp+9 /* 86: fl(x + 10) >= 1032 */,
-    0x1.0280000000000p+10 /* 87: fl(x + 10) >= 1044 */,
-    0x1.0580000000000p+10 /* 88: fl(x + 10) >= 1056 */
-};
-
-template <int K> struct Cand {
-    double rx0, ry0, rx1, ry1;   // gathered cell range in pixels: [24 c0, 24 (c1 + 1))
-    bool ok;
-    uint32_t s[K];               // packed segment (bits 0-15, incl. cell y) | cell x << 16 | valid << 31
-    double x1[K], y1[K], x2[K], y2[K];       // linear: end points; arc: centre, p_hor.x, p_ver.y
-    double wx[K], wy[K], l2[K], rl2[K];      // linear: segment vector, |w|^2 and RN(1 / |w|^2)
-    double ox[K], oy[K];                     // origin of the owning cell
-    double bx0[K], by0[K], bx1[K], by1[K];   // the owning cell's bounds over its segments (:86-105)
-    double tx0[K], tx1[K], ty0[K], ty1[K];   // the segment's AABB as thresholds on the ninja position (AABB_LO above): tx0 <= x <= tx1, ...
-};
-
-template <int G, int K>
-DEV void cand_gather(const Lv &lv, int r, double qx0, double qy0, double qx1, double qy1, Cand<K> &c) {
-    const int c0x = cell_coord(qx0, 43), c1x = cell_coord(qx1, 43), c0y = cell_coord(qy0, 24), c1y = cell_coord(qy1, 24);
-    c.rx0 = 24.0 * c0x; c.rx1 = 24.0 * (c1x + 1); c.ry0 = 24.0 * c0y; c.ry1 = 24.0 * (c1y + 1);
-    const int ncol = c1x - c0x + 1;
-    int a0 = lv.seg_start[c0x * 25 + c0y], n0 = lv.seg_start[c0x * 25 + c1y + 1] - a0;
-    int a1 = 0, n1 = 0, a2 = 0, n2 = 0;
-    if (ncol > 1) { a1 = lv.seg_start[(c0x + 1) * 25 + c0y]; n1 = lv.seg_start[(c0x + 1) * 25 + c1y + 1] - a1; }
-    if (ncol > 2) { a2 = lv.seg_start[(c0x + 2) * 25 + c0y]; n2 = lv.seg_start[(c0x + 2) * 25 + c1y + 1] - a2; }
-    const int total = n0 + n1 + n2;
-    c.ok = ncol <= 3 && total <= G * K;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        int f = k * G + r;
-        c.s[k] = 0;
-        c.x1[k] = 0; c.y1[k] = 0; c.x2[k] = 0; c.y2[k] = 0; c.wx[k] = 0; c.wy[k] = 0; c.l2[k] = 1; c.rl2[k] = 1;
-        c.ox[k] = 0; c.oy[k] = 0; c.bx0[k] = 0; c.by0[k] = 0; c.bx1[k] = 0; c.by1[k] = 0;
-        c.tx0[k] = 0; c.tx1[k] = 0; c.ty0[k] = 0; c.ty1[k] = 0;
-        if (c.ok && f < total) {
-            int xc = c0x, i = a0 + f;
-            if (f >= n0) { xc += 1; i = a1 + (f - n0); }
-            if (f >= n0 + n1) { xc += 1; i = a2 + (f - n0 - n1); }
-            uint32_t s = lv.segs[i];
-            int yc = s >> 11;
-            uint32_t cb = lv.bounds[xc * 25 + yc];
-            c.s[k] = s | ((uint32_t)xc << 16) | 0x80000000u;
-            double ox = 24.0 * xc, oy = 24.0 * yc;
-            c.ox[k] = ox; c.oy[k] = oy;
-            c.bx0[k] = ox + 12.0 * (cb & 3); c.by0[k] = oy + 12.0 * ((cb >> 2) & 3);
-            c.bx1[k] = ox + 12.0 * ((cb >> 4) & 3); c.by1[k] = oy + 12.0 * ((cb >> 6) & 3);
-            c.x1[k] = ox + 12.0 * ((s >> 2) & 3); c.y1[k] = oy + 12.0 * ((s >> 4) & 3);
-            if ((s & 1u) == 0) {
-                c.x2[k] = ox + 12.0 * ((s >> 6) & 3); c.y2[k] = oy + 12.0 * ((s >> 8) & 3);
-                int wxu = (int)((s >> 6) & 3) - (int)((s >> 2) & 3), wyu = (int)((s >> 8) & 3) - (int)((s >> 4) & 3);
-                int aw = wxu * wxu + wyu * wyu;   // |w|^2 / 144: 1 axis aligned, 8 at 45 degrees, 5 for the 1:2 slopes
-                c.wx[k] = 12.0 * wxu; c.wy[k] = 12.0 * wyu;
-                c.l2[k] = aw == 1 ? 144.0 : (aw == 8 ? 1152.0 : 720.0);
-                c.rl2[k] = aw == 1 ? 1.0 / 144.0 : (aw == 8 ? 1.0 / 1152.0 : 1.0 / 720.0);
-                if (!(aw == 1 || aw == 8 || aw == 5)) c.ok = false;   // never produced by the tile tables
-            } else {
-                c.x2[k] = c.x1[k] + (((s >> 6) & 1) ? 24.0 : -24.0);   // p_hor.x (entities.py:113)
-                c.y2[k] = c.y1[k] + (((s >> 7) & 1) ? 24.0 : -24.0);   // p_ver.y (entities.py:114)
-            }
-            {   // AABB of the segment in units of 12 px (entities.py:36-41,119-125): min / max of (x1, x2) and of (y1, y2)
-                const int ux1 = 2 * xc + (int)((s >> 2) & 3), uy1 = 2 * yc + (int)((s >> 4) & 3);
-                int ux2, uy2;
-                if ((s & 1u) == 0) { ux2 = 2 * xc + (int)((s >> 6) & 3); uy2 = 2 * yc + (int)((s >> 8) & 3); }
-                else { ux2 = ux1 + (((s >> 6) & 1) ? 2 : -2); uy2 = uy1 + (((s >> 7) & 1) ? 2 : -2); }
-                const int ulo = ux1 < ux2 ? ux1 : ux2, uhi = ux1 < ux2 ? ux2 : ux1, vlo = uy1 < uy2 ? uy1 : uy2, vhi = uy1 < uy2 ? uy2 : uy1;
-                if (ulo < 0 || uhi > 88 || vlo < 0 || vhi > 88) c.ok = false;   // never produced by the tile tables
-                c.tx0[k] = AABB_LO[ulo < 0 ? 0 : (ulo > 88 ? 88 : ulo)]; c.tx1[k] = 12.0 * uhi + 10.0;
-                c.ty0[k] = AABB_LO[vlo < 0 ? 0 : (vlo > 88 ? 88 : vlo)]; c.ty1[k] = 12.0 * vhi + 10.0;
-            }
-        }
-    }
-    if constexpr (G > 1) {   // the "unexpected segment length" veto must be group-wide
-        const int glane0 = (threadIdx.x & 63) & ~(G - 1);
-        unsigned long long bad = __ballot(!c.ok) >> glane0;
-        if constexpr (G < 64) bad &= (1ull << G) - 1;
-        c.ok = bad == 0;
-    }
-}
-
-template <int K> DEV bool cand_covers(const Cand<K> &c, const QBox &q) {
-    return c.ok & (q.cx0 >= c.rx0) & (q.cx1 < c.rx1) & (q.cy0 >= c.ry0) & (q.cy1 < c.ry1);
-}
-
-// would the reference's query have returned candidate k?  (its cell inside the query's clamped cell range and the
-// inclusive cell-bounds test of utils/spatial_segment_index.py:186-188)
-template <int K> DEV bool cand_in_box(const Cand<K> &c, int k, const QBox &q) {
-    bool in_range = (c.ox[k] <= q.cx1) & (c.ox[k] + 24.0 > q.cx0) & (c.oy[k] <= q.cy1) & (c.oy[k] + 24.0 > q.cy0);
-    bool reject = (q.x1 < c.bx0[k]) | (q.x0 > c.bx1[k]) | (q.y1 < c.by0[k]) | (q.y0 > c.by1[k]);
-    return (c.s[k] >> 31) & in_range & !reject;
-}
-
-template <int G> DEV bool group_any(bool v) {
-    if constexpr (G == 1) return v;
-    const int glane0 = (threadIdx.x & 63) & ~(G - 1);
-    unsigned long long bal = __ballot(v) >> glane0;
-    if constexpr (G < 64) bal &= (1ull << G) - 1;
-    return bal != 0;
-}
-
-// intersect_with_ray on a decoded candidate (entities.py:82-96,180-203)
-DEV double cand_toi(uint32_t s, double x1, double y1, double x2, double y2, double px, double py, double dx, double dy,
-                    double vel_sq, double radius) {
-    double t1, t2, t3;
-    if ((s & 1u) == 0) {
-        int wxu = (int)((s >> 6) & 3) - (int)((s >> 2) & 3), wyu = (int)((s >> 8) & 3) - (int)((s >> 4) & 3);
-        t1 = toi_circle_point(px, py, dx, dy, vel_sq, x1, y1, radius);
-        t2 = toi_circle_point(px, py, dx, dy, vel_sq, x2, y2, radius);
-        t3 = toi_circle_lineseg(px, py, dx, dy, x1, y1, wxu, wyu, radius);
-    } else {
-        double hor = ((s >> 6) & 1) ? 1.0 : -1.0, ver = ((s >> 7) & 1) ? 1.0 : -1.0;
-        t1 = toi_circle_point(px, py, dx, dy, vel_sq, x2, y1, radius);
-        t2 = toi_circle_point(px, py, dx, dy, vel_sq, x1, y2, radius);
-        t3 = toi_circle_arc(px, py, dx, dy, vel_sq, x1, y1, hor, ver, radius);
-    }
-    double t = t1;
-    if (t2 < t) t = t2;
-    if (t3 < t) t = t3;
-    return t;
-}
-
-// GridSegmentCircular.get_closest_point on a decoded candidate (entities.py:127-157)
-DEV bool cand_closest_arc(uint32_t s, double x1, double y1, double x2, double y2, double px, double py,
-                                              double &a, double &b) {
-    double hor = ((s >> 6) & 1) ? 1.0 : -1.0, ver = ((s >> 7) & 1) ? 1.0 : -1.0;
-    bool convex = (s >> 8) & 1;
-    double dx = px - x1, dy = py - y1;
-    bool back = false;
-    if (dx * hor > 0 && dy * ver > 0) {
-        double dist = dsqrt(sq(dx) + sq(dy));
-        if (dist == 0) {
-            if (dx * hor > dy * ver) { a = x2; b = y1; }
-            else { a = x1; b = y2; }
-            return false;
-        }
-        a = x1 + 24.0 * dx / dist;
-        b = y1 + 24.0 * dy / dist;
-        back = convex ? (dist < 24.0) : (dist > 24.0);
-    } else {
-        if (dx * hor > dy * ver) { a = x2; b = y1; }
-        else { a = x1; b = y2; }
-    }
-    return back;
-}
-
-// GridSegmentLinear.get_closest_point (entities.py:43-59) on decoded registers, branch-free.  max/min are the
-// hardware ones: they differ from Python's max(u, 0) / min(u, 1) only in the sign of a zero u, which cannot reach
-// a or b (x1 + (+-0) * w == x1).
-template <int K> DEV bool cand_closest_lin(const Cand<K> &c, int k, double px, double py, double &a, double &b) {
-    double dx = px - c.x1[k], dy = py - c.y1[k];
-    double num = dx * c.wx[k] + dy * c.wy[k];
-    double u = div_const(num, c.l2[k], c.rl2[k]);
-    u = __builtin_fmax(u, 0.0);
-    u = __builtin_fmin(u, 1.0);
-    a = c.x1[k] + u * c.wx[k];
-    b = c.y1[k] + u * c.wy[k];
-    return dy * c.wx[k] - dx * c.wy[k] < 0;
-}
-
-// sweep_circle_vs_tiles (physics.py:104-128).  The early `return 0` of the reference equals the minimum.
-template <int G>
-__device__ __noinline__ double sweep_generic(TileRefs lv, int r, double xo, double yo, double dx, double dy, double radius) {
-    double xn = xo + dx, yn = yo + dy;
-    double width = radius + 1;
-    double qx0 = (xo < xn ? xo : xn) - width, qy0 = (yo < yn ? yo : yn) - width;
-    double qx1 = (xo > xn ? xo : xn) + width, qy1 = (yo > yn ? yo : yn) + width;
-    int c0x = cell_coord(qx0, 43), c1x = cell_coord(qx1, 43), c0y = cell_coord(qy0, 24), c1y = cell_coord(qy1, 24);
-    double vel_sq = sq(dx) + sq(dy);
-    double shortest = 1;
-    for (int xc = c0x; xc <= c1x; xc++) {
-        int i0 = lv.seg_start[xc * 25 + c0y], i1 = lv.seg_start[xc * 25 + c1y + 1];   // the column's cells are contiguous
-        for (int i = i0 + r; i < i1; i += G) {
-            uint32_t s = lv.segs[i];
-            int yc = s >> 11;
-            if (!cell_passes(lv.bounds[xc * 25 + yc], xc, yc, qx0, qy0, qx1, qy1)) continue;
-            double t = seg_toi(s, xc, yc, xo, yo, dx, dy, vel_sq, radius);
-            if (t < shortest) shortest = t;
-        }
-    }
-    return group_min<G>(shortest);
-}
 
 // sqrt(x) and 1/x for operands that are known to be normal and far from the exponent limits (1e-16 <= x <= 1e8):
 // exactly the instruction sequences hipcc emits for IEEE f64 sqrt and division (v_rsq / v_rcp seed, Newton-Raphson
@@ -855,31 +385,11 @@ DEV void crush_add(DepenIOZ &io, double dx, double dy, double len) { io.xcr += d
 template <int G, typename IO>
 __device__ __noinline__ void depen_generic(TileRefs lv, int r, double gx0, double gy0, double gx1, double gy1, IO *slot) {
     IO io = *slot;
-    const int c0x = cell_coord(gx0, 43), c1x = cell_coord(gx1, 43), c0y = cell_coord(gy0, 24), c1y = cell_coord(gy1, 24);
     const NPP_DEPEN_CONSTS
     for (int it = 0; it < 32; it++) {
-        Best m;
-        m.key = __builtin_inf(); m.idx = 0x7fffffff; m.a = 0; m.b = 0;
-        const double qx0 = io.x - NINJA_RADIUS, qy0 = io.y - NINJA_RADIUS, qx1 = io.x + NINJA_RADIUS, qy1 = io.y + NINJA_RADIUS;
-        int base = 0;
-        for (int xc = c0x; xc <= c1x; xc++) {
-            int i0 = lv.seg_start[xc * 25 + c0y], i1 = lv.seg_start[xc * 25 + c1y + 1];
-            for (int i = i0 + r; i < i1; i += G) {
-                uint32_t s = lv.segs[i];
-                int yc = s >> 11;
-                if (!cell_passes(lv.bounds[xc * 25 + yc], xc, yc, gx0, gy0, gx1, gy1)) continue;
-                double bx0, by0, bx1, by1;
-                seg_aabb(s, xc, yc, bx0, by0, bx1, by1);
-                if (bx1 < qx0 || bx0 > qx1 || by1 < qy0 || by0 > qy1) continue;
-                double a, b;
-                bool back = seg_closest(s, xc, yc, io.x, io.y, a, b);
-                double distance_sq = sq(io.x - a) + sq(io.y - b);
-                if (!back) distance_sq -= dk_bias;
-                if (distance_sq < m.key) { m.key = distance_sq; m.a = a; m.b = b; m.idx = ((base + i - i0) << 8) | (r << 1) | (back ? 1 : 0); }
-            }
-            base += i1 - i0;
-        }
-        group_argmin<G>(m);
+        // the cell filter keeps the gather box, the per-segment AABB test follows the moving position
+        const Best m = region_closest<G, true>(lv, r, io.x, io.y, gx0, gy0, gx1, gy1, io.x - NINJA_RADIUS, io.y - NINJA_RADIUS,
+                                         io.x + NINJA_RADIUS, io.y + NINJA_RADIUS, dk_bias);
         NPP_DEPEN_STEP(io, m, break)
     }
     if (r == 0) *slot = io;
@@ -935,33 +445,7 @@ template <int G, int K, bool ZOO>
 DEV int collide_vs_tiles(const Lv &lv, int r, Nj &n, const Cand<K> &cd, double xold, double yold, double &fnsx, double &fnsy,
                           double &cnsx, double &cnsy, Crush &cr STAMP_ARG) {
     double dx = n.x - xold, dy = n.y - yold;
-    // ---- sweep_circle_vs_tiles (physics.py:104-128); the early `return 0` of the reference equals the minimum
-    double time = 1;
-    {
-        const double radius = NINJA_RADIUS * 0.5, width = radius + 1;
-        double xn = xold + dx, yn = yold + dy;
-        const QBox q = make_qbox((xold < xn ? xold : xn) - width, (yold < yn ? yold : yn) - width,
-                                 (xold > xn ? xold : xn) + width, (yold > yn ? yold : yn) + width);
-        if (cand_covers(cd, q)) {
-            bool in[K];
-            bool any = false;
-#pragma unroll
-            for (int k = 0; k < K; k++) { in[k] = cand_in_box(cd, k, q); any |= in[k]; }
-            if (group_any<G>(any)) {   // most sweeps touch no segment at all
-                double vel_sq = sq(dx) + sq(dy);
-                double shortest = 1;
-#pragma unroll
-                for (int k = 0; k < K; k++)
-                    if (in[k]) {
-                        double t = cand_toi(cd.s[k], cd.x1[k], cd.y1[k], cd.x2[k], cd.y2[k], xold, yold, dx, dy, vel_sq, radius);
-                        if (t < shortest) shortest = t;
-                    }
-                time = group_min<G>(shortest);
-            }
-        } else {
-            time = sweep_generic<G>(TileRefs{lv.seg_start, lv.segs, lv.bounds}, r, xold, yold, dx, dy, radius);
-        }
-    }
+    const double time = tile_sweep<G, K>(lv, r, cd, xold, yold, dx, dy, NINJA_RADIUS * 0.5);
     n.x = xold + time * dx;
     n.y = yold + time * dy;
     // the segment list is gathered ONCE at the post-sweep position (ninja.py:282-285): the cell filter keeps using
@@ -1107,56 +591,6 @@ DEV void logical_collisions(const Lv &lv, Nj &n, EntBits eb) {
     if (pend1 >= 0) ent_set(eb, pend1, 1);
 }
 
-// sum the wall-probe terms of one pass in lane (= query) order (ninja.py:441)
-template <int G> DEV void ordered_add(double &acc, double term) {
-    if constexpr (G == 1) {
-        acc += term;
-    } else {
-        const int glane0 = (threadIdx.x & 63) & ~(G - 1);
-        unsigned long long bal = __ballot(term != 0) >> glane0;
-        if constexpr (G < 64) bal &= (1ull << G) - 1;
-        while (bal) {
-            int k = __builtin_ctzll(bal);
-            bal &= bal - 1;
-            acc += __shfl(term, glane0 + k, 64);
-        }
-    }
-}
-
-DEV double wall_term(double px, double py, double a, double b, double rad) {
-    double dx = px - a, dy = py - b;
-    if (dabs(dy) < 0.00001) {
-        double dist = dsqrt(sq(dx) + sq(dy));
-        if (0 < dist && dist <= rad) return dx / dist;
-    }
-    return 0;
-}
-
-template <int G>
-__device__ __noinline__ double wall_probe_generic(TileRefs lv, int r, double px, double py, double qx0, double qy0,
-                                                  double qx1, double qy1, double wall_normal) {
-    const double rad = NINJA_RADIUS + 0.1;
-    const int c0x = cell_coord(qx0, 43), c1x = cell_coord(qx1, 43), c0y = cell_coord(qy0, 24), c1y = cell_coord(qy1, 24);
-    for (int xc = c0x; xc <= c1x; xc++) {
-        int i0 = lv.seg_start[xc * 25 + c0y], i1 = lv.seg_start[xc * 25 + c1y + 1];
-        for (int ib = i0; ib < i1; ib += G) {   // group-uniform trip count
-            int i = ib + r;
-            double term = 0;
-            if (i < i1) {
-                uint32_t s = lv.segs[i];
-                int yc = s >> 11;
-                if (cell_passes(lv.bounds[xc * 25 + yc], xc, yc, qx0, qy0, qx1, qy1)) {
-                    double a, b;
-                    seg_closest(s, xc, yc, px, py, a, b);
-                    term = wall_term(px, py, a, b, rad);
-                }
-            }
-            ordered_add<G>(wall_normal, term);
-        }
-    }
-    return wall_normal;
-}
-
 #include "npp_zoo.hpp"
 
 // Ninja.post_collision (ninja.py:381-537)
@@ -1176,8 +610,7 @@ DEV void post_collision(const Lv &lv, const Zoo &z, int r, Nj &n, const Cand<K> 
             double term = 0;
             if (cand_in_box(cd, k, q)) {
                 double a, b;
-                if ((cd.s[k] & 1u) == 0) cand_closest_lin(cd, k, n.x, n.y, a, b);
-                else cand_closest_arc(cd.s[k], cd.x1[k], cd.y1[k], cd.x2[k], cd.y2[k], n.x, n.y, a, b);
+                cand_closest(cd, k, n.x, n.y, a, b);
                 term = wall_term(n.x, n.y, a, b, rad);
             }
             if (group_any<G>(term != 0)) ordered_add<G>(wall_normal, term);

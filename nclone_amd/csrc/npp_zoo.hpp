@@ -1,5 +1,5 @@
 // npp_zoo.hpp -- the "entity zoo" of SURVEY.md 8(f) row 2, device side.  Included by npp_kernels.hip (it uses that
-// file's Nj / Lv / EntBits, the lane-group butterflies and the tile primitives) and only instantiated by the ZOO step
+// file's Nj / Lv / EntBits and the tile queries of npp_tilequery.hpp) and only instantiated by the ZOO step
 // kernel, which runs when some environment plays a level holding any of:
 //   regular / trap doors (entity_door_regular.py, entity_door_trap.py), launch pads (entity_launch_pad.py), one-way
 //   platforms (entity_one_way_platform.py), zap / mini drones (entity_drone_base.py), bounce blocks
@@ -394,60 +394,6 @@ DEV bool shove_think(const Zoo &z, int m, int &newcell) {
         return newcell != (int)(w0 & 0x7ffu);
     }
     return false;
-}
-
-// get_single_closest_point with its own region query (physics.py:131-180, segments=None), group-cooperative
-template <int G>
-__device__ __noinline__ Best closest_generic(TileRefs lv, int r, double px, double py, double radius) {
-    const double qx0 = px - radius, qy0 = py - radius, qx1 = px + radius, qy1 = py + radius;
-    const int c0x = cell_coord(qx0, 43), c1x = cell_coord(qx1, 43), c0y = cell_coord(qy0, 24), c1y = cell_coord(qy1, 24);
-    Best m;
-    m.key = __builtin_inf(); m.idx = 0x7fffffff; m.a = 0; m.b = 0;
-    int base = 0;
-    for (int xc = c0x; xc <= c1x; xc++) {
-        const int i0 = lv.seg_start[xc * 25 + c0y], i1 = lv.seg_start[xc * 25 + c1y + 1];
-        for (int i = i0 + r; i < i1; i += G) {
-            const uint32_t s = lv.segs[i];
-            const int yc = s >> 11;
-            if (!cell_passes(lv.bounds[xc * 25 + yc], xc, yc, qx0, qy0, qx1, qy1)) continue;
-            double bx0, by0, bx1, by1;
-            seg_aabb(s, xc, yc, bx0, by0, bx1, by1);
-            if (bx1 < qx0 || bx0 > qx1 || by1 < qy0 || by0 > qy1) continue;
-            double a, b;
-            const bool back = seg_closest(s, xc, yc, px, py, a, b);
-            double distance_sq = sq(px - a) + sq(py - b);
-            if (!back) distance_sq -= 0.1;
-            if (distance_sq < m.key) { m.key = distance_sq; m.a = a; m.b = b; m.idx = ((base + i - i0) << 8) | (r << 1) | (back ? 1 : 0); }
-        }
-        base += i1 - i0;
-    }
-    group_argmin<G>(m);
-    return m;
-}
-
-// get_single_closest_point (physics.py:131-180) answered from candidate registers: the query's own region (cell filter with
-// the inclusive cell-bounds test) and per-segment AABB both use the box q = position +- radius; first-wins argmin in the
-// reference's iteration order (the gather order).  Same per-candidate arithmetic as the ninja's depenetration loop.
-template <int G, int K>
-DEV Best cand_closest_query(const Cand<K> &cd, int r, double px, double py, const QBox &q) {
-    Best m;
-    m.key = __builtin_inf(); m.idx = 0x7fffffff; m.a = 0; m.b = 0;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        if (!cand_in_box(cd, k, q)) continue;
-        const double bx0 = __builtin_fmin(cd.x1[k], cd.x2[k]), bx1 = __builtin_fmax(cd.x1[k], cd.x2[k]);
-        const double by0 = __builtin_fmin(cd.y1[k], cd.y2[k]), by1 = __builtin_fmax(cd.y1[k], cd.y2[k]);
-        if ((bx1 < q.x0) | (bx0 > q.x1) | (by1 < q.y0) | (by0 > q.y1)) continue;
-        double a, b;
-        bool back;
-        if ((cd.s[k] & 1u) == 0) back = cand_closest_lin(cd, k, px, py, a, b);
-        else back = cand_closest_arc(cd.s[k], cd.x1[k], cd.y1[k], cd.x2[k], cd.y2[k], px, py, a, b);
-        const double distance_sq = sq(px - a) + sq(py - b);
-        const double key = back ? distance_sq : distance_sq - 0.1;
-        if (key < m.key) { m.key = key; m.a = a; m.b = b; m.idx = ((k * G + r) << 8) | (r << 1) | (back ? 1 : 0); }
-    }
-    group_argmin<G>(m);
-    return m;
 }
 
 // entity_death_ball.py:74-167 for ball slot m; all lanes of the group cooperate on the tile queries.  Returns true when

@@ -9,6 +9,9 @@ Levels (curriculum-0 set, chosen with the oracle on the CPU):
     depenetrations next to a circular tile on about 5 000 of the 19 200 env-ticks;
   * CREASE = 29: the V crease under the spawn, 452 applied depenetrations per 4-tick step at rest (oracle).
 No env terminates under these inputs (asserted from the oracle's run), so every tick of every env is compared.
+
+test_table_forms drives the other form of the tile queries, the walk over the level's segment table, with launch
+geometries whose candidate registers cannot hold what ARCS and STRAIGHT put around the ninja.
 """
 import functools
 
@@ -74,16 +77,17 @@ def _oracle_run(om, level, env):
 _DEVICE = {}
 
 
-def _device_run(level_of_env, variant):
-    """Device trajectory, one workgroup: 16 envs, 16 lanes per env, 4 wavefronts; dump after every tick.  Cached."""
-    key = (tuple(level_of_env), variant)
+def _device_run(level_of_env, variant, geometry=(16, 4)):
+    """Device trajectory of the 16 envs at `geometry` = (lanes per env, wavefronts per workgroup); the default is one
+    workgroup of 4 wavefronts with 16 lanes per env.  Dump after every tick.  Cached."""
+    key = (tuple(level_of_env), variant, tuple(geometry))
     if key not in _DEVICE:
         from nclone_amd.engine import NppBatch
 
         ids = sorted(set(level_of_env))
         b = NppBatch(N, autoreset=False)
         b.load_levels([_levels()[i] for i in ids])
-        b.set_launch_geometry(16, 4)
+        b.set_launch_geometry(*geometry)
         b.set_step_variant(variant)
         b.assign_levels(np.array([ids.index(i) for i in level_of_env], dtype=np.int64))
         d_inputs = torch.from_numpy(np.array(_inputs())).cuda()
@@ -156,6 +160,48 @@ def test_both_kinds_in_one_wavefront(variant, oracle_mod):
         rF, rD = (Fs, Ds) if e % 2 == 0 else (Fa, Da)
         assert np.array_equal(F[:, e].view(np.int64), rF[:, e].view(np.int64)), e
         assert np.array_equal(D[:, e], rD[:, e]), e
+
+
+def _over_capacity(om, level, capacity):
+    """(env-ticks of the oracle's run on `level` whose gather region holds more than `capacity` segments, those of them
+    with an applied depenetration).  The region: the cells of the box from the previous to the current position, padded
+    by 12.2 px (tick 0 has no previous position in the run and uses its own, a smaller box); segments per cell from the
+    level compiler.  Such a tick cannot keep its candidates in registers, so every
+    tile query of it walks the table.  (The box ends at the post-collision position where the kernel's ends at the
+    pre-collision one; the thresholds below leave a factor of two for cells that flip at a boundary.)"""
+    from nclone_amd.engine import compile_level_segments
+
+    rows, _ = compile_level_segments(np.asarray(_levels()[level], dtype=np.float64))
+    per_cell = np.zeros((44, 25), dtype=np.int64)
+    np.add.at(per_cell, (rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64)), 1)
+    over = applied = 0
+    for e in range(N):
+        oF, oD = _oracle_run(om, level, e)
+        x, y = oF[:, 0], oF[:, 1]
+        px, py = np.concatenate([x[:1], x[:-1]]), np.concatenate([y[:1], y[:-1]])
+        c0x = np.clip(np.floor((np.minimum(x, px) - 12.2) / 24), 0, 43).astype(np.int64)
+        c1x = np.clip(np.floor((np.maximum(x, px) + 12.2) / 24), 0, 43).astype(np.int64)
+        c0y = np.clip(np.floor((np.minimum(y, py) - 12.2) / 24), 0, 24).astype(np.int64)
+        c1y = np.clip(np.floor((np.maximum(y, py) + 12.2) / 24), 0, 24).astype(np.int64)
+        for k in range(TICKS):
+            if per_cell[c0x[k]:c1x[k] + 1, c0y[k]:c1y[k] + 1].sum() > capacity:
+                over += 1
+                applied += bool(oD[k, 8] + oD[k, 9] > 0)
+    return over, applied
+
+
+@pytest.mark.parametrize("level,lanes,least", [(ARCS, 1, 1000), (ARCS, 2, 1000), (STRAIGHT, 1, 300)])
+def test_table_forms(level, lanes, least, oracle_mod):
+    """1 and 2 lanes per env keep 4 candidate registers per lane (KSlots), 4 and 8 per env: most ticks on ARCS and many on
+    STRAIGHT gather more segments than that, and the sweep, the depenetration loop and the wall probe of such a tick all
+    take the table form.  Oracle, out of 19 200 env-ticks: ARCS 19 090 over 4 (5 572 with an applied depenetration) and
+    10 618 over 8 (2 458); STRAIGHT 1 335 over 4 (582)."""
+    over, applied = _over_capacity(oracle_mod, level, lanes * 4)
+    print("level %d, %d lanes: %d env-ticks over capacity, %d with an applied depenetration" % (level, lanes, over, applied))
+    assert applied >= least, (over, applied)
+    lv = [level] * N
+    F, D = _device_run(lv, 0, (lanes, 1))
+    _assert_matches_oracle(oracle_mod, lv, F, D)
 
 
 def test_crease_every_variant(oracle_mod):

@@ -184,12 +184,12 @@ def test_host_helpers():
 
 
 def test_aabb_threshold_table_is_exact():
-    """AABB_LO (npp_kernels.hip): entry i is the smallest double x with fl(x + 10) >= 12 i, and 12 i + 10 is the largest with
+    """AABB_LO (npp_tilequery.hpp): entry i is the smallest double x with fl(x + 10) >= 12 i, and 12 i + 10 is the largest with
     fl(x - 10) <= 12 i -- the thresholds that replace the rounded box of get_single_closest_point's AABB test (physics.py:150-167).
     Checked on 64 doubles either side of every threshold."""
     import re
 
-    src = open(os.path.join(ROOT, "nclone_amd", "csrc", "npp_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "nclone_amd", "csrc", "npp_tilequery.hpp")).read()
     body = src[src.index("__constant__ double AABB_LO[89] = {"):]
     body = body[:body.index("};")]
     vals = [float.fromhex(m) for m in re.findall(r"(-?0x1\.[0-9a-f]+p[+-]\d+)", body)]
