@@ -289,6 +289,11 @@ int npp_render_global_view(npp_handle h, uint8_t *d_out);
  *                            applied_gravity applied_drag
  * i32 [count][NPP_DUMP_I32]: see DESIGN.md ("state dump layout"). */
 int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *i32_out);
+/* Parity hook, a TEST AID: overwrites xpos, ypos, xspeed, yspeed of envs [env0, env0+count) from the HOST buffer
+ * xyv f64 [count][4] and nothing else (every other plane and word of the env's state keeps its value).  Joins an open observation
+ * overlap and synchronises, as the dump does.  NPP_ERR_INVALID for a non-finite value: then no env is touched.  After it an env's
+ * action route and its archive meta rows no longer describe its state (tests/inject_states.py, DESIGN.md "injected states"). */
+int npp_set_ninja_state(npp_handle h, int env0, int count, const double *xyv /* [count][4] x y vx vy */);
 /* Host-only: npp_dump_state's own decode of one env's five packed state words (planes A..E, DESIGN.md "packed state layout") into
  * its i32 row.  Columns 13 and 27 are not in the words: 2 (no exit switch) and level 0. */
 int npp_state_decode_host(const uint32_t words[5], int32_t *out /* NPP_DUMP_I32 */);

@@ -2277,6 +2277,23 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
     return NPP_OK;
 }
 
+int npp_set_ninja_state(npp_handle h, int env0, int count, const double *xyv) {
+    if (!h || !xyv || env0 < 0 || count <= 0 || env0 + count > h->n) return fail(h, NPP_ERR_INVALID, "npp_set_ninja_state: bad arguments");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_ninja_state: no levels loaded");
+    for (size_t i = 0; i < (size_t)count * 4; i++)
+        if (!std::isfinite(xyv[i])) return fail(h, NPP_ERR_INVALID, "npp_set_ninja_state: non-finite value");
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n;
+    const int plane[4] = {F_X, F_Y, F_VX, F_VY};
+    std::vector<double> col((size_t)count);
+    for (int k = 0; k < 4; k++) {
+        for (int i = 0; i < count; i++) col[i] = xyv[(size_t)i * 4 + k];
+        HIP_TRY(h, hipMemcpy(h->env.f64.get() + plane[k] * N + env0, col.data(), sizeof(double) * count, hipMemcpyHostToDevice));
+    }
+    return NPP_OK;
+}
+
 int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out) {
     if (!h || env < 0 || env >= h->n || !out || !n_out) return fail(h, NPP_ERR_INVALID, "npp_dump_entities: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_entities: no levels loaded");

@@ -883,6 +883,18 @@ class NppBatch:
             self.h, env0, count, f.ctypes.data_as(C.POINTER(C.c_double)), i.ctypes.data_as(C.POINTER(C.c_int32))))
         return f, i
 
+    def set_ninja_state(self, xyv, env0=0):
+        """Test aid: overwrite xpos, ypos, xspeed, yspeed of envs [env0, env0 + len(xyv)) with the rows of xyv (f64 [count, 4])
+        and nothing else; synchronises like dump_state().  Non-finite values raise ValueError and leave every env untouched.
+        Afterwards an env's action route and archive meta rows no longer describe its state."""
+        a = np.ascontiguousarray(xyv, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("set_ninja_state: xyv must be [count, 4] (x, y, vx, vy)")
+        code = self.lib.npp_set_ninja_state(self.h, int(env0), len(a), a.ctypes.data_as(C.POINTER(C.c_double)))
+        if code == nat.NPP_ERR_INVALID:
+            raise ValueError(self.lib.npp_last_error(self.h).decode())
+        nat.check(self.h, code)
+
     def dump_entities(self, env):
         buf = np.zeros(4096, dtype=np.int32)
         n = C.c_int(0)

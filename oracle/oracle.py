@@ -66,6 +66,8 @@ def _lib(variant):
     lib.osim_entity_states.argtypes = [P, C.POINTER(C.c_int), C.c_int]
     lib.osim_entity_states.restype = C.c_int
     lib.osim_set_entity_pos.argtypes = [P, C.c_int, C.c_double, C.c_double]
+    lib.osim_set_ninja.argtypes = [P, C.c_double, C.c_double, C.c_double, C.c_double]
+    lib.osim_set_ninja.restype = None
     lib.osim_dump_draw.argtypes = [P, C.POINTER(C.c_double), C.c_int]
     lib.osim_dump_draw.restype = C.c_int
     lib.osim_dump_edges.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -160,6 +162,10 @@ class Oracle:
     def set_entity_pos(self, kind, x, y):
         """Curriculum repositioning of the exit switch (0) / exit door (1); survives resets."""
         self.lib.osim_set_entity_pos(self.h, int(kind), float(x), float(y))
+
+    def set_ninja(self, x, y, vx, vy):
+        """Test aid: overwrite the ninja's xpos, ypos, xspeed, yspeed (tests/inject_states.py); nothing else changes."""
+        self.lib.osim_set_ninja(self.h, float(x), float(y), float(vx), float(vy))
 
     def draw_list(self):
         """[n, 13] rows of what the entity layer would draw, entity_dic order (see osim_dump_draw)."""

@@ -31,6 +31,17 @@ def test_header_symbols_exported(native):
     assert sorted(native.EXPORTS) == declared
 
 
+def test_set_ninja_state_abi(native):
+    """The injection hook is declared, exported, listed and bound, and refuses a null handle without touching anything."""
+    hdr = open(os.path.join(ROOT, "include", "npp_amd.h")).read()
+    assert re.search(r"int npp_set_ninja_state\(npp_handle h, int env0, int count, const double \*xyv", hdr)
+    assert "npp_set_ninja_state" in native.EXPORTS
+    lib = native.lib()
+    assert lib.npp_set_ninja_state.argtypes == [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    xyv = (C.c_double * 4)(100.0, 100.0, 0.0, 0.0)
+    assert lib.npp_set_ninja_state(None, 0, 1, xyv) == native.NPP_ERR_INVALID
+
+
 def test_header_is_plain_c(tmp_path):
     """The boundary is a C ABI: include/npp_amd.h must compile as C99 (no C++-isms, no torch / HIP types)."""
     import subprocess
