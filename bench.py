@@ -25,7 +25,14 @@ does not depend on the caller's warm-up.  Every launch of the timed region
 is bracketed by HIP events on the launch stream: mean / p50 / p95 / max are reported, together with the levels that own
 the slowest 5 % of the launches (the env with the most depenetration iterations in that launch, npp_step_out.d_work).
 
-Without --workload the line carries every BASELINE config that fits the run (round 3):
+A plain run (no --full) does what the headline figure needs and nothing else: set-up, pre-roll, warm-up, the K timed steps of
+the workload, --dump-outputs if given, and the line -- `value`, `ms_per_step`, the per-launch times, stragglers and roofline of
+those same K steps.  Everything that takes runs of its own sits behind --full (off by default): the other BASELINE configs
+(`other_configs`, `config4`), `cpu_baseline`, `async_subbatches` and `open_loop_rollout`; --other-steps, --no-cpu-baseline,
+--async-streams and --open-loop-chunk trim a --full run and mean nothing without it.  The observation kernels, overlap passes and
+gather of --player-frame, --full-obs and --gather-obs are asked for by name and run with or without --full.
+
+With --full and without --workload the line carries every BASELINE config that fits the run (round 3):
   N = 1:  value = config 2 (c0) and `other_configs` = {config3 (mines + player_frame every step), config4_shard (c3mixed, one GPU's
           8192 of the 65 536 envs), config5_full_obs (doors, every Dict observation every step)}, --other-steps (200) timed steps
           each after their own pre-roll, each with its own roofline block(s); config5_full_obs is timed twice -- every kernel on one
@@ -33,7 +40,7 @@ Without --workload the line carries every BASELINE config that fits the run (rou
           include/npp_amd.h npp_set_obs_overlap (`obs_overlap`, --obs-overlap: same work, same bits) -- `value` is the better one;
   N > 1:  value = config 2 on N GPUs (so that N = 1 agrees with the line above) and `config4` = c3mixed on the N GPUs with and
           without the RCCL all_gather of the packed observation block.
-With --workload X the line is that workload alone, as before.
+With --workload X the line is that workload alone, as before (with --full: plus its secondary figures and the CPU baseline).
 
 Weak scaling: each rank (one process per GPU) steps its own envs; there is no data-path collective unless --gather-obs.
 Prints ONE JSON line on rank 0.
@@ -173,12 +180,16 @@ def parse_args(argv=None):
                     help="also time the steps with the RCCL all_gather of the packed observation block (config 4)")
     ap.add_argument("--player-frame", action="store_true",
                     help="render the 84x84 player_frame of every env each step inside the timed region (config 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure that takes runs of its own: the other BASELINE configs "
+                         "(other_configs / config4), cpu_baseline, async_subbatches and open_loop_rollout (module docstring).  Off by "
+                         "default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU oracle's cpu_baseline out")
     ap.add_argument("--async-streams", type=int, default=4,
-                    help="also time the same K steps with the envs split into this many independent sub-batches on "
+                    help="--full: also time the same K steps with the envs split into this many independent sub-batches on "
                          "separate HIP streams (reported as async_subbatches, never as value); 0 = skip")
     ap.add_argument("--open-loop-chunk", type=int, default=50,
-                    help="also time the K steps as npp_step_many launches of this many steps (open_loop_rollout; 0 = skip)")
+                    help="--full: also time the K steps as npp_step_many launches of this many steps (open_loop_rollout; 0 = skip)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsing the "
                                                       "multi-rank path on one GPU together with --device)")
     ap.add_argument("--device", type=int, default=None, help="GPU index for every rank (rehearsal on a one-GPU box)")
@@ -187,10 +198,10 @@ def parse_args(argv=None):
                          "switch_states, player_frame, global_view, reachability_features + mine_sdf_features; per-kernel times "
                          "are reported under obs_kernels")
     ap.add_argument("--workload", default=None, choices=["c0", "mines", "doors", "zoo", "c3mixed"],
-                    help="time this workload alone (c0 = config 2, the headline metric); default: c0 as `value` plus the other "
-                         "BASELINE configs in their own blocks, see the module docstring")
+                    help="time this workload alone (c0 = config 2, the headline metric); default: c0 as `value`, and with --full the "
+                         "other BASELINE configs in their own blocks, see the module docstring")
     ap.add_argument("--other-steps", type=int, default=200,
-                    help="timed steps of each block of `other_configs` / `config4` (0 = leave them out)")
+                    help="--full: timed steps of each block of `other_configs` / `config4` (0 = leave them out)")
     ap.add_argument("--step-variant", type=int, default=-1, choices=[-1, 0, 1, 2],
                     help="pin a build variant of the step kernel (A/B runs); -1 = the autotuner decides (default)")
     ap.add_argument("--obs-overlap", type=str, default="50",
@@ -645,10 +656,10 @@ def main():
     K, W, P = args.steps, args.warmup, args.preroll
     single = args.workload is not None
     head = run_workload(ctx, args.workload or "c0", K, W, P, player_frame=args.player_frame, full_obs=args.full_obs,
-                        gather_obs=args.gather_obs, secondaries=True, dump_dir=args.dump_outputs)
+                        gather_obs=args.gather_obs, secondaries=args.full, dump_dir=args.dump_outputs)
     others = {}
     Ko = args.other_steps
-    if not single and Ko > 0 and not (args.player_frame or args.full_obs or args.gather_obs):
+    if args.full and not single and Ko > 0 and not (args.player_frame or args.full_obs or args.gather_obs):
         Wo = min(W, 50)
         if world == 1:
             # BASELINE configs 3, 4 (one GPU's shard) and 5 in the driver's default run
@@ -678,6 +689,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": bool(args.full),
         }
         for k, v in head.items():
             if k not in line:
@@ -690,7 +702,7 @@ def main():
                 line["other_configs"] = others
             else:
                 line["config4"] = others["config4"]
-        if not args.no_cpu_baseline and world == 1:   # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported at N = 1 only
             try:
                 line["cpu_baseline"] = cpu_baseline(levels)
             except Exception as e:  # the baseline is a reported figure, never a dependency of the GPU number

@@ -56,6 +56,13 @@ def test_write_outputs_samples_the_same_rows_within_budget(tmp_path):
     assert reps[0]["envs_kept"] == len(rows) and reps[0]["bytes"] <= budget
 
 
+def test_full_is_an_option_and_off_by_default():
+    bench = _bench()
+    plain = bench.parse_args(["--gpus", "1", "--steps", "10", "--warmup", "2"])
+    assert plain.full is False and plain.steps == 10 and plain.warmup == 2
+    assert bench.parse_args(["--gpus", "1", "--steps", "10", "--warmup", "2", "--full"]).full is True
+
+
 def _run(args, out_dir):
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)

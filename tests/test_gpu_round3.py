@@ -165,13 +165,45 @@ def test_config5_full_dict_step_on_the_whole_door_set(oracle_mod):
     b.close()
 
 
-def test_bench_default_line_carries_the_other_configs():
-    """`python bench.py` (N = 1, no --workload): value = config 2 and other_configs = configs 3, 4-shard and 5 with their own
-    rooflines (VERDICT r2 #4); config 5 runs on its whole level set."""
+def test_bench_plain_line_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline figure of the K timed steps and what is read
+    off those same steps -- none of the measurements that take runs of their own, although nothing switches them off here."""
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--preroll", "40", "--envs-per-gpu",
-                        "1024", "--other-steps", "12", "--no-cpu-baseline", "--async-streams", "0", "--open-loop-chunk", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "5", "--preroll", "40",
+                        "--envs-per-gpu", "1024"], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "env-steps/sec (whole node) at N parallel envs" and line["unit"] == "env-steps/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["full"] is False
+    assert line["n_gpus"] == 1 and line["steps"] == 60 and line["warmup"] == 5 and "config 2" in line["config"]["workload"]
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 1024) < 1e-6 * 1024
+    assert line["roofline"]["frac"] > 0 and line["launch_us"]["p95"] >= line["launch_us"]["p50"] and line["stragglers"]["launches"] == 3
+    assert not {"other_configs", "config4", "cpu_baseline", "async_subbatches", "open_loop_rollout"} & set(line)
+
+
+def test_bench_full_line_carries_the_secondary_figures():
+    """--full on one workload: the sub-batch and open-loop figures of the same steps sit beside `value` (the CPU oracle's leg, which
+    runs for 12 s, is switched off here)."""
+    env = dict(os.environ)
+    env.pop("RANK", None); env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "c0", "--steps", "60", "--warmup", "5",
+                        "--preroll", "40", "--envs-per-gpu", "1024", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["full"] is True and line["steps"] == 60 and line["value"] > 0 and "other_configs" not in line
+    assert line["async_subbatches"]["streams"] == 4 and line["async_subbatches"]["value"] > 0
+    assert line["open_loop_rollout"]["steps"] == 50 and line["open_loop_rollout"]["value"] > 0
+    assert "cpu_baseline" not in line
+
+
+def test_bench_default_line_carries_the_other_configs():
+    """`python bench.py --full` (N = 1, no --workload): value = config 2 and other_configs = configs 3, 4-shard and 5 with their
+    own rooflines (VERDICT r2 #4); config 5 runs on its whole level set."""
+    env = dict(os.environ)
+    env.pop("RANK", None); env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--preroll", "40",
+                        "--envs-per-gpu", "1024", "--other-steps", "12", "--no-cpu-baseline", "--async-streams", "0", "--open-loop-chunk", "0"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -189,12 +221,12 @@ def test_bench_default_line_carries_the_other_configs():
 
 
 def test_bench_two_ranks_default_line_reports_config4():
-    """`python bench.py --gpus 2` without --workload (what a SCALE run launches): value = config 2 on both ranks and a `config4`
-    block = the mixed set with and without the observation gather.  Rehearsed on one GPU over gloo."""
+    """`python bench.py --gpus 2 --full` without --workload (what a SCALE run launches): value = config 2 on both ranks and a
+    `config4` block = the mixed set with and without the observation gather.  Rehearsed on one GPU over gloo."""
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0", "--steps", "20",
-                        "--warmup", "5", "--preroll", "10", "--envs-per-gpu", "1024", "--other-steps", "10", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--device", "0", "--steps",
+                        "20", "--warmup", "5", "--preroll", "10", "--envs-per-gpu", "1024", "--other-steps", "10", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
