@@ -294,12 +294,25 @@ int npp_dump_state(npp_handle h, int env0, int count, double *f64_out, int32_t *
  * overlap and synchronises, as the dump does.  NPP_ERR_INVALID for a non-finite value: then no env is touched.  After it an env's
  * action route and its archive meta rows no longer describe its state (tests/inject_states.py, DESIGN.md "injected states"). */
 int npp_set_ninja_state(npp_handle h, int env0, int count, const double *xyv /* [count][4] x y vx vy */);
+/* Parity hook, a TEST AID: for envs [env0, env0+count) and mover slot `slot` (the level's movers -- drones, bounce blocks, thwumps,
+ * death balls, shove thwumps -- in entity_dic order) overwrites the record's four doubles from the HOST buffer xyab f64 [count][4]:
+ * x, y and the speed of a bounce block / death ball or the target of a drone (thwumps and shove thwumps have neither: 0, 0).
+ * field (i32 [count], or NULL to leave it alone) is the reference's own value of the 2-bit field: a thwump's state -1 / 0 / 1, a
+ * drone's dir 0..3.  The record's cell and list-order number keep their values, like Entity.cell and the grid lists after an
+ * attribute assignment in the reference: the next grid_move updates them.  NPP_ERR_INVALID for a non-finite value, a slot past
+ * the movers of an env's level, a field the mover's kind does not have, or a non-zero third / fourth value for a thwump: then
+ * nothing is written.  Joins and synchronises, as the dump does (tests/inject_zoo_states.py). */
+int npp_set_mover_state(npp_handle h, int env0, int count, int slot, const double *xyab /* [count][4] */, const int32_t *field);
+/* Parity hook, a TEST AID: one env's movers in slot order as rows of 5 doubles on the HOST: x, y, a, b and the field as above (a shove
+ * thwump's state 0..3; 0 for bounce blocks and death balls).  Returns the count via *n_out. */
+int npp_dump_movers(npp_handle h, int env, double *out /* [max_rows][5] */, int max_rows, int *n_out);
 /* Host-only: npp_dump_state's own decode of one env's five packed state words (planes A..E, DESIGN.md "packed state layout") into
  * its i32 row.  Columns 13 and 27 are not in the words: 2 (no exit switch) and level 0. */
 int npp_state_decode_host(const uint32_t words[5], int32_t *out /* NPP_DUMP_I32 */);
 
-/* Parity hook: per-entity dynamic state of one env in level (map) order:
- * mines -> state 0/1/2, exit door -> switch_hit, others -> active.  Returns count via *n_out. */
+/* Parity hook: per-entity dynamic state of one env in level (map) order, movers left out (npp_dump_movers has them):
+ * mines -> state 0/1/2, exit door -> switch_hit, regular door -> active + 2 * closed, boost pad -> active + 2 * touching,
+ * others -> active.  Returns count via *n_out. */
 int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out);
 
 /* Parity hook: the compiled collision table of a level as rows of 8 int16

@@ -2294,6 +2294,76 @@ int npp_set_ninja_state(npp_handle h, int env0, int count, const double *xyv) {
     return NPP_OK;
 }
 
+// field of a mover record as the reference holds it: drone dir, thwump state -1 / 0 / 1, shove thwump state; 0 for the rest
+static int mover_field(uint32_t kind, uint32_t w0) {
+    const int bits = (int)((w0 >> 11) & 3u);
+    if (kind == MK_DRONE || kind == MK_MINI || kind == MK_SHOVE) return bits;
+    return kind == MK_THWUMP ? bits - 1 : 0;
+}
+
+int npp_set_mover_state(npp_handle h, int env0, int count, int slot, const double *xyab, const int32_t *field) {
+    if (!h || !xyab || env0 < 0 || count <= 0 || env0 + count > h->n || slot < 0) return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: bad arguments");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_mover_state: no levels loaded");
+    for (size_t i = 0; i < (size_t)count * 4; i++)
+        if (!std::isfinite(xyab[i])) return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: non-finite value");
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = pull_levels(h)) return rc;
+    if (!h->ls.zoo) return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: the level set has no movers");
+    for (int i = 0; i < count; i++) {
+        const CompiledLevel &L = h->ls.levels[h->env_level[env0 + i]];
+        if (slot >= (int)L.mov_meta.size()) return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: slot past the level's movers");
+        const uint32_t kind = L.mov_meta[slot] & 7u;
+        if ((kind == MK_THWUMP || kind == MK_SHOVE) && (xyab[(size_t)i * 4 + 2] != 0 || xyab[(size_t)i * 4 + 3] != 0))
+            return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: thwumps have no third and fourth value");
+        if (!field) continue;
+        const bool ok = kind == MK_THWUMP ? (field[i] >= -1 && field[i] <= 1)
+                                          : ((kind == MK_DRONE || kind == MK_MINI) && field[i] >= 0 && field[i] <= 3);
+        if (!ok) return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: the mover's kind has no such state");
+    }
+    const int door_words = (h->ls.zoo_doors + 1) / 2;
+    const size_t off = (size_t)ZOO_HEAD + door_words + (size_t)ZOO_MOV_WORDS * slot;
+    if (off + ZOO_MOV_WORDS > (size_t)h->ls.zoo_words) return fail(h, NPP_ERR_INVALID, "npp_set_mover_state: slot past the zoo block");
+    for (int i = 0; i < count; i++) {
+        double *rec = h->ls.zoo.get() + (size_t)(env0 + i) * h->ls.zoo_words + off;
+        HIP_TRY(h, hipMemcpy(rec, xyab + (size_t)i * 4, sizeof(double) * 4, hipMemcpyHostToDevice));
+        if (!field) continue;
+        uint32_t w0;   // low half of word 4: cell | bits << 11 | static attributes; the high half (list-order number) is not touched
+        HIP_TRY(h, hipMemcpy(&w0, rec + 4, sizeof(w0), hipMemcpyDeviceToHost));
+        const uint32_t kind = h->ls.levels[h->env_level[env0 + i]].mov_meta[slot] & 7u;
+        const uint32_t bits = (uint32_t)(kind == MK_THWUMP ? field[i] + 1 : field[i]);
+        w0 = (w0 & ~(3u << 11)) | (bits << 11);
+        HIP_TRY(h, hipMemcpy(rec + 4, &w0, sizeof(w0), hipMemcpyHostToDevice));
+    }
+    return NPP_OK;
+}
+
+int npp_dump_movers(npp_handle h, int env, double *out, int max_rows, int *n_out) {
+    if (!h || env < 0 || env >= h->n || !out || !n_out || max_rows < 0) return fail(h, NPP_ERR_INVALID, "npp_dump_movers: bad arguments");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_movers: no levels loaded");
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = pull_levels(h)) return rc;
+    const CompiledLevel &L = h->ls.levels[h->env_level[env]];
+    const int n = (int)L.mov_meta.size();
+    if (n > max_rows) return fail(h, NPP_ERR_INVALID, "npp_dump_movers: buffer too small");
+    *n_out = n;
+    if (!n) return NPP_OK;
+    const int door_words = (h->ls.zoo_doors + 1) / 2;
+    std::vector<double> rec((size_t)ZOO_MOV_WORDS * n);
+    HIP_TRY(h, hipMemcpy(rec.data(), h->ls.zoo.get() + (size_t)env * h->ls.zoo_words + ZOO_HEAD + door_words, sizeof(double) * rec.size(),
+                         hipMemcpyDeviceToHost));
+    for (int m = 0; m < n; m++) {
+        const double *p = rec.data() + (size_t)ZOO_MOV_WORDS * m;
+        uint64_t wd;
+        std::memcpy(&wd, p + 4, 8);
+        double *o = out + (size_t)m * 5;
+        o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3];
+        o[4] = (double)mover_field(L.mov_meta[m] & 7u, (uint32_t)wd);
+    }
+    return NPP_OK;
+}
+
 int npp_dump_entities(npp_handle h, int env, int32_t *out, int max, int *n_out) {
     if (!h || env < 0 || env >= h->n || !out || !n_out) return fail(h, NPP_ERR_INVALID, "npp_dump_entities: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_dump_entities: no levels loaded");

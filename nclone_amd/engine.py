@@ -895,6 +895,32 @@ class NppBatch:
             raise ValueError(self.lib.npp_last_error(self.h).decode())
         nat.check(self.h, code)
 
+    def set_mover_state(self, slot, xyab, field=None, env0=0):
+        """Test aid: overwrite x, y, a, b of mover `slot` (entity_dic order) in envs [env0, env0 + len(xyab)) with the rows of xyab
+        (f64 [count, 4]; a, b: speed of a bounce block / death ball, target of a drone, 0 for the thwumps) and, when `field` (int
+        [count]) is given, its state (thwump -1 / 0 / 1) or dir (drone 0..3).  Cell and list-order number stay, as Entity.cell does
+        after an attribute assignment in the reference.  Synchronises.  A refusal raises ValueError and writes nothing."""
+        a = np.ascontiguousarray(xyab, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("set_mover_state: xyab must be [count, 4] (x, y, a, b)")
+        fp = None
+        if field is not None:
+            f = np.ascontiguousarray(field, dtype=np.int32).ravel()
+            if len(f) != len(a):
+                raise ValueError("set_mover_state: one field value per row")
+            fp = f.ctypes.data_as(C.POINTER(C.c_int32))
+        code = self.lib.npp_set_mover_state(self.h, int(env0), len(a), int(slot), a.ctypes.data_as(C.POINTER(C.c_double)), fp)
+        if code == nat.NPP_ERR_INVALID:
+            raise ValueError(self.lib.npp_last_error(self.h).decode())
+        nat.check(self.h, code)
+
+    def dump_movers(self, env):
+        """[n, 5] f64 rows x, y, a, b, state / dir of one env's movers in entity_dic order (see npp_dump_movers)."""
+        buf = np.zeros((1024, 5), dtype=np.float64)
+        n = C.c_int(0)
+        nat.check(self.h, self.lib.npp_dump_movers(self.h, int(env), buf.ctypes.data_as(C.POINTER(C.c_double)), len(buf), C.byref(n)))
+        return buf[: n.value].copy()
+
     def dump_entities(self, env):
         buf = np.zeros(4096, dtype=np.int32)
         n = C.c_int(0)

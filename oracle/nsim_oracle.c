@@ -212,6 +212,9 @@ typedef struct OSim {
      * every reset like the reference does after every map load */
     int ovr_set[2];
     double ovr_x[2], ovr_y[2];
+    /* debug counters of ball_think since the last osim_ball_debug(..., clear = 1): applied depenetrations that ran into the
+     * 16-iteration cap, `dist == 0` bails, bounce_strength == 2, new_speed snapped to 0 (tests/test_inject_zoo_host.py census) */
+    int ball_dbg[4];
     Entity *cached[256];      /* ninja._cached_entities (ninja.py:220-222) */
     int ncached;
     /* mine-overlay cache of gym_environment/spatial_context.py:103-110,309-367 (per env = per process there) */
@@ -638,6 +641,65 @@ void osim_set_entity_pos(OSim *S, int kind, double x, double y)
 void osim_set_ninja(OSim *S, double x, double y, double vx, double vy)
 {
     S->nj.xpos = x; S->nj.ypos = y; S->nj.xspeed = vx; S->nj.yspeed = vy;
+}
+
+/* Test aids (tests/inject_zoo_states.py): one mover's four doubles and its state / direction, the counterpart of assigning
+ * xpos, ypos and xspeed, yspeed (bounce block, death ball) or xtarget, ytarget (drones), and state (thwump: -1, 0, 1) or dir
+ * (drones: 0..3), on sim.entity_dic[...][...] between two ticks.  Entity.cell and the grid lists stay as they are until the
+ * entity's next grid_move, like in the reference.  `slot` counts the movers (drones, bounce blocks, thwumps, death balls,
+ * shove thwumps) in entity_dic order; field == OSIM_KEEP_FIELD leaves state / dir alone.  Thwumps and shove thwumps have no
+ * third and fourth attribute: a and b must be 0 for them.  Returns 0, or -1 with nothing written. */
+#define OSIM_KEEP_FIELD (-2)
+static int is_mover(const Entity *e)
+{
+    return e->kind == K_DRONE || e->kind == K_BOUNCE || e->kind == K_THWUMP || e->kind == K_BALL || e->kind == K_SHOVE;
+}
+static Entity *mover_slot(const OSim *S, int slot)
+{
+    if (slot < 0) return NULL;
+    for (int i = 0; i < S->ndic; i++)
+        if (is_mover(S->dic_order[i]) && slot-- == 0) return S->dic_order[i];
+    return NULL;
+}
+int osim_set_mover(OSim *S, int slot, double x, double y, double a, double b, int field)
+{
+    Entity *e = mover_slot(S, slot);
+    if (!e || !isfinite(x) || !isfinite(y) || !isfinite(a) || !isfinite(b)) return -1;
+    if (field != OSIM_KEEP_FIELD) {
+        if (e->kind == K_THWUMP) { if (field < -1 || field > 1) return -1; }
+        else if (e->kind == K_DRONE) { if (field < 0 || field > 3) return -1; }
+        else return -1;
+    }
+    if ((e->kind == K_THWUMP || e->kind == K_SHOVE) && (a != 0 || b != 0)) return -1;
+    e->x = x; e->y = y;
+    if (e->kind == K_DRONE) { e->xtarget = a; e->ytarget = b; }
+    else if (e->kind == K_BOUNCE || e->kind == K_BALL) { e->xspeed = a; e->yspeed = b; }
+    if (field != OSIM_KEEP_FIELD) { if (e->kind == K_THWUMP) e->state = field; else e->dir = field; }
+    return 0;
+}
+/* rows of 5 doubles per mover in slot order: x, y, a, b (0 where the kind has none), state / dir (shove thwump: state; 0 for
+ * bounce blocks and death balls).  Returns the number of movers, -1 when `max_rows` is too small. */
+int osim_dump_movers(const OSim *S, double *out, int max_rows)
+{
+    int r = 0;
+    for (int i = 0; i < S->ndic; i++) {
+        const Entity *e = S->dic_order[i];
+        if (!is_mover(e)) continue;
+        if (r >= max_rows) return -1;
+        double *o = out + 5 * r++;
+        o[0] = e->x; o[1] = e->y; o[2] = 0; o[3] = 0; o[4] = 0;
+        if (e->kind == K_DRONE) { o[2] = e->xtarget; o[3] = e->ytarget; o[4] = e->dir; }
+        else if (e->kind == K_BOUNCE || e->kind == K_BALL) { o[2] = e->xspeed; o[3] = e->yspeed; }
+        else o[4] = e->state;
+    }
+    return r;
+}
+
+/* debug counters of ball_think (see OSim.ball_dbg): out[4]; clear != 0 zeroes them afterwards */
+void osim_ball_debug(OSim *S, int *out, int clear)
+{
+    memcpy(out, S->ball_dbg, sizeof S->ball_dbg);
+    if (clear) memset(S->ball_dbg, 0, sizeof S->ball_dbg);
 }
 
 void osim_reset(OSim *S)
@@ -1266,7 +1328,7 @@ static void ball_think(OSim *S, Entity *e)
         double speed = sqrt(SQ(e->xspeed) + SQ(e->yspeed));
         if (speed > 0.85) {
             double new_speed = (speed - 0.85) * 0.9;
-            if (new_speed <= 0.01) new_speed = 0;
+            if (new_speed <= 0.01) { new_speed = 0; S->ball_dbg[3]++; }
             new_speed += 0.85;
             e->xspeed = e->xspeed / speed * new_speed;
             e->yspeed = e->yspeed / speed * new_speed;
@@ -1279,7 +1341,8 @@ static void ball_think(OSim *S, Entity *e)
     e->x = xpos_old + time * e->xspeed;
     e->y = ypos_old + time * e->yspeed;
     double xnormal = 0, ynormal = 0;
-    for (int it = 0; it < 16; it++) {
+    int it;
+    for (it = 0; it < 16; it++) {
         Seg *segs[MAXQ];
         int nseg = query_region(S, e->x - 8, e->y - 8, e->x + 8, e->y + 8, segs);
         double a = 0, b = 0;
@@ -1289,13 +1352,14 @@ static void ball_think(OSim *S, Entity *e)
         double dist = sqrt(SQ(dx) + SQ(dy));
         double depen_len = 8 - dist * result;
         if (depen_len < 0.0000001) break;
-        if (dist == 0) return;
+        if (dist == 0) { S->ball_dbg[1]++; return; }
         double xnorm = dx / dist, ynorm = dy / dist;
         e->x += xnorm * depen_len;
         e->y += ynorm * depen_len;
         xnormal += xnorm;
         ynormal += ynorm;
     }
+    if (it == 16) S->ball_dbg[0]++;
     double normal_len = sqrt(SQ(xnormal) + SQ(ynormal));
     if (normal_len > 0) {
         double dx = xnormal / normal_len, dy = ynormal / normal_len;
@@ -1303,6 +1367,7 @@ static void ball_think(OSim *S, Entity *e)
         if (dot_product < 0) {
             double speed = sqrt(SQ(e->xspeed) + SQ(e->yspeed));
             int bounce_strength = speed <= 1.35 ? 1 : 2;
+            if (bounce_strength == 2) S->ball_dbg[2]++;
             e->xspeed -= dx * dot_product * bounce_strength;
             e->yspeed -= dy * dot_product * bounce_strength;
         }
@@ -2279,6 +2344,24 @@ int osim_entity_states(const OSim *S, int *out, int max)
     for (int i = 0; i < S->nents && r < max; i++) {
         const Entity *e = &S->ents[i];
         out[r++] = e->kind == K_MINE ? e->state : (e->kind == K_EXIT ? e->switch_hit : e->active);
+    }
+    return r;
+}
+
+/* per-entity state words as npp_dump_entities packs them: the entities that never change cell (everything but drones, bounce
+ * blocks, thwumps, death balls, shove thwumps) in map order; mines -> state, exit door -> switch_hit, regular door -> active +
+ * 2 * closed, boost pad -> active + 2 * is_touching_ninja, others -> active */
+int osim_entity_words(const OSim *S, int *out, int max)
+{
+    int r = 0;
+    for (int i = 0; i < S->nents && r < max; i++) {
+        const Entity *e = &S->ents[i];
+        if (e->kind == K_DRONE || e->kind == K_BOUNCE || e->kind == K_THWUMP || e->kind == K_BALL || e->kind == K_SHOVE) continue;
+        if (e->kind == K_MINE) out[r++] = e->state;
+        else if (e->kind == K_EXIT) out[r++] = e->switch_hit;
+        else if (e->kind == K_DOOR_REG) out[r++] = e->active + 2 * e->closed;
+        else if (e->kind == K_BOOST) out[r++] = e->active + 2 * e->touching;
+        else out[r++] = e->active;
     }
     return r;
 }

@@ -18,6 +18,7 @@ _LIBS = {}
 
 ACTIONS = [(0, 0), (-1, 0), (1, 0), (0, 1), (-1, 1), (1, 1)]
 N_DISC = 22
+KEEP_FIELD = -2   # osim_set_mover: leave state / dir alone (OSIM_KEEP_FIELD)
 
 
 def build(force=False):
@@ -65,9 +66,17 @@ def _lib(variant):
     lib.osim_dump_entities.restype = C.c_int
     lib.osim_entity_states.argtypes = [P, C.POINTER(C.c_int), C.c_int]
     lib.osim_entity_states.restype = C.c_int
+    lib.osim_entity_words.argtypes = [P, C.POINTER(C.c_int), C.c_int]
+    lib.osim_entity_words.restype = C.c_int
     lib.osim_set_entity_pos.argtypes = [P, C.c_int, C.c_double, C.c_double]
     lib.osim_set_ninja.argtypes = [P, C.c_double, C.c_double, C.c_double, C.c_double]
     lib.osim_set_ninja.restype = None
+    lib.osim_set_mover.argtypes = [P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
+    lib.osim_set_mover.restype = C.c_int
+    lib.osim_dump_movers.argtypes = [P, C.POINTER(C.c_double), C.c_int]
+    lib.osim_dump_movers.restype = C.c_int
+    lib.osim_ball_debug.argtypes = [P, C.POINTER(C.c_int), C.c_int]
+    lib.osim_ball_debug.restype = None
     lib.osim_dump_draw.argtypes = [P, C.POINTER(C.c_double), C.c_int]
     lib.osim_dump_draw.restype = C.c_int
     lib.osim_dump_edges.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -167,6 +176,27 @@ class Oracle:
         """Test aid: overwrite the ninja's xpos, ypos, xspeed, yspeed (tests/inject_states.py); nothing else changes."""
         self.lib.osim_set_ninja(self.h, float(x), float(y), float(vx), float(vy))
 
+    def set_mover(self, slot, x, y, a, b, field=None):
+        """Test aid: overwrite one mover's x, y, a, b (a, b: speed of a bounce block / death ball, target of a drone, 0 for the
+        thwumps) and optionally its state (thwump -1 / 0 / 1) or dir (drone 0..3); the cell and the grid lists stay as they
+        are.  `slot` counts the movers in entity_dic order.  A refusal raises ValueError and writes nothing."""
+        if self.lib.osim_set_mover(self.h, int(slot), float(x), float(y), float(a), float(b), KEEP_FIELD if field is None else int(field)) != 0:
+            raise ValueError("set_mover: refused (slot %r, field %r)" % (slot, field))
+
+    def dump_movers(self):
+        """[n, 5] f64 rows x, y, a, b, state / dir of every mover in entity_dic order (see osim_dump_movers)."""
+        buf = np.zeros((1024, 5), dtype=np.float64)
+        n = self.lib.osim_dump_movers(self.h, buf.ctypes.data_as(C.POINTER(C.c_double)), len(buf))
+        assert n >= 0
+        return buf[:n].copy()
+
+    def ball_debug(self, clear=True):
+        """int [4]: death-ball think calls since the last clear that ran all 16 depenetrations, bailed on dist == 0, bounced with
+        bounce_strength 2, snapped new_speed to 0 (debug counters of the oracle only)."""
+        o = np.zeros(4, dtype=np.int32)
+        self.lib.osim_ball_debug(self.h, o.ctypes.data_as(C.POINTER(C.c_int)), 1 if clear else 0)
+        return o
+
     def draw_list(self):
         """[n, 13] rows of what the entity layer would draw, entity_dic order (see osim_dump_draw)."""
         buf = np.zeros((4096, 13), dtype=np.float64)
@@ -197,6 +227,12 @@ class Oracle:
     def entity_states(self):
         buf = np.zeros(4096, dtype=np.int32)
         n = self.lib.osim_entity_states(self.h, buf.ctypes.data_as(C.POINTER(C.c_int)), len(buf))
+        return buf[:n].copy()
+
+    def entity_words(self):
+        """per-entity state words as NppBatch.dump_entities packs them, zoo kinds included (see osim_entity_words)"""
+        buf = np.zeros(4096, dtype=np.int32)
+        n = self.lib.osim_entity_words(self.h, buf.ctypes.data_as(C.POINTER(C.c_int)), len(buf))
         return buf[:n].copy()
 
 
