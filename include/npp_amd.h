@@ -141,8 +141,9 @@ int npp_level_truncation_limit(const double *map, int64_t n, int32_t *limit, int
 /* NppEnvironment.step for all envs (base_environment.py:483-755): d_actions[N] in 0..5
  * (_actions_to_execute, :366-402), up to frame_skip ticks with early stop on win/death (:535-609),
  * truncation check (:613), observation (:627,680).
- * d_reward: the sparse terminal constants only (+20 win, -3 death, +10 exit switch) -- REWARD PARITY: NONE; the reference's
- * reward is its PBRS calculator (reward_calculation/main_reward_calculator.py:225), which is out of scope. */
+ * d_reward: the sparse terminal constants only (+20 win, -3 death, +10 exit switch) -- reward parity, sparse mode: none; pbrs mode:
+ * section 20 of DESIGN.md (npp_set_reward_mode / npp_step_reward below: the reference's PBRS calculator,
+ * reward_calculation/main_reward_calculator.py:225, from a launch of its own behind this one, which overwrites d_reward). */
 int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out);
 
 /* Several Gymnasium steps in ONE launch, for action sequences that do not depend on the observations in between: batched
@@ -274,6 +275,59 @@ int npp_path_mask_stats_view(npp_handle h, const uint32_t **d_observed, const ui
  * (npp_reachability refuses it). */
 int npp_path_direction_host(const double *map, int64_t n, const double *pos, const uint8_t *switch_activated, int count,
                             int8_t *direction_out, uint8_t *from_graph_out, int32_t *status);
+
+/* Reward mode "pbrs": the step reward of the reference's RewardCalculator.calculate_reward
+ * (gym_environment/reward_calculation/main_reward_calculator.py:225-904) as base_environment.step calls it (:644-657) with
+ * RewardConfig(enable_path_waypoints=False), no goal curriculum, no momentum waypoints and a calculator reset() at every episode
+ * start: terminal rewards (death with the switch milestone credited, win with the path-efficiency bonus), switch milestone, time
+ * penalty x frames, distance milestones, gamma * Phi(s') - Phi(s) on the reference's potential WITH its position cache, the
+ * completion-approach bonus, all times 0.1.  The rule is one function, npp_reward.hpp, compiled for the device (npp_reward.hip) and
+ * for npp_reward_host; DESIGN.md 20 has the rule, the reference's quirks it reproduces, the per-env state and what the fixture
+ * (tests/golden/reward.npz) pins.  Out of scope: the waypoint systems, the goal curriculum, RewardConfig's schedules (its properties
+ * as functions of the success rate: set the numbers with npp_set_reward_params), the TensorBoard diagnostics.  Known deviation: a step
+ * that ends by TRUNCATION under NPP_FLAG_AUTORESET gets time penalty + switch milestone only (the reference evaluates the final
+ * position, which the in-kernel reset has overwritten).
+ * Off by default: nothing is allocated or launched, and d_reward of npp_step keeps its sparse constants bit for bit.
+ * npp_set_reward_mode(h, mode, params): 0 sparse, 1 pbrs (params NULL = the defaults); other values: NPP_ERR_INVALID.  Switching on
+ *   needs levels loaded (NPP_ERR_STATE), builds the tables of npp_reachability and each level's constants, allocates the per-env state
+ *   (132 bytes per env, + 13 KB per env when a level takes the reference's miss branch) and restarts the reward state of every env
+ *   on its current state.  NPP_ERR_UNSUPPORTED where npp_reachability refuses a level, and where the reference itself raises
+ *   ("Combined geometric path distance is infinite") or would leave the restated paths; the mode then stays off.  npp_load_levels
+ *   switches the mode off.
+ * npp_set_reward_params(h, params): new numbers from the next npp_step_reward on (NULL: the defaults).
+ * npp_step_reward(h, d_reward, d_components, d_status): the launch, on the handle's stream, after joining an observation overlap.  Call
+ *   it once per npp_step, after it (NPP_ERR_STATE otherwise, in mode 0, and while an entity is repositioned with npp_set_entity_pos it
+ *   is NPP_ERR_UNSUPPORTED).  d_reward f32[n_envs]: the fp64 reward rounded once.  d_components (f32[n_envs][6], may be NULL), unscaled:
+ *   pbrs, distance milestone, switch milestone, approach bonus, terminal reward, potential.  d_status (i32[n_envs], may be NULL): which
+ *   branch evaluated the potential: 0 full evaluation, 1 position-cache hit, 2 hit without next hop, 3 none (terminal step).  The
+ *   handle remembers the flags and frames rows of the last npp_step (a caller's d_flags / d_frames must stay allocated until this call;
+ *   rows of the handle's are used where the caller passed none).
+ * Episode starts: the in-kernel auto-reset (from the step's flags byte), npp_reset, npp_assign_levels, the level pool's draw,
+ *   npp_restore / npp_archive_restore and the test aids npp_set_ninja_state / npp_set_mover_state restart the reward state of the envs
+ *   they touch ON THE STATE THEY LEAVE: calculator state emptied, cache key dropped, that state observed as the next step's prev_obs.
+ *   Archive / snapshot records do NOT carry reward state.  npp_step_many is NPP_ERR_STATE while the mode is on: its inner steps have no
+ *   observation.
+ * The per-episode dictionary of the path calculator (levels whose exit door lies 12-24 px from its switch) is the handle's one, shared
+ *   with npp_reachability: an entry is written once per (episode, cell), from the position of the first query, so the two launches
+ *   agree whichever runs first PROVIDED both run at every observation when both are in use (NppVecEnvironment does). */
+typedef struct NppRewardParams {
+    double death_penalty, level_completion_reward, switch_activation_reward, time_penalty_per_step, pbrs_objective_weight, pbrs_gamma;
+} NppRewardParams;
+/* what a fresh RewardConfig() and PBRS_GAMMA give (recorded in tests/golden/reward.npz): -80, 200, 100, 0, 40, 0.99 */
+void npp_reward_default_params(NppRewardParams *out);
+int npp_set_reward_mode(npp_handle h, int mode, const NppRewardParams *params);
+int npp_set_reward_params(npp_handle h, const NppRewardParams *params);
+int npp_step_reward(npp_handle h, float *d_reward /* [N] */, float *d_components /* [N,6] or NULL */, int32_t *d_status /* [N] or NULL */);
+/* Host-only: PBRSCalculator._compute_combined_path_distance (pbrs_potentials.py:897-1178) for one level: out[3] = spawn -> switch,
+ * switch -> exit, their sum (pixels along the physics-optimal path on the base graph).  NPP_ERR_UNSUPPORTED (status 2, out = +inf where
+ * the reference raises) for a level the mode refuses. */
+int npp_reward_level_constants_host(const double *map, int64_t n, double *out, int32_t *status);
+/* Host-only: the rollout twin of npp_step_reward on one level.  pos0: the position after the first reset; per step k pos[k] (the state the
+ * env is in after the step: the reset state when flags[k] & end_bits), flags[k] (NPP_F_* of the state the step ended in), frames[k].
+ * reward_out f64[count]; components_out f64[count][6] and kind_out u8[count] (d_status) may be NULL. */
+int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params, const double *pos0, const double *pos, const uint8_t *flags,
+                    const uint16_t *frames, int count, int end_bits, double *reward_out, double *components_out, uint8_t *kind_out,
+                    int32_t *status);
 
 /* The whole gray frame of envs [env0, env0 + count): what NPlayHeadless.render() returns in grayscale mode
  * (nplay_headless.py:144-156, nsim_renderer.py:71-134).  d_out: u8[count][600][1056]. */

@@ -43,6 +43,8 @@ EXPORTS = [
     "npp_archive_cell_keys_host", "npp_archive_cell_pick_host",
     "npp_set_routes", "npp_route_view", "npp_archive_route_view", "npp_route_apply_host",
     "npp_set_action_masking", "npp_path_action_mask", "npp_path_mask_stats_view", "npp_path_direction_host",
+    "npp_set_reward_mode", "npp_set_reward_params", "npp_step_reward", "npp_reward_default_params", "npp_reward_level_constants_host",
+    "npp_reward_host",
 ]
 
 
@@ -179,6 +181,13 @@ def lib():
     L.npp_path_direction_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
     L.npp_num_envs.argtypes = [H]
+    L.npp_set_reward_mode.argtypes = [H, C.c_int, C.c_void_p]
+    L.npp_set_reward_params.argtypes = [H, C.c_void_p]
+    L.npp_step_reward.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_reward_default_params.argtypes = [C.c_void_p]
+    L.npp_reward_level_constants_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p]
+    L.npp_reward_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.npp_num_levels.argtypes = [H]
     for name in EXPORTS:
         if name != "npp_last_error":

@@ -87,12 +87,16 @@ class NppAsyncVecEnvironment:
     observations here): enable_augmentation is refused likewise (NppVecEnvironment(enable_augmentation=True) has it).
     No path-direction action masking: action_masking_mode other than None / "none" raises ValueError
     (NppVecEnvironment(action_masking_mode="hard") has it).
+    No reward mode "pbrs": reward_mode other than "sparse" raises ValueError (NppVecEnvironment(reward_mode="pbrs") has it).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
-                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None):
+                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None, reward_mode="sparse"):
         assert output in ("torch", "numpy")
+        if reward_mode != "sparse":
+            raise ValueError("NppAsyncVecEnvironment has no reward mode %r: its sub-batches step on streams of their own and the reward "
+                             'launch follows every single step; NppVecEnvironment(reward_mode="pbrs") has it' % (reward_mode,))
         if action_masking_mode not in (None, "none"):
             raise ValueError("NppAsyncVecEnvironment has no path-direction action masking (action_masking_mode=%r): "
                              "NppVecEnvironment(action_masking_mode=...) has it" % (action_masking_mode,))

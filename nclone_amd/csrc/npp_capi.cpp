@@ -18,6 +18,7 @@
 #include "npp_internal.hpp"
 #include "npp_level.hpp"
 #include "npp_reach_build.hpp"
+#include "npp_reward.hpp"
 
 using namespace npp;
 
@@ -280,6 +281,25 @@ struct PathMask {
     uint32_t *plane(int k, int n) const { return counters.get() + (size_t)k * n; }
 };
 
+// reward mode "pbrs" (npp_set_reward_mode / npp_step_reward, npp_reward.hip): the mode, the parameters, the levels' constants, the
+// per-env state planes and where the last step wrote its flags and frames rows.  Allocated when the mode is switched on; dropped by
+// npp_load_levels (the constants belong to the level set).
+struct Reward {
+    int mode = 0;                        // 0 sparse, 1 pbrs
+    NppRewardParams params{};
+    DevBuf<RewardLevel> levels;          // [n_levels]
+    DevBuf<double> sd;                   // [RW_ND][n]
+    DevBuf<uint32_t> si;                 // [RW_NI][n]
+    DevBuf<uint32_t> stamp2;             // [n][REACH_CELLS] the fallback query's dictionary (levels with ReachHdr::miss_exit only)
+    DevBuf<double> raw2;
+    DevBuf<uint8_t> flagbuf;             // [n] the step's flags row when the caller asked for none
+    DevBuf<uint16_t> framebuf;           // [n] likewise the frames row
+    DevBuf<int32_t> restore_status;      // status row of an npp_archive_restore whose caller asked for none (only restored envs restart)
+    size_t restore_cap = 0;
+    const uint8_t *flags = nullptr;      // rows of the last npp_step not yet consumed by npp_step_reward
+    const uint16_t *frames = nullptr;
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -316,6 +336,7 @@ struct npp_handle_s {
     Cells cells;
     Routes rt;
     PathMask pm;
+    Reward rw;
 };
 
 
@@ -642,14 +663,16 @@ int ensure_gv(npp_handle h) {
 
 // The reachability tables (npp_reach.cpp) are built the first time the observation is asked for: ~1 ms of host work and
 // ~260 KB of HBM per level, which handles that never ask for it do not pay.
-int ensure_reach(npp_handle h) {
+// `keep` (may be null): receives every level's ReachBuilt when the tables are built by this call (left empty when they existed)
+int ensure_reach(npp_handle h, std::vector<ReachBuilt> *keep = nullptr) {
     if (h->ls.reach.hdr) return NPP_OK;
     const size_t N = (size_t)h->n, nl = h->ls.levels.size();
     std::vector<ReachHdr> hdrs(nl);
     std::vector<unsigned char> blob;
     bool any_miss = false;
+    std::vector<ReachBuilt> local(keep ? nl : 1);
     for (size_t i = 0; i < nl; i++) {
-        ReachBuilt R;
+        ReachBuilt &R = local[keep ? i : 0];
         build_reach(h->ls.levels[i], R);
         if (!R.hdr.supported)
             return fail(h, NPP_ERR_UNSUPPORTED, "npp_reachability: level " + std::to_string(i) + ": " + R.note +
@@ -676,6 +699,7 @@ int ensure_reach(npp_handle h) {
     HIP_TRY(h, r.hdr.alloc(nl));
     HIP_TRY(h, hipMemcpy(r.hdr.get(), hdrs.data(), r.hdr.bytes(), hipMemcpyHostToDevice));
     h->ls.reach = std::move(r);
+    if (keep) *keep = std::move(local);
     return NPP_OK;
 }
 
@@ -806,6 +830,56 @@ int route_append(npp_handle h, const uint8_t *d_actions, int n_steps, int frame_
     });
 }
 
+// reward mode "pbrs": what both kernels of npp_reward.hip read (the caller fills in the rows, the outputs or the envs)
+RewardArgs reward_args(npp_handle h) {
+    const LevelSet &L = h->ls;
+    const Reward &w = h->rw;
+    RewardArgs a{};
+    a.n = h->n;
+    a.f64 = h->env.f64.get();
+    a.u32 = h->env.u32.get();
+    a.ent_bits = L.ent.get();
+    a.env_level = h->env.level.get();
+    a.hdr = L.hdr.get();
+    a.rh = L.reach.hdr.get();
+    a.rblob = L.reach.blob.get();
+    a.rl = w.levels.get();
+    const double q[6] = {w.params.death_penalty, w.params.level_completion_reward, w.params.switch_activation_reward,
+                         w.params.time_penalty_per_step, w.params.pbrs_objective_weight, w.params.pbrs_gamma};
+    std::memcpy(a.params, q, sizeof(q));
+    a.sd = w.sd.get();
+    a.si = w.si.get();
+    a.md = L.reach.miss();
+    a.stamp2 = w.stamp2.get();
+    a.raw2 = w.raw2.get();
+    a.end_bits = (h->flags & NPP_FLAG_AUTORESET) ? (int)(NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED) : 0;
+    return a;
+}
+
+// an episode start outside the step kernel: the reward state of the envs under the device mask (null = all), or of the `count` envs
+// listed in d_envs (those whose d_status entry, when given, is 0), restarts on the state they are in.  The caller has joined the
+// streams; no-op with the mode off.
+int reward_restart(npp_handle h, const uint8_t *d_mask, const int32_t *d_envs = nullptr, const int32_t *d_status = nullptr, int count = 0, int init = 0) {
+    if (!h->rw.mode) return NPP_OK;
+    RewardArgs a = reward_args(h);
+    a.mask = d_mask;
+    a.envs = d_envs;
+    a.env_status = d_status;
+    a.count = count;
+    HIP_TRY(h, launch_reward_restart(a, init, h->stream));
+    h->rw.flags = nullptr;
+    h->rw.frames = nullptr;
+    return NPP_OK;
+}
+
+int reward_restart_range(npp_handle h, int env0, int count) {
+    if (!h->rw.mode) return NPP_OK;
+    std::vector<uint8_t> mask((size_t)h->n, 0);
+    std::fill(mask.begin() + env0, mask.begin() + env0 + count, 1);
+    HIP_TRY(h, hipMemcpy(h->env.mask.get(), mask.data(), mask.size(), hipMemcpyHostToDevice));
+    return reward_restart(h, h->env.mask.get());
+}
+
 // `fresh` = the entities are created for the first time since the level was assigned (the state a replay starts from);
 // any later reset is a Simulator.reset(), after which Entity.index no longer starts at 0 (see ZOO_HEAD in npp_internal.hpp)
 int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, int automatic = 0) {
@@ -826,6 +900,7 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
         HIP_TRY(h, launch_path_mask_restart(h->n, a.reset_mask, h->pm.plane(0, h->n), h->pm.plane(1, h->n), h->stream));
         h->pm.flags = nullptr;
     }
+    if (int rc = reward_restart(h, a.reset_mask)) return rc;   // (reward mode "pbrs") an episode start
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));  // env_mask is caller memory: finish the copy
     return NPP_OK;
 }
@@ -869,6 +944,10 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
         o.obs_mask = h->pool.changed.get();
         HIP_TRY(h, launch_step(o, h->stream));
     }
+    // (reward mode "pbrs") after a step the reward launch restarts the envs whose episode ended, on their new level, from the step's
+    // flags; an explicit draw (npp_draw_levels) is an episode start of its own
+    if (!out)
+        if (int rc = reward_restart(h, h->pool.changed.get())) return rc;
     return NPP_OK;
 }
 
@@ -1003,6 +1082,7 @@ int npp_restore(npp_handle h, const uint8_t *env_mask) {
         a.draws = nullptr;
     }
     HIP_TRY(h, launch_archive_restore(a, h->stream));
+    if (int rc = reward_restart(h, a.mask)) return rc;   // (reward mode "pbrs") records carry no reward state: it restarts on the restored one
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));
     // the restored zoo blocks carry the repositioning flags / coordinates of the snapshot (head words 3..7): the host's
     // view of them (which decides whether the zoo kernels run) is restored with them
@@ -1041,11 +1121,23 @@ int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_env
     a.envs = d_envs;
     a.slots = d_slots;
     a.status = d_status;
+    if (!store && h->rw.mode && !d_status && count > 0) {   // (reward mode "pbrs") which entries restored decides which envs restart
+        Reward &w = h->rw;
+        if (w.restore_cap < (size_t)count) {
+            DevBuf<int32_t> t;
+            HIP_TRY(h, t.alloc((size_t)count));
+            w.restore_status = std::move(t);
+            w.restore_cap = (size_t)count;
+        }
+        a.status = w.restore_status.get();
+    }
     a.rec = A.rec.get();
     a.meta_f64 = A.meta_f64.get();
     a.meta_i32 = A.meta_i32.get();
     if (!store) a.draws = nullptr;   // (the pool is refused: a restored env keeps its draw count)
     HIP_TRY(h, store ? launch_archive_store(a, h->stream) : launch_archive_restore(a, h->stream));
+    if (!store && count > 0)   // (reward mode "pbrs") records carry no reward state: it restarts on the restored one
+        if (int rc = reward_restart(h, nullptr, d_envs, a.status, count)) return rc;
     // a restored env takes the record's truncation limit on the device: the host mirror is read back where a host path needs it
     if (!store && count > 0) h->pool.dirty = true;
     return NPP_OK;
@@ -1406,6 +1498,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     h->ls = std::move(next);
     h->ar = Archive();   // the checkpoint archive's records were laid out for the old set
     h->cells = Cells();  // (the cell index goes with the archive)
+    h->rw = Reward();    // (reward mode "pbrs") the levels' constants and every env's reward state belonged to the old set: the mode is off
     h->snap = Snapshot();   // likewise
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
     h->pool.w.clear();
@@ -1761,7 +1854,7 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
     if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
     const bool pool = h->pool.on && (h->flags & NPP_FLAG_AUTORESET);
-    if (!pool && !h->rt.cap && !h->pm.mode) return step_impl(h, d_actions, frame_skip, out);
+    if (!pool && !h->rt.cap && !h->pm.mode && !h->rw.mode) return step_impl(h, d_actions, frame_skip, out);
     npp_step_out o;
     std::memset(&o, 0, sizeof(o));
     if (out) o = *out;
@@ -1772,6 +1865,12 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
     if (h->rt.cap) {   // action routes: the append behind the step reads the step's flags and frames rows
         ON_DEVICE_JOINED(h);
         if (int rc = route_rows(h, o, 1)) return rc;
+    }
+    if (h->rw.mode) {   // reward mode "pbrs": npp_step_reward reads the step's flags and frames rows
+        if (!o.d_flags) o.d_flags = h->rw.flagbuf.get();
+        if (!o.d_frames) o.d_frames = h->rw.framebuf.get();
+        h->rw.flags = o.d_flags;
+        h->rw.frames = o.d_frames;
     }
     if (pool && !o.d_flags) o.d_flags = h->pool.flags.get();
     if (int rc = step_impl(h, d_actions, frame_skip, &o)) return rc;
@@ -1788,6 +1887,9 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
 int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0 || n_steps <= 0) return fail(h, NPP_ERR_INVALID, "npp_step_many: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step_many: no levels loaded");
+    if (h->rw.mode)
+        return fail(h, NPP_ERR_STATE, "npp_step_many: reward mode \"pbrs\" is on and the launch's inner steps have no observation "
+                                      "(npp_set_reward_mode(h, 0, NULL) first)");
     ON_DEVICE_JOINED(h);
     KernelArgs a = base_args(h);
     a.inputs = d_actions;
@@ -2179,6 +2281,87 @@ int npp_path_mask_stats_view(npp_handle h, const uint32_t **d_observed, const ui
     return NPP_OK;
 }
 
+int npp_set_reward_params(npp_handle h, const NppRewardParams *params) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_reward_params: NULL handle");
+    NppRewardParams q;
+    if (params) q = *params; else npp_reward_default_params(&q);
+    const double v[6] = {q.death_penalty, q.level_completion_reward, q.switch_activation_reward, q.time_penalty_per_step,
+                         q.pbrs_objective_weight, q.pbrs_gamma};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(h, NPP_ERR_INVALID, "npp_set_reward_params: non-finite value");
+    h->rw.params = q;
+    return NPP_OK;
+}
+
+int npp_set_reward_mode(npp_handle h, int mode, const NppRewardParams *params) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_reward_mode: NULL handle");
+    if (mode < 0 || mode > 1) return fail(h, NPP_ERR_INVALID, "npp_set_reward_mode: mode must be 0 (sparse) or 1 (pbrs)");
+    Reward &w = h->rw;
+    if (!mode) {
+        w.mode = 0;
+        w.flags = nullptr; w.frames = nullptr;
+        return NPP_OK;
+    }
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_reward_mode: no levels loaded");
+    if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_set_reward_mode: exit switch / door repositioned with npp_set_entity_pos");
+    if (int rc = npp_set_reward_params(h, params)) return rc;
+    ON_DEVICE_JOINED(h);
+    std::vector<ReachBuilt> built;   // every level's host tables, built ONCE: by ensure_reach when it builds, else below
+    if (int rc = ensure_reach(h, &built)) return rc;   // (refuses what npp_reachability refuses, with its message)
+    const size_t N = (size_t)h->n, nl = h->ls.levels.size();
+    if (!w.levels) {
+        std::vector<RewardLevel> rl(nl);
+        bool any_miss = false;
+        ReachBuilt one;
+        for (size_t i = 0; i < nl; i++) {
+            if (built.empty()) build_reach(h->ls.levels[i], one);
+            const ReachBuilt &R = built.empty() ? one : built[i];
+            std::string note;
+            if (!reward_level_constants(h->ls.levels[i], R, rl[i], note))
+                return fail(h, NPP_ERR_UNSUPPORTED, "npp_set_reward_mode: level " + std::to_string(i) + ": " + note + " (DESIGN.md 20)");
+            any_miss = any_miss || R.hdr.miss_exit;
+        }
+        Reward t;   // complete or not at all
+        HIP_TRY(h, t.levels.alloc(nl));
+        HIP_TRY(h, hipMemcpy(t.levels.get(), rl.data(), t.levels.bytes(), hipMemcpyHostToDevice));
+        HIP_TRY(h, t.sd.alloc((size_t)RW_ND * N));
+        HIP_TRY(h, t.si.alloc((size_t)RW_NI * N));
+        HIP_TRY(h, t.flagbuf.alloc(N));
+        HIP_TRY(h, t.framebuf.alloc(N));
+        if (any_miss) {
+            HIP_TRY(h, t.stamp2.alloc(REACH_CELLS * N));
+            HIP_TRY(h, hipMemset(t.stamp2.get(), 0, t.stamp2.bytes()));
+            HIP_TRY(h, t.raw2.alloc(REACH_CELLS * N));
+        }
+        t.params = w.params;
+        w = std::move(t);
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (w.stamp2) HIP_TRY(h, hipMemset(w.stamp2.get(), 0, w.stamp2.bytes()));   // (every env's epoch restarts at 1 below)
+    w.mode = 1;
+    return reward_restart(h, nullptr, nullptr, nullptr, 0, 1);   // switching on resets all reward state
+}
+
+int npp_step_reward(npp_handle h, float *d_reward, float *d_components, int32_t *d_status) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_step_reward: NULL handle");
+    Reward &w = h->rw;
+    if (!w.mode) return fail(h, NPP_ERR_STATE, "npp_step_reward: reward mode \"pbrs\" is off (npp_set_reward_mode)");
+    if (!d_reward) return fail(h, NPP_ERR_INVALID, "npp_step_reward: d_reward is NULL");
+    if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_step_reward: exit switch / door repositioned with npp_set_entity_pos");
+    if (!w.flags || !w.frames) return fail(h, NPP_ERR_STATE, "npp_step_reward: no npp_step since the last call (one call per step)");
+    ON_DEVICE_JOINED(h);
+    RewardArgs a = reward_args(h);
+    a.flags = w.flags;
+    a.frames = w.frames;
+    a.reward = d_reward;
+    a.comps = d_components;
+    a.status = d_status;
+    HIP_TRY(h, launch_reward(a, h->stream));
+    w.flags = nullptr;   // consumed
+    w.frames = nullptr;
+    return NPP_OK;
+}
+
 int npp_graph_observation(npp_handle h, float *d_node_feats, uint16_t *d_edge_index, uint8_t *d_node_mask, uint8_t *d_edge_mask, int flags) {
     if (!h || !d_node_feats || !d_edge_index || !d_node_mask || !d_edge_mask || (flags & ~1))
         return fail(h, NPP_ERR_INVALID, "npp_graph_observation: bad arguments");
@@ -2291,7 +2474,7 @@ int npp_set_ninja_state(npp_handle h, int env0, int count, const double *xyv) {
         for (int i = 0; i < count; i++) col[i] = xyv[(size_t)i * 4 + k];
         HIP_TRY(h, hipMemcpy(h->env.f64.get() + plane[k] * N + env0, col.data(), sizeof(double) * count, hipMemcpyHostToDevice));
     }
-    return NPP_OK;
+    return reward_restart_range(h, env0, count);   // (reward mode "pbrs") an injected state starts the env's reward state afresh
 }
 
 // field of a mover record as the reference holds it: drone dir, thwump state -1 / 0 / 1, shove thwump state; 0 for the rest
@@ -2335,7 +2518,7 @@ int npp_set_mover_state(npp_handle h, int env0, int count, int slot, const doubl
         w0 = (w0 & ~(3u << 11)) | (bits << 11);
         HIP_TRY(h, hipMemcpy(rec + 4, &w0, sizeof(w0), hipMemcpyHostToDevice));
     }
-    return NPP_OK;
+    return reward_restart_range(h, env0, count);   // (reward mode "pbrs") likewise
 }
 
 int npp_dump_movers(npp_handle h, int env, double *out, int max_rows, int *n_out) {

@@ -314,6 +314,37 @@ struct PathMaskArgs {
 };
 hipError_t launch_path_mask(const PathMaskArgs &a, hipStream_t s);
 hipError_t launch_path_mask_restart(int n, const uint8_t *mask, uint32_t *observed, uint32_t *applied, hipStream_t s);
+// npp_reward.hip: reward mode "pbrs" (see npp_set_reward_mode in include/npp_amd.h; the rule: npp_reward.hpp)
+struct RewardLevel;
+struct RewardArgs {
+    int n;
+    const double *f64;            // [NF64][n]
+    const uint32_t *u32;          // [NU32][n]
+    const uint32_t *ent_bits;     // [n_words_max][n]
+    const int32_t *env_level;     // [n]
+    const LevelHdr *hdr;          // [n_levels]
+    const ReachHdr *rh;           // [n_levels] the reachability tables (npp_reach.hpp)
+    const unsigned char *rblob;
+    const RewardLevel *rl;        // [n_levels] the levels' constants
+    double params[6];             // NppRewardParams
+    double *sd;                   // [RW_ND][n] the per-env reward state (npp_reward.hpp RewardState), doubles
+    uint32_t *si;                 // [RW_NI][n] ... words
+    ReachMissDev md;              // the path calculator's per-episode dictionary, shared with npp_reachability (null pointers: none)
+    uint32_t *stamp2;             // [n][REACH_CELLS] the fallback query's own dictionary, or null
+    double *raw2;
+    const uint8_t *flags;         // [n] flags row of the step
+    const uint16_t *frames;       // [n] frames row of the step
+    int end_bits;                 // flags bits after which the step kernel auto-reset the env (0 without auto-reset)
+    const uint8_t *mask;          // restart: the envs (null = all) ...
+    const int32_t *envs;          // ... or, when not null, a list of `count` envs, entry i skipped when env_status[i] != 0
+    const int32_t *env_status;    //     (null = none skipped; an entry outside 0 .. n - 1 is skipped)
+    int count;
+    float *reward;                // [n]
+    float *comps;                 // [n][6] or null
+    int32_t *status;              // [n] or null
+};
+hipError_t launch_reward(const RewardArgs &a, hipStream_t s);
+hipError_t launch_reward_restart(const RewardArgs &a, int init, hipStream_t s);
 hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n, const int *edge, int parts, uint8_t *phase, hipStream_t s);
 hipError_t launch_spin(long long ticks, hipStream_t s);   // a bounded idle wavefront (stream calibration)
 // order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)

@@ -21,6 +21,7 @@
 #include "npp_level.hpp"
 #include "npp_reach_build.hpp"
 #include "npp_reach_features.hpp"
+#include "npp_reward.hpp"
 
 namespace npp {
 namespace {
@@ -760,6 +761,153 @@ void pack_reach(const ReachBuilt &R, ReachHdr &hdr, std::vector<unsigned char> &
     hdr.off_rec = append(rec.data(), sizeof(ReachRec) * RNODES);
 }
 
+// ---- reward mode "pbrs": the per-level constants of PBRSCalculator._compute_combined_path_distance (pbrs_potentials.py:897-1178)
+namespace {
+
+// find_ninja_node(pos, adjacency, ninja_radius=10) without a goal node (pathfinding_utils.py:1331-1496) on a host graph: the
+// overlapping node closest to the ninja (first minimum in dict order), else the first node in dict order inside the 24-px box
+int graph_ninja_node(const Graph &g, double px, double py) {
+    const double nx = px - 24.0, ny = py - 24.0;
+    int best = -1, bkey = 0;
+    double bd = 0.0;
+    for (int id = 0; id < RNODES; id++) {
+        if (!g.in[id]) continue;
+        const double dx = reach_node_x(id) - nx, dy = reach_node_y(id) - ny, d2 = dx * dx + dy * dy;
+        if (!(d2 <= 100.0)) continue;
+        const int key = reach_order_key(id);
+        if (best < 0 || d2 < bd || (d2 == bd && key < bkey)) { best = id; bd = d2; bkey = key; }
+    }
+    if (best >= 0) return best;
+    for (int id = 0; id < RNODES; id++) {
+        if (!g.in[id]) continue;
+        if (std::fabs(reach_node_x(id) + 24.0 - px) < 24.0 && std::fabs(reach_node_y(id) + 24.0 - py) < 24.0) {
+            const int key = reach_order_key(id);
+            if (best < 0 || key < bkey) { best = id; bkey = key; }
+        }
+    }
+    return best;
+}
+
+// calculate_geometric_path_distance (pathfinding_utils.py:1766-1959) from the integer position (sx, sy) to the goal (gx, gy) on
+// C.adj: bfs_distance_from_start(use_geometric_costs=False, track_geometric_distances=True, return_parents=True) (:1499-1763) -- a
+// Dijkstra on the physics cost that carries the pixel length of its paths -- then the sub-node projection tail.  It differs from
+// the A* above in what it hands the cost function as the aerial chain (:1693-1701: the chain of the NEIGHBOUR, counted for every
+// move off an ungrounded node) and in its soft early stop (:1644-1655).
+double geometric_path_distance(const AStarCtx &C, const std::vector<uint8_t> &ph, int sx, int sy, int gx, int gy, double entity_radius) {
+    const Graph &A = *C.adj;
+    const int start = graph_ninja_node(A, (double)sx, (double)sy);
+    const int goal = find_closest_node(A, ph, (double)gx, (double)gy, 10.0 + entity_radius, false);
+    if (start < 0 || goal < 0) return INFINITY;
+    if (start == goal) return 0.0;
+    std::vector<double> dist(RNODES, 0.0), geo(RNODES, 0.0);
+    std::vector<uint8_t> has(RNODES, 0), visited(RNODES, 0);
+    std::vector<int16_t> parent(RNODES, -1), grand(RNODES, -1), chain(RNODES, 0);
+    const double tdx = reach_node_x(goal) - reach_node_x(start), tdy = reach_node_y(goal) - reach_node_y(start);
+    const double early = py_pow(tdx * tdx + tdy * tdy, 0.5) * 2.0;
+    std::priority_queue<PQ> pq;
+    pq.push({0.0, reach_node_x(start), reach_node_y(start), start});
+    has[start] = 1;
+    while (!pq.empty()) {
+        const PQ cur = pq.top();
+        pq.pop();
+        if (visited[cur.id]) continue;
+        visited[cur.id] = 1;
+        if (cur.id == goal) break;
+        if (cur.d > early && has[goal]) break;
+        const bool grounded = (ph[cur.id] & 1) != 0;
+        const int cpar = parent[cur.id], cgrand = grand[cur.id];
+        const int nchain = grounded ? 0 : chain[cur.id] + 1;
+        const int i = cur.id / RH, j = cur.id % RH;
+        for (int d = 0; d < 8; d++) {
+            if (!A.edge(cur.id, d)) continue;
+            const int nb = nid(i + DX[d], j + DY[d]);
+            if (visited[nb]) continue;
+            if (DY[d] == 0 && !(grounded && (ph[nb] & 1)) && cpar >= 0 && reach_node_y(cpar) == reach_node_y(cur.id) &&
+                reach_node_x(cpar) != reach_node_x(cur.id))
+                continue;   // _violates_horizontal_rule
+            const double cost = physics_cost(C, cur.id, nb, cpar, cgrand, nchain);
+            if (cost == INFINITY) continue;
+            const double nd = cur.d + cost;
+            if (!has[nb] || nd < dist[nb]) {
+                dist[nb] = nd; has[nb] = 1;
+                parent[nb] = (int16_t)cur.id; grand[nb] = (int16_t)cpar; chain[nb] = (int16_t)nchain;
+                geo[nb] = geo[cur.id] + (d < 4 ? 12.0 : py_pow(288.0, 0.5));
+                pq.push({nd, reach_node_x(nb), reach_node_y(nb), nb});
+            }
+        }
+    }
+    if (!has[goal]) return INFINITY;
+    const double target = geo[goal];
+    // next hop: the second node of the path, rebuilt from the goal with the reference's 1000-node limit
+    int hop = -1, cur = goal, len = 0, prev = -1;
+    while (cur >= 0 && len < 1000) { prev = cur; len++; if (parent[cur] == start) hop = cur; cur = parent[cur]; }
+    if (!(len >= 2 && prev == start)) hop = -1;
+    const double combined = 10.0 + entity_radius;
+    if (hop >= 0) {
+        const double pdx = reach_node_x(hop) - reach_node_x(start), pdy = reach_node_y(hop) - reach_node_y(start);
+        const double plen = py_pow(pdx * pdx + pdy * pdy, 0.5);
+        if (plen > 0.001) {
+            const double dirx = pdx / plen, diry = pdy / plen;
+            const double projection = ((double)sx - (reach_node_x(start) + 24)) * dirx + ((double)sy - (reach_node_y(start) + 24)) * diry;
+            const double t = target - projection - combined;
+            return t > 0.0 ? t : 0.0;
+        }
+    }
+    const double t = target - combined;
+    return t > 0.0 ? t : 0.0;
+}
+
+}  // namespace
+
+bool reward_level_constants(const CompiledLevel &L, const ReachBuilt &R, RewardLevel &out, std::string &note) {
+    const ReachHdr &H = R.hdr;
+    out.spawn_to_switch = out.switch_to_exit = out.combined = INFINITY;
+    out.supported = 0; out.pad_ = 0;
+    if (!H.supported) { note = R.note; return false; }
+    if (!H.sw_valid || !H.ex_valid) { note = "no exit switch / door (the reference returns an infinite combined distance)"; return false; }
+    Graph base;
+    base.in = R.base_in; base.adj = R.base_adj;
+    const AStarCtx C{&base, &R.phys, &R.mine_mult, &R.grad};
+    const int spx = (int)(long)L.spawn_x, spy = (int)(long)L.spawn_y;
+    const double a = geometric_path_distance(C, R.phys, spx, spy, H.goal_x[0], H.goal_y[0], 6.0);
+    const double b = geometric_path_distance(C, R.phys, H.goal_x[0], H.goal_y[0], H.goal_x[1], H.goal_y[1], 12.0);
+    out.spawn_to_switch = a; out.switch_to_exit = b; out.combined = a + b;
+    if (a == INFINITY || b == INFINITY) {
+        out.spawn_to_switch = out.switch_to_exit = out.combined = INFINITY;
+        note = "combined geometric path distance is infinite (the reference raises RuntimeError)";
+        return false;
+    }
+    // the physics costs of the same two pairs (pbrs_potentials.py:1045-1054, 1094-1103) must be finite too, and the feature
+    // computation's geometric query must stay on its fast path (its goal node is looked up with the 16-px threshold only)
+    Graph fin;
+    fin.in = R.in; fin.adj = R.adj;
+    ReachHdr P;
+    std::vector<unsigned char> blob;
+    pack_reach(R, P, blob);
+    const ReachTabs T{&P, blob.data() + P.base};
+    bool miss = false;
+    const ReachNear Ns = reach_near(T, (double)spx, (double)spy), Nw = reach_near(T, (double)H.goal_x[0], (double)H.goal_y[0]);
+    const double pa = reach_goal_distance(T, Ns, (double)spx, (double)spy, 0, 6.0, nullptr, false, &miss);
+    const double pb = reach_goal_distance(T, Nw, (double)H.goal_x[0], (double)H.goal_y[0], 1, 12.0, nullptr, false, &miss);
+    if (pa == INFINITY || pb == INFINITY || miss) { note = "combined physics cost is infinite (the reference raises RuntimeError)"; return false; }
+    if (find_closest_node(fin, R.phys, H.goal_x[0], H.goal_y[0], 16.0, false) < 0) {
+        note = "no graph node within 16 px of the exit switch (the reference's geometric query leaves its fast path)";
+        return false;
+    }
+    {   // the spawn observation must write the path calculator's last-call record (npp_reward.hpp reward_observe): the record
+        // survives episode ends, and the terminal observation that could have written it last is not modelled
+        RewardState S;
+        reward_state_init(S);
+        reward_observe(T, S, L.spawn_x, L.spawn_y, 0, nullptr);
+        if (S.pc_node < 0) {
+            note = "the spawn's geometric query leaves no last-call record (spawn on the exit switch or on its goal node)";
+            return false;
+        }
+    }
+    out.supported = 1;
+    return true;
+}
+
 }  // namespace npp
 
 using namespace npp;
@@ -861,6 +1009,75 @@ int npp_reach_rollout_host(const double *map, int64_t n, const double *pos, cons
             cy = cy < 0 ? 0 : (cy > 24 ? 24 : cy);
             raw_out[k] = stamp[cx * 25 + cy] == M.epoch ? raw[cx * 25 + cy] : NAN;
         }
+    }
+    return NPP_OK;
+}
+
+void npp_reward_default_params(NppRewardParams *out) {
+    if (!out) return;
+    // a fresh RewardConfig() (reward_config.py: death_penalty, level_completion_reward, switch_activation_reward, time_penalty_per_step,
+    // pbrs_objective_weight at success rate 0) and PBRS_GAMMA (reward_constants.py:309), as tests/golden/reward.npz records them
+    *out = NppRewardParams{-80.0, 200.0, 100.0, 0.0, 40.0, 0.99};
+}
+
+int npp_reward_level_constants_host(const double *map, int64_t n, double *out, int32_t *status) {
+    if (!map || !out) return NPP_ERR_INVALID;
+    CompiledLevel L;
+    std::string err;
+    if (!compile_level(map, n, L, err)) return NPP_ERR_INVALID;
+    ReachBuilt R;
+    build_reach(L, R);
+    RewardLevel RL;
+    std::string note;
+    const bool ok = reward_level_constants(L, R, RL, note);
+    out[0] = RL.spawn_to_switch; out[1] = RL.switch_to_exit; out[2] = RL.combined;
+    if (status) *status = ok ? 0 : 2;
+    return ok ? NPP_OK : NPP_ERR_UNSUPPORTED;
+}
+
+int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params, const double *pos0, const double *pos, const uint8_t *flags,
+                    const uint16_t *frames, int count, int end_bits, double *reward_out, double *components_out, uint8_t *kind_out,
+                    int32_t *status) {
+    if (!map || !pos0 || count < 0 || (count > 0 && (!pos || !flags || !frames || !reward_out))) return NPP_ERR_INVALID;
+    CompiledLevel L;
+    std::string err;
+    if (!compile_level(map, n, L, err)) return NPP_ERR_INVALID;
+    ReachBuilt R;
+    build_reach(L, R);
+    RewardLevel RL;
+    std::string note;
+    if (!reward_level_constants(L, R, RL, note)) {
+        if (status) *status = 2;
+        return NPP_ERR_UNSUPPORTED;
+    }
+    if (status) *status = 0;
+    ReachHdr H;
+    std::vector<unsigned char> blob;
+    pack_reach(R, H, blob);
+    const ReachTabs T{&H, blob.data() + H.base};
+    NppRewardParams def;
+    npp_reward_default_params(&def);
+    const NppRewardParams &q = params ? *params : def;
+    const RewardParams P{q.death_penalty, q.level_completion_reward, q.switch_activation_reward, q.time_penalty_per_step, q.pbrs_objective_weight,
+                         q.pbrs_gamma};
+    // the two per-episode dictionaries: the feature computation's (shared with npp_reachability on the device) and the fallback query's
+    std::vector<uint32_t> stamp(REACH_CELLS, 0u), stamp2(REACH_CELLS, 0u);
+    std::vector<double> raw(REACH_CELLS, 0.0), raw2(REACH_CELLS, 0.0);
+    ReachMiss M{stamp.data(), raw.data(), 1u}, M2{stamp2.data(), raw2.data(), 1u};
+    RewardState S;
+    reward_state_init(S);
+    reward_observe(T, S, pos0[0], pos0[1], 0, &M);   // the observation of the reset state
+    for (int k = 0; k < count; k++) {
+        const bool ended = (flags[k] & (unsigned)end_bits) != 0;
+        if (ended) M.epoch++;   // clear_cache() of the path calculator (reachability_mixin.py:67-70) before the reset state is observed
+        const RewardOut o = reward_step(T, RL, P, S, pos[2 * k], pos[2 * k + 1], ended ? 0 : (flags[k] >> 2) & 1, flags[k], frames[k], (unsigned)end_bits,
+                                        &M, &M2);
+        reward_out[k] = o.reward;
+        if (components_out) {
+            double *c = components_out + 6 * (size_t)k;
+            c[0] = o.pbrs; c[1] = o.dist_milestone; c[2] = o.switch_milestone; c[3] = o.approach; c[4] = o.terminal; c[5] = o.potential;
+        }
+        if (kind_out) kind_out[k] = (uint8_t)o.kind;
     }
     return NPP_OK;
 }

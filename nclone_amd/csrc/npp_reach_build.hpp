@@ -37,6 +37,9 @@ struct CompiledLevel;
 void build_adjacency(const CompiledLevel &level, ReachAdjacency &out);
 bool build_reach(const double *map, int64_t n, ReachBuilt &out, std::string &err);
 void build_reach(const CompiledLevel &level, ReachBuilt &out);
+// reward mode "pbrs" (npp_reward.hpp): the level's constants; false + note when the level is refused (out.supported = 0)
+struct RewardLevel;
+bool reward_level_constants(const CompiledLevel &level, const ReachBuilt &R, RewardLevel &out, std::string &note);
 // appends the level's tables to `blob` (offsets in `hdr` relative to hdr.base)
 void pack_reach(const ReachBuilt &R, ReachHdr &hdr, std::vector<unsigned char> &blob);
 

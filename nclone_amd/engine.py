@@ -63,6 +63,7 @@ _FIELDS = {
     "reach_status": ((), torch.int32),
     "minimal_observation": ((40,), torch.float32),
     "path_direction": ((), torch.int8),
+    "reward_components": ((6,), torch.float32),
 }
 # graph observations (NppBatch.graph_observation): shape per env and dtype; kept out of the packed output block, which numpy-mode
 # environments copy to the host every step
@@ -71,7 +72,10 @@ GRAPH_KEYS = {"graph_node_feats": ((2500, 6), torch.float32), "graph_edge_index"
 _ALWAYS = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags", "terminal_state")
 _PACKED = ("game_state", "entity_pos", "reward", "frames", "action_mask", "flags")
 _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_frame", "global_view", "reachability_features",
-             "mine_sdf_features", "reach_status", "minimal_observation", "path_direction")
+             "mine_sdf_features", "reach_status", "minimal_observation", "path_direction", "reward_components")
+REWARD_COMPONENTS = ("pbrs", "distance_milestone", "switch_milestone", "approach_bonus", "terminal", "potential")
+REWARD_PARAMS = ("death_penalty", "level_completion_reward", "switch_activation_reward", "time_penalty_per_step", "pbrs_objective_weight",
+                 "pbrs_gamma")
 
 
 AUG_SCALES = {"light": 0.7, "medium": 1.0, "strong": 1.3}   # frame_augmentation.py:57
@@ -219,6 +223,8 @@ class NppBatch:
         self._enabled = set(_ALWAYS)
         self._masking = 0         # action masking mode (set_action_masking)
         self._mask_stats = None   # views of the handle's counters (path_mask_stats): the handle's own buffers, alive as long as it is
+        self._reward_mode = 0     # 0 sparse, 1 pbrs (set_reward_mode)
+        self._reward_pending = False   # a step() ran whose step_reward() has not: the handle holds that step's flags / frames rows
         for k in outputs:
             if k not in _OPTIONAL:
                 raise ValueError("unknown output %r (optional outputs: %s)" % (k, ", ".join(_OPTIONAL)))
@@ -226,6 +232,7 @@ class NppBatch:
         self._build_block()
 
     def _build_block(self):
+        self._reward_pending = False   # (the rows of the last step may have been in the old block)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             self.out = OutputBlock(self.n, self.device, self._enabled)
         t = self.out.t
@@ -250,7 +257,7 @@ class NppBatch:
             nat.check(self.h, self.lib.npp_set_minimal_observation(self.h, 1))
 
     def enable_outputs(self, *names):
-        """Add optional outputs (spatial_context, positions, work, switch_states, player_frame, global_view, reachability_features, mine_sdf_features, reach_status, minimal_observation, path_direction); the output
+        """Add optional outputs (spatial_context, positions, work, switch_states, player_frame, global_view, reachability_features, mine_sdf_features, reach_status, minimal_observation, path_direction, reward_components); the output
         block is re-allocated, so tensors obtained earlier are stale."""
         new = [k for k in names if k not in self._enabled]
         for k in new:
@@ -286,6 +293,7 @@ class NppBatch:
             self.h, blob.ctypes.data_as(C.POINTER(C.c_double)), offsets.ctypes.data_as(C.POINTER(C.c_int64)), len(offsets) - 1))
         self.n_levels = len(offsets) - 1
         self._archive_meta = self._archive_cells = self._archive_route_views = None   # (the checkpoint archive and its cell index go with the level set)
+        self._reward_mode, self._reward_pending = 0, False   # (so does reward mode "pbrs": its constants are per level)
 
     def assign_levels(self, level_ids, env_ids=None):
         lv = np.ascontiguousarray(level_ids, dtype=np.int32)
@@ -403,14 +411,19 @@ class NppBatch:
             tmp.d_work = work_out.data_ptr()
             out = tmp
         nat.check(self.h, self.lib.npp_step(self.h, C.c_void_p(actions.data_ptr()), int(frame_skip), C.byref(out)))
+        self._reward_pending = bool(self._reward_mode)
 
     def step_many(self, actions, frame_skip=4):
         """actions: uint8 CUDA tensor [K, N].  K Gymnasium steps in one launch (open-loop sequences: checkpoint replay, fixed
         plans).  Returns (flags u8 [K, N], reward f32 [K, N], frames i16 [K, N]); observations of the last step land in
         self.game_state etc.; with auto-reset, envs that terminate mid-sequence restart on the spot.  Nothing is pushed onto
         the frame stacks (NppVecEnvironment re-pads them from the observation after a checkpoint replay).
-        Raises ValueError while action masking is on (set_action_masking): its counters need every observation."""
+        Raises ValueError while action masking is on (set_action_masking): its counters need every observation; likewise while
+        reward mode "pbrs" is on (set_reward_mode): the reward needs the observation of every step."""
         assert actions.dtype == torch.uint8 and actions.is_cuda and actions.dim() == 2 and actions.shape[1] == self.n
+        if self._reward_mode:
+            raise ValueError('step_many with reward mode "pbrs" on: the reward is computed once per observation and the launch\'s '
+                             'inner steps have none (set_reward_mode("sparse") first)')
         if self._masking:
             raise ValueError("step_many with action masking on: the detector runs once per observation and the launch's inner "
                              "steps have none (set_action_masking(0) first)")
@@ -498,6 +511,63 @@ class NppBatch:
         st = C.c_void_p(t["reach_status"].data_ptr()) if "reach_status" in t else None
         nat.check(self.h, self.lib.npp_minimal_observation(self.h, C.c_void_p(out.data_ptr()), st))
         return out
+
+    # ---- reward mode "pbrs" (include/npp_amd.h npp_set_reward_mode) ------------------------------------
+    REWARD_MODES = {None: 0, "sparse": 0, "pbrs": 1, 0: 0, 1: 1}
+
+    def _reward_params_struct(self, params):
+        """None, a dict with some of REWARD_PARAMS (the others keep the reference's defaults) or a sequence of all six -> the six
+        doubles of NppRewardParams"""
+        q = (C.c_double * 6)()
+        self.lib.npp_reward_default_params(q)
+        if params is None:
+            return q
+        if isinstance(params, dict):
+            for k, v in params.items():
+                if k not in REWARD_PARAMS:
+                    raise ValueError("unknown reward parameter %r (parameters: %s)" % (k, ", ".join(REWARD_PARAMS)))
+                q[REWARD_PARAMS.index(k)] = float(v)
+            return q
+        if len(params) != 6:
+            raise ValueError("reward parameters: a dict or the six values %s" % (REWARD_PARAMS,))
+        for i, v in enumerate(params):
+            q[i] = float(v)
+        return q
+
+    def set_reward_mode(self, mode, params=None):
+        """"sparse" (default): the block's reward holds the step kernel's three constants.  "pbrs": step_reward() after every step()
+        overwrites it with the reference's RewardCalculator.calculate_reward (potential-based shaping on path distance, milestones,
+        terminal rewards).  Switching "pbrs" on restarts every env's reward state on its current state.  Raises
+        NppError (NPP_ERR_UNSUPPORTED) for a level set the reference's reward cannot handle; the mode then stays off."""
+        if mode not in self.REWARD_MODES:
+            raise ValueError('reward mode must be "sparse" or "pbrs", not %r' % (mode,))
+        code = self.REWARD_MODES[mode]
+        self._reward_mode = 0
+        self._reward_pending = False
+        nat.check(self.h, self.lib.npp_set_reward_mode(self.h, code, self._reward_params_struct(params) if code else None))
+        self._reward_mode = code
+
+    def set_reward_params(self, params=None):
+        """New RewardConfig numbers (REWARD_PARAMS) from the next step_reward() on; None: the reference's defaults."""
+        nat.check(self.h, self.lib.npp_set_reward_params(self.h, self._reward_params_struct(params)))
+
+    def step_reward(self, status_out=None):
+        """One call per step(), after it: the reference's step reward of every env into the block's reward, and its unscaled
+        components (REWARD_COMPONENTS) into reward_components when that output is enabled.  status_out: optional int32 CUDA tensor
+        [N]: 0 the potential was evaluated in full, 1 from the position cache, 2 from it without next hop, 3 not at all (terminal
+        step).  Enqueued on the handle's stream, so to_host() after it stages the new reward."""
+        if not self._reward_mode:
+            raise ValueError('step_reward: reward mode "pbrs" is off (set_reward_mode("pbrs"))')
+        if not self._reward_pending:
+            raise ValueError("step_reward: no step() since the last call, or the output block was re-allocated since (one call per step)")
+        t = self.out.t
+        comp = C.c_void_p(t["reward_components"].data_ptr()) if "reward_components" in t else None
+        st = None
+        if status_out is not None:
+            assert status_out.dtype == torch.int32 and status_out.is_cuda and status_out.numel() == self.n and status_out.is_contiguous()
+            st = C.c_void_p(status_out.data_ptr())
+        nat.check(self.h, self.lib.npp_step_reward(self.h, C.c_void_p(self.reward.data_ptr()), comp, st))
+        self._reward_pending = False
 
     # ---- path-direction action masking (include/npp_amd.h npp_set_action_masking; DESIGN.md 19) ---------------------
     MASKING_MODES = {None: 0, "none": 0, "off": 0, "hard": 1, "soft": 2, 0: 0, 1: 1, 2: 2}

@@ -82,8 +82,8 @@ class NppVecEnvironment:
     output      "torch" (CUDA tensors, zero copies) or "numpy" (host copies; drop-in for numpy training loops)
     truncation_limit  "dynamic" (default; the reference env's per-level limit from the reachable surface area,
                 npp_environment.py:1238-1256) or a number of frames for every env (10000 = the reference's fallback)
-    The step's `reward` carries only the sparse terminal constants -- reward parity: NONE (the reference's PBRS reward
-    calculator is out of scope); compute the reward from the observations / info flags.
+    The step's `reward` carries only the sparse terminal constants by default -- reward parity, sparse mode: none; pbrs mode:
+    section 20 of DESIGN.md (reward_mode="pbrs" below returns the reference's PBRS reward from a device kernel).
 
     Frame stacking (the reference's EnvironmentConfig.frame_stack + FrameStackWrapper, frame_stack_wrapper.py):
     enable_visual_frame_stacking / visual_stack_size, enable_state_stacking / state_stack_size, frame_stack_padding_type
@@ -178,6 +178,22 @@ class NppVecEnvironment:
     auto-resetting env never shows (parity of the two numbers is unpinned).  None / "none" (default): today's mask, nothing is
     launched.  set_action_masking_mode(mode) changes it between steps (the reference's annealing schedule hard -> soft -> none).
     Levels npp_reachability refuses (several exit switches) raise at the first observation with the mode on.
+
+    Reward.  reward_mode="sparse" (default): the step kernel's three constants, reward parity with the
+    reference: none.  reward_mode="pbrs": `reward` is the reference's RewardCalculator.calculate_reward (main_reward_calculator.py:
+    225-904 with RewardConfig(enable_path_waypoints=False), no goal curriculum): potential-based shaping on path distance with the
+    reference's position cache, distance and switch milestones, time penalty, completion-approach bonus, terminal rewards, times
+    0.1 -- from a device kernel behind the step, in both output modes and without auto-reset too; parity: section 20.
+    info["pbrs_components"] ([N, 6] f32, unscaled: pbrs, distance milestone, switch milestone, approach bonus, terminal, potential)
+    goes with it.  reward_params: a dict with some of death_penalty, level_completion_reward, switch_activation_reward,
+    time_penalty_per_step, pbrs_objective_weight, pbrs_gamma (defaults: a fresh RewardConfig()); set_reward_params(**kw) changes
+    them between steps (the reference's schedules are the caller's business).  Every episode start -- auto-reset, reset(),
+    restart() / restart_from_archive(), the checkpoint options of reset (a sequence replay runs with the mode off and restarts the
+    reward state on the state it ends in) -- restarts the env's reward state.  One deviation: the last step of an episode that ends by
+    TRUNCATION under auto-reset carries time penalty + switch milestone only (the reference evaluates the final position, which the
+    in-kernel reset has overwritten).  The reward launch follows the observation kernels, so obs_overlap keeps its effect.  Levels the mode refuses (those npp_reachability
+    refuses, and those on which the reference itself raises "Combined geometric path distance is infinite") raise NppError in
+    the constructor.
     """
 
     metadata = {"render_modes": []}
@@ -189,8 +205,12 @@ class NppVecEnvironment:
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
                  augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False,
-                 route_capacity=None, action_masking_mode=None):
+                 route_capacity=None, action_masking_mode=None, reward_mode="sparse", reward_params=None):
         assert output in ("torch", "numpy")
+        if reward_mode not in ("sparse", "pbrs"):
+            raise ValueError('reward_mode must be "sparse" or "pbrs", not %r' % (reward_mode,))
+        self._pbrs = reward_mode == "pbrs"
+        self._reward_params = dict(reward_params) if reward_params else {}
         if action_masking_mode not in (None, "none", "hard", "soft"):
             raise ValueError('action_masking_mode must be None, "none", "hard" or "soft", not %r' % (action_masking_mode,))
         self._mask_on = action_masking_mode in ("hard", "soft")
@@ -239,6 +259,8 @@ class NppVecEnvironment:
             outputs += ["reachability_features", "mine_sdf_features"]
         if self._mask_on:
             outputs.append("path_direction")
+        if self._pbrs:   # (the last field of the block)
+            outputs.append("reward_components")
         # same-level resets are Simulator.fast_reset in the reference's env (npp_environment.py:541-557): the default here
         self._b = NppBatch(self.num_envs, device=device, autoreset=autoreset, outputs=outputs, fast_reset=fast_reset,
                            stream=stream)
@@ -268,12 +290,14 @@ class NppVecEnvironment:
         with self._b._ctx():
             self._actions = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
         self._reset_bits = 11 if autoreset else 0
-        self._obs_names = ["game_state", "action_mask", "entity_pos", "positions", "flags"] + outputs[1:]
+        self._obs_names = ["game_state", "action_mask", "entity_pos", "positions", "flags"] + [k for k in outputs[1:] if k != "reward_components"]
         if self._minimal:   # (the packed block keeps game_state and entity_pos in front; they are neither returned nor copied)
             self._obs_names = ["action_mask", "positions", "flags", "minimal_observation"] + (["path_direction"] if self._mask_on else [])
         self._autoreset = bool(autoreset)
         if self._mask_on:
             self._b.set_action_masking(action_masking_mode)
+        if self._pbrs:
+            self._b.set_reward_mode("pbrs", self._reward_params)
         self._term_stack = None
         if self._vk or self._sk:
             self._b.set_frame_stack(self._vk, self._sk, frame_stack_padding_type)
@@ -453,11 +477,15 @@ class NppVecEnvironment:
                     mode = self._b._masking   # (action masking) the replay's inner steps have no observation: the detector
                     if mode:                  # runs once, in _produce() below, on the state the replay ends in
                         self._b.set_action_masking(0)
+                    if self._pbrs:            # (reward mode "pbrs") likewise: off around the replay, and switched on again on the
+                        self._b.set_reward_mode("sparse")   # state the replay ends in, which restarts every env's reward state
                     try:
                         flags, _rew, frames = self._b.step_many(acts, fs)
                     finally:
                         if mode:
                             self._b.set_action_masking(mode)
+                        if self._pbrs:
+                            self._b.set_reward_mode("pbrs", self._reward_params)
                     info = {"checkpoint_replay": True, "replay_frames": frames.to(torch.int64).sum(dim=0),
                             "replay_terminated": (flags & 3).ne(0).any(dim=0)}
                 else:
@@ -474,6 +502,16 @@ class NppVecEnvironment:
         if self._mask_on:
             info["path_direction"] = src["path_direction"]
         return self._with_graph(self._obs(src)), info
+
+    def set_reward_params(self, **kw):
+        """reward_mode="pbrs": new values for some of the six reward parameters (the constructor's reward_params), from the next
+        step on."""
+        if not self._pbrs:
+            raise RuntimeError('set_reward_params: this env was created with reward_mode="sparse"')
+        p = dict(self._reward_params)
+        p.update(kw)
+        self._b.set_reward_params(p)   # (raises ValueError for an unknown name)
+        self._reward_params = p
 
     def set_action_masking_mode(self, mode):
         """None / "none", "hard" or "soft" (the constructor's action_masking_mode), from the next observation on.  The first
@@ -730,6 +768,10 @@ class NppVecEnvironment:
                 self._actions.copy_(torch.as_tensor(np.asarray(actions, dtype=np.uint8)), non_blocking=True)
         b.step(self._actions, self.frame_skip, want_terminal=True)
         self._produce()
+        if self._pbrs:
+            # the reference's reward, into the block's reward.  Behind the observation kernels: the launch joins an observation
+            # overlap, which has then done its work
+            b.step_reward()
 
     def step_wait(self):
         """Results of the step enqueued by step_async: (obs, reward, terminated, truncated, info) with batch dims.
@@ -740,7 +782,7 @@ class NppVecEnvironment:
             src = self._stacked(b.out.t, with_terminal=True)
         else:
             stk = self._stacked({}, with_terminal=True)   # (copies enqueued before to_host's synchronisation)
-            src = b.to_host(self._obs_names + ["reward", "frames", "terminal_state"])
+            src = b.to_host(self._obs_names + ["reward", "frames", "terminal_state"] + (["reward_components"] if self._pbrs else []))
             src.update(stk)
         flags = src["flags"]
         info = {
@@ -757,6 +799,8 @@ class NppVecEnvironment:
         info["level_id"] = self._level_id(self.output == "numpy")
         if self._mask_on:
             info.update(self._mask_info(src, (flags & 11) != 0))
+        if self._pbrs:
+            info["pbrs_components"] = src["reward_components"]
         return self._with_graph(self._obs(src), info["level_id"]), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
@@ -821,7 +865,8 @@ class NppEnvironment:
     checkpoint_slots / archive_store(slot) / reset(options={"checkpoint": {"slots": [slot]}}): NppVecEnvironment's checkpoint archive;
     checkpoint_cells / checkpoint_seed are passed through to it.
     action_masking_mode / set_action_masking_mode(mode): NppVecEnvironment's path-direction action masking; info["path_direction"] is
-    an int, and the step that ends the episode adds info["deterministic_mask_applied_count"] / info["deterministic_mask_rate"]."""
+    an int, and the step that ends the episode adds info["deterministic_mask_applied_count"] / info["deterministic_mask_rate"].
+    reward_mode / reward_params / set_reward_params(**kw): NppVecEnvironment's reward mode "pbrs"; info["pbrs_components"] is (6,)."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
@@ -829,7 +874,7 @@ class NppEnvironment:
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
                  checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None,
-                 action_masking_mode=None):
+                 action_masking_mode=None, reward_mode="sparse", reward_params=None):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -855,7 +900,7 @@ class NppEnvironment:
                                     augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed,
                                     checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
                                     checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity,
-                                    action_masking_mode=action_masking_mode)
+                                    action_masking_mode=action_masking_mode, reward_mode=reward_mode, reward_params=reward_params)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -880,6 +925,9 @@ class NppEnvironment:
 
     def set_action_masking_mode(self, mode):
         self._v.set_action_masking_mode(mode)
+
+    def set_reward_params(self, **kw):
+        self._v.set_reward_params(**kw)
 
     def archive_store(self, slot):
         """Store the current state in slot `slot` of the checkpoint archive (checkpoint_slots > 0); returns the status (0 =
@@ -909,6 +957,8 @@ class NppEnvironment:
             if bool(term[0]) or bool(trunc[0]):
                 out_info["deterministic_mask_applied_count"] = int(info["deterministic_mask_applied_count"][0])
                 out_info["deterministic_mask_rate"] = float(info["deterministic_mask_rate"][0])
+        if "pbrs_components" in info:
+            out_info["pbrs_components"] = np.array(info["pbrs_components"][0], dtype=np.float32)
         return self._unbatch(obs), float(rew[0]), bool(term[0]), bool(trunc[0]), out_info
 
     def close(self):
