@@ -710,6 +710,67 @@ int npp_frame_augment_params_host(uint64_t seed, double p, double scale, const i
                                   int count, int32_t *out);
 int npp_frame_augment_apply_host(const uint8_t *frames, int count, int height, int width, const int32_t *params, uint8_t *out);
 
+/* Demonstration transitions from recorded replays, played as one batch: what the reference's ReplayExecutor.execute_replay
+ * (replay/replay_executor.py:304-462) and DemonstrationBuffer (replay/demonstration_buffer.py:72-209) produce one replay at a time in
+ * Python, for R replays over the handle's n_envs envs.  For a replay with input bytes in[0 .. L) and frame skip fs:
+ *   load     a level assignment plus Simulator.reset (NPlayHeadless.load_map_from_map_data); every byte is one NPlayHeadless.tick with
+ *            decode_input_to_controls' controls -- npp_tick's semantics: NO stop at a win or a death
+ *   rows     a transition AFTER tick f whenever (f + 1) % fs == 0: rows = min(L / fs, max_transitions); the trailing L % fs ticks yield
+ *            nothing, ticks behind the cap are unobservable and are not promised to run
+ *   columns  frame = f; action = map_input_to_action(in[f]) (bytes 6, 7 and above -> 0); done = 1 on the replay's last row
+ *   game_state[0:40] = get_ninja_state() after tick f; game_state[40] = the EXECUTOR's time value max(0, (L - (f + 1)) / L), an fp64
+ *            division rounded once to f32 (replay_executor.py:537-544) -- not the env's truncation value
+ *   action_mask  all ones (:595); with NPP_DEMO_MASK_ENV the mask npp_observe produces
+ *   reachability_features, spatial_context, switch_states, mine_sdf_features: DELIBERATELY the rows npp_observe / npp_reachability_ex
+ *            give for the state (the env's definitions, pinned against the reference's env), not the executor's private variants
+ * The dataset is replay-major in the CALLER's order and time-ordered inside a replay: replay r owns rows row_base[r] .. + rows[r].
+ * npp_demo_plan_host (host only): rows i32[n], row_base i64[n], the schedule order i32[n] (the replays with rows > 0 by descending
+ *   rows, ties by index; -1 padded; round q plays entries q * n_envs .. one per env), round_ticks i32[n] (max rows of the round x fs;
+ *   0 padded), counts i32[2] = scheduled replays, rounds; *rows_total.  Any output may be NULL.  NPP_ERR_INVALID for frame_skip < 1, a
+ *   negative length, n_envs < 1, max_transitions < 0: nothing is written.
+ * npp_demo_create: uploads the ragged byte table (HOST inputs u8[offsets[n]], offsets i64[n + 1] from 0) and the plan for the handle's
+ *   n_envs.  levels[r] names a level of the loaded set (the caller de-duplicates maps); out of range: NPP_ERR_INVALID.  key_flags:
+ *   NPP_DEMO_* planes to fill.  NPP_ERR_STATE while action routes, reward mode "pbrs", action masking, frame stacks, the level pool or
+ *   the observation overlap are on (the player ticks outside their bookkeeping); NPP_ERR_UNSUPPORTED with the reachability keys where
+ *   npp_reachability refuses a level.  Replaces a previous object.  npp_demo_destroy frees it; npp_load_levels drops it.
+ * npp_demo_play: plays every round and fills `out` (DEVICE pointers, one plane [rows_total][dim] per key of key_flags; the per-row
+ *   columns may be NULL).  Per round: npp_assign_levels (envs without a replay get the level of the round's first replay and zero
+ *   inputs) and a full reset -- the assignment synchronises as it always does --, then per period, on the handle's stream and without
+ *   synchronisation or host read-back: the feed kernel (ragged table -> [fs][n_envs] input rows), npp_tick, npp_observe,
+ *   npp_reachability_ex when its keys are on, and the collect kernel, which writes row row_base[r] + p of every plane for every env
+ *   whose replay has a row in period p and NOTHING for the others.  Rows of `out` that belong to no transition do not exist; the
+ *   call leaves the handle on the last round's levels.  d_flags: NPP_F_WON | NPP_F_DEAD | NPP_F_SWITCH of the row's state;
+ *   d_status: npp_reachability's status word (0 without its keys). */
+enum {
+    NPP_DEMO_GAME_STATE = 1u << 0, NPP_DEMO_ACTION_MASK = 1u << 1, NPP_DEMO_ENTITY_POSITIONS = 1u << 2, NPP_DEMO_SPATIAL_CONTEXT = 1u << 3,
+    NPP_DEMO_REACHABILITY = 1u << 4, NPP_DEMO_MINE_SDF = 1u << 5, NPP_DEMO_SWITCH_STATES = 1u << 6, NPP_DEMO_POSITIONS = 1u << 7,
+    NPP_DEMO_MASK_ENV = 1u << 16
+};
+typedef struct NppDemoOut {
+    float *d_game_state;            /* [rows,41]  */
+    int8_t *d_action_mask;          /* [rows,6]   */
+    float *d_entity_positions;      /* [rows,6]   */
+    float *d_spatial_context;       /* [rows,112] */
+    float *d_reachability_features; /* [rows,38]  */
+    float *d_mine_sdf_features;     /* [rows,3]   */
+    float *d_switch_states;         /* [rows,25]  */
+    double *d_positions;            /* [rows,6] f64: player, exit switch, exit door in pixels */
+    uint8_t *d_action;              /* [rows] 0..5 */
+    int32_t *d_frame;               /* [rows] */
+    uint8_t *d_done;                /* [rows] */
+    int32_t *d_replay;              /* [rows] the caller's replay index */
+    int32_t *d_level;               /* [rows] levels[replay] */
+    uint8_t *d_flags;               /* [rows] */
+    int32_t *d_status;              /* [rows] */
+} NppDemoOut;
+int npp_demo_plan_host(const int64_t *lengths, int n_replays, int frame_skip, int64_t max_transitions, int n_envs, int32_t *rows,
+                       int64_t *row_base, int32_t *order, int32_t *round_ticks, int32_t *counts, int64_t *rows_total);
+int npp_demo_create(npp_handle h, const uint8_t *inputs, const int64_t *offsets, const int32_t *levels, int n_replays, int frame_skip,
+                    int64_t max_transitions, unsigned key_flags);
+int npp_demo_destroy(npp_handle h);
+int npp_demo_rows(npp_handle h, int64_t *rows_total, int32_t *n_rounds, int64_t *ticks_total);
+int npp_demo_play(npp_handle h, const NppDemoOut *out);
+
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);
 

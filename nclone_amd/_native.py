@@ -45,6 +45,7 @@ EXPORTS = [
     "npp_set_action_masking", "npp_path_action_mask", "npp_path_mask_stats_view", "npp_path_direction_host",
     "npp_set_reward_mode", "npp_set_reward_params", "npp_step_reward", "npp_reward_default_params", "npp_reward_level_constants_host",
     "npp_reward_host",
+    "npp_demo_plan_host", "npp_demo_create", "npp_demo_destroy", "npp_demo_rows", "npp_demo_play",
 ]
 
 
@@ -61,6 +62,17 @@ class StepOut(C.Structure):
         ("d_positions", C.c_void_p),
         ("d_work", C.c_void_p),
     ]
+
+
+class DemoOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in (
+        "d_game_state", "d_action_mask", "d_entity_positions", "d_spatial_context", "d_reachability_features", "d_mine_sdf_features",
+        "d_switch_states", "d_positions", "d_action", "d_frame", "d_done", "d_replay", "d_level", "d_flags", "d_status")]
+
+
+DEMO_KEY_FLAGS = {"game_state": 1, "action_mask": 2, "entity_positions": 4, "spatial_context": 8, "reachability_features": 16,
+                  "mine_sdf_features": 32, "switch_states": 64, "positions": 128}
+DEMO_MASK_ENV = 1 << 16
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -189,6 +201,12 @@ def lib():
     L.npp_reward_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.npp_num_levels.argtypes = [H]
+    L.npp_demo_plan_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+    L.npp_demo_create.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_uint]
+    L.npp_demo_destroy.argtypes = [H]
+    L.npp_demo_rows.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.npp_demo_play.argtypes = [H, C.POINTER(DemoOut)]
     for name in EXPORTS:
         if name != "npp_last_error":
             getattr(L, name).restype = C.c_int

@@ -13,6 +13,7 @@
 #include "npp_archive.hpp"
 #include "npp_augment.hpp"
 #include "npp_cells.hpp"
+#include "npp_demo.hpp"
 #include "npp_graph.hpp"
 #include "npp_host.hpp"
 #include "npp_internal.hpp"
@@ -300,6 +301,27 @@ struct Reward {
     const uint16_t *frames = nullptr;
 };
 
+// demonstration player (npp_demo_create / npp_demo_play, npp_demo.hip): the ragged input table and the plan on the device, the
+// staging rows npp_tick reads and one observation row per env for the existing observation launches to write.  Dropped by
+// npp_load_levels (its level ids belong to the set).
+struct Demo {
+    bool on = false;
+    int n_replays = 0, fs = 1;
+    unsigned keys = 0;
+    DemoPlan plan;
+    std::vector<int32_t> levels;          // [n_replays]
+    DevBuf<uint8_t> inputs;               // the ragged table
+    DevBuf<int64_t> offsets, row_base;    // [n_replays + 1], [n_replays]
+    DevBuf<int32_t> rows, rep_level;      // [n_replays]
+    DevBuf<int32_t> slot;                 // [n_rounds][n] the replay of env e in round q, -1 = none
+    DevBuf<uint8_t> staging;              // [fs][n]
+    DevBuf<float> gs, epos, sc, reach, sdf, sw;   // the observation rows, one per env (allocated for the keys that are on)
+    DevBuf<int8_t> mask;
+    DevBuf<uint8_t> flags;
+    DevBuf<double> pos;
+    DevBuf<int32_t> rstatus;
+};
+
 // the launch plan (plan_geometry)
 struct Plan {
     int g = 1, wpb = 1;         // lanes per env, wavefronts per workgroup
@@ -337,6 +359,7 @@ struct npp_handle_s {
     Routes rt;
     PathMask pm;
     Reward rw;
+    Demo demo;
 };
 
 
@@ -1498,6 +1521,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     h->ls = std::move(next);
     h->ar = Archive();   // the checkpoint archive's records were laid out for the old set
     h->cells = Cells();  // (the cell index goes with the archive)
+    h->demo = Demo();    // (demonstration player) its level ids named levels of the old set
     h->rw = Reward();    // (reward mode "pbrs") the levels' constants and every env's reward state belonged to the old set: the mode is off
     h->snap = Snapshot();   // likewise
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
@@ -2359,6 +2383,178 @@ int npp_step_reward(npp_handle h, float *d_reward, float *d_components, int32_t 
     HIP_TRY(h, launch_reward(a, h->stream));
     w.flags = nullptr;   // consumed
     w.frames = nullptr;
+    return NPP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the features that keep books per step, per reset or per stream part: the player ticks outside all of them
+const char *demo_refusal(npp_handle h) {
+    if (h->rt.cap) return "action routes are on (npp_set_routes(h, 0) first)";
+    if (h->rw.mode) return "reward mode \"pbrs\" is on (npp_set_reward_mode(h, 0, NULL) first)";
+    if (h->pm.mode) return "action masking is on (npp_set_action_masking(h, 0) first)";
+    if (h->fs.vk || h->fs.sk) return "frame stacking is on (npp_set_frame_stack(h, 0, 0, 0) first)";
+    if (h->pool.on) return "the level pool is on (npp_set_level_pool(h, NULL, 0, 0) first)";
+    if (h->ov.n_cuts) return "the observation overlap is on (npp_set_obs_overlap(h, 0) first)";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int npp_demo_create(npp_handle h, const uint8_t *inputs, const int64_t *offsets, const int32_t *levels, int n_replays, int frame_skip,
+                    int64_t max_transitions, unsigned key_flags) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_demo_create: NULL handle");
+    if (n_replays <= 0 || !offsets || !levels || (key_flags & ~(unsigned)DEMO_KEYS_ALL))
+        return fail(h, NPP_ERR_INVALID, "npp_demo_create: bad arguments");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_demo_create: no levels loaded");
+    if (const char *why = demo_refusal(h)) return fail(h, NPP_ERR_STATE, std::string("npp_demo_create: ") + why);
+    if (offsets[0] != 0) return fail(h, NPP_ERR_INVALID, "npp_demo_create: offsets[0] must be 0");
+    std::vector<int64_t> len((size_t)n_replays);
+    for (int r = 0; r < n_replays; r++) {
+        len[r] = offsets[r + 1] - offsets[r];   // (a negative one is the plan's to refuse)
+        if (levels[r] < 0 || levels[r] >= (int)h->ls.levels.size())
+            return fail(h, NPP_ERR_INVALID, "npp_demo_create: replay " + std::to_string(r) + ": level id out of range");
+    }
+    const int64_t total = offsets[n_replays];
+    if (total > 0 && !inputs) return fail(h, NPP_ERR_INVALID, "npp_demo_create: inputs is NULL");
+    Demo d;   // complete or not at all
+    const char *why = nullptr;
+    if (!demo_plan(len.data(), n_replays, frame_skip, max_transitions, h->n, d.plan, &why))
+        return fail(h, NPP_ERR_INVALID, std::string("npp_demo_create: ") + why);
+    ON_DEVICE_JOINED(h);
+    if (key_flags & (DEMO_REACH | DEMO_MINE_SDF)) {   // (refuses what npp_reachability refuses, with its message)
+        if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_demo_create: exit switch / door repositioned with npp_set_entity_pos");
+        if (int rc = ensure_reach(h)) return rc;
+    }
+    const size_t N = (size_t)h->n, R = (size_t)n_replays, rounds = d.plan.round_ticks.size();
+    d.n_replays = n_replays;
+    d.fs = frame_skip;
+    d.keys = key_flags;
+    d.levels.assign(levels, levels + n_replays);
+    std::vector<int32_t> slot(std::max<size_t>(rounds, 1) * N, -1);
+    for (size_t i = 0; i < d.plan.order.size(); i++) slot[i] = d.plan.order[i];   // round i / N, env i % N
+    HIP_TRY(h, d.inputs.alloc((size_t)std::max<int64_t>(total, 1)));
+    HIP_TRY(h, d.offsets.alloc(R + 1));
+    HIP_TRY(h, d.row_base.alloc(R));
+    HIP_TRY(h, d.rows.alloc(R));
+    HIP_TRY(h, d.rep_level.alloc(R));
+    HIP_TRY(h, d.slot.alloc(slot.size()));
+    HIP_TRY(h, d.staging.alloc((size_t)frame_skip * N));
+    HIP_TRY(h, d.gs.alloc(N * NPP_GAME_STATE_DIM));
+    HIP_TRY(h, d.mask.alloc(N * NPP_ACTION_DIM));
+    HIP_TRY(h, d.epos.alloc(N * NPP_ENTITY_POS_DIM));
+    HIP_TRY(h, d.flags.alloc(N));
+    HIP_TRY(h, d.pos.alloc(N * 6));
+    if (key_flags & DEMO_SPATIAL) HIP_TRY(h, d.sc.alloc(N * NPP_SPATIAL_CONTEXT_DIM));
+    if (key_flags & DEMO_REACH) HIP_TRY(h, d.reach.alloc(N * REACH_DIM));
+    if (key_flags & DEMO_MINE_SDF) HIP_TRY(h, d.sdf.alloc(N * 3));
+    if (key_flags & (DEMO_REACH | DEMO_MINE_SDF)) HIP_TRY(h, d.rstatus.alloc(N));
+    if (key_flags & DEMO_SWITCH_STATES) HIP_TRY(h, d.sw.alloc(N * 25));
+    if (total > 0) HIP_TRY(h, hipMemcpy(d.inputs.get(), inputs, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d.offsets.get(), offsets, d.offsets.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d.row_base.get(), d.plan.row_base.data(), d.row_base.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d.rows.get(), d.plan.rows.data(), d.rows.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d.rep_level.get(), levels, d.rep_level.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d.slot.get(), slot.data(), d.slot.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // a queued play of the previous object may still read its tables
+    d.on = true;
+    h->demo = std::move(d);
+    return NPP_OK;
+}
+
+int npp_demo_destroy(npp_handle h) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_demo_destroy: NULL handle");
+    if (!h->demo.on) return NPP_OK;
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->demo = Demo();
+    return NPP_OK;
+}
+
+int npp_demo_rows(npp_handle h, int64_t *rows_total, int32_t *n_rounds, int64_t *ticks_total) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_demo_rows: NULL handle");
+    if (!h->demo.on) return fail(h, NPP_ERR_STATE, "npp_demo_rows: no demo object (npp_demo_create)");
+    const DemoPlan &p = h->demo.plan;
+    if (rows_total) *rows_total = p.rows_total;
+    if (n_rounds) *n_rounds = (int32_t)p.round_ticks.size();
+    if (ticks_total) *ticks_total = std::accumulate(p.round_ticks.begin(), p.round_ticks.end(), (int64_t)0);
+    return NPP_OK;
+}
+
+int npp_demo_play(npp_handle h, const NppDemoOut *out) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_demo_play: NULL handle");
+    Demo &d = h->demo;
+    if (!d.on) return fail(h, NPP_ERR_STATE, "npp_demo_play: no demo object (npp_demo_create)");
+    if (!out) return fail(h, NPP_ERR_INVALID, "npp_demo_play: out is NULL");
+    if (const char *why = demo_refusal(h)) return fail(h, NPP_ERR_STATE, std::string("npp_demo_play: ") + why);
+    const unsigned k = d.keys;
+    if (((k & DEMO_GAME_STATE) && !out->d_game_state) || ((k & DEMO_ACTION_MASK) && !out->d_action_mask) ||
+        ((k & DEMO_ENTITY_POS) && !out->d_entity_positions) || ((k & DEMO_SPATIAL) && !out->d_spatial_context) ||
+        ((k & DEMO_REACH) && !out->d_reachability_features) || ((k & DEMO_MINE_SDF) && !out->d_mine_sdf_features) ||
+        ((k & DEMO_SWITCH_STATES) && !out->d_switch_states) || ((k & DEMO_POSITIONS) && !out->d_positions))
+        return fail(h, NPP_ERR_INVALID, "npp_demo_play: a plane of the object's key_flags has no destination");
+    ON_DEVICE_JOINED(h);
+    const int N = h->n;
+    DemoArgs a{};
+    a.n = N;
+    a.fs = d.fs;
+    a.inputs = d.inputs.get();
+    a.offsets = d.offsets.get();
+    a.rows = d.rows.get();
+    a.row_base = d.row_base.get();
+    a.rep_level = d.rep_level.get();
+    a.staging = d.staging.get();
+    a.gs = d.gs.get(); a.epos = d.epos.get(); a.sc = d.sc.get(); a.reach = d.reach.get(); a.sdf = d.sdf.get(); a.sw = d.sw.get();
+    a.mask = d.mask.get(); a.flags = d.flags.get(); a.pos = d.pos.get(); a.rstatus = d.rstatus.get();
+    a.mask_ones = (k & DEMO_MASK_ENV) ? 0 : 1;
+    // a plane that is off has no destination, whatever the caller's struct holds
+    a.out.game_state = (k & DEMO_GAME_STATE) ? out->d_game_state : nullptr;
+    a.out.action_mask = (k & DEMO_ACTION_MASK) ? out->d_action_mask : nullptr;
+    a.out.entity_positions = (k & DEMO_ENTITY_POS) ? out->d_entity_positions : nullptr;
+    a.out.spatial_context = (k & DEMO_SPATIAL) ? out->d_spatial_context : nullptr;
+    a.out.reachability_features = (k & DEMO_REACH) ? out->d_reachability_features : nullptr;
+    a.out.mine_sdf_features = (k & DEMO_MINE_SDF) ? out->d_mine_sdf_features : nullptr;
+    a.out.switch_states = (k & DEMO_SWITCH_STATES) ? out->d_switch_states : nullptr;
+    a.out.positions = (k & DEMO_POSITIONS) ? out->d_positions : nullptr;
+    a.out.action = out->d_action; a.out.frame = out->d_frame; a.out.done = out->d_done; a.out.replay = out->d_replay;
+    a.out.level = out->d_level; a.out.flags = out->d_flags; a.out.status = out->d_status;
+    npp_step_out so;
+    std::memset(&so, 0, sizeof(so));
+    so.d_game_state = d.gs.get();
+    so.d_action_mask = d.mask.get();
+    so.d_entity_pos = d.epos.get();
+    so.d_flags = d.flags.get();
+    so.d_spatial_context = d.sc.get();
+    so.d_positions = d.pos.get();
+    std::vector<int32_t> lv((size_t)N);
+    for (size_t q = 0; q < d.plan.round_ticks.size(); q++) {
+        // the round's levels (an env without a replay plays the level of the round's first) and the reference's load: a level
+        // assignment plus Simulator.reset.  The assignment is npp_assign_levels' and synchronises as it always does; between
+        // here and the end of the round nothing does
+        const size_t first = q * (size_t)N;
+        for (int e = 0; e < N; e++) {
+            const size_t i = first + (size_t)e;
+            lv[e] = d.levels[d.plan.order[i < d.plan.order.size() ? i : first]];
+        }
+        if (int rc = npp_assign_levels(h, nullptr, lv.data(), N)) return rc;
+        if (int rc = npp_reset_ex(h, nullptr, 1)) return rc;
+        a.slot = d.slot.get() + first;
+        const int periods = d.plan.round_ticks[q] / d.fs;
+        for (int p = 0; p < periods; p++) {
+            a.period = p;
+            HIP_TRY(h, launch_demo_feed(a, h->stream));
+            if (int rc = npp_tick(h, d.staging.get(), d.fs)) return rc;
+            if (int rc = npp_observe(h, &so)) return rc;
+            if (k & (DEMO_REACH | DEMO_MINE_SDF)) {
+                if (int rc = npp_reachability_ex(h, d.reach.get(), d.sdf.get(), d.rstatus.get(), d.sw.get())) return rc;
+            } else if (k & DEMO_SWITCH_STATES) {
+                if (int rc = npp_switch_states(h, d.sw.get())) return rc;
+            }
+            HIP_TRY(h, launch_demo_collect(a, h->stream));
+        }
+    }
     return NPP_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "../../include/npp_amd.h"
 #include "npp_augment.hpp"
 #include "npp_cells.hpp"
+#include "npp_demo.hpp"
 #include "npp_minimal.hpp"
 #include "npp_pathmask.hpp"
 #include "npp_pool.hpp"
@@ -249,6 +250,23 @@ int npp_level_truncation_limit(const double *map, int64_t n, int32_t *limit, int
     if (!build_reach(map, n, R, err)) return NPP_ERR_INVALID;
     if (limit) *limit = truncation_limit_for_area(R.spawn_area);
     if (surface_area) *surface_area = R.spawn_area;
+    return NPP_OK;
+}
+
+int npp_demo_plan_host(const int64_t *lengths, int n_replays, int frame_skip, int64_t max_transitions, int n_envs, int32_t *rows,
+                       int64_t *row_base, int32_t *order, int32_t *round_ticks, int32_t *counts, int64_t *rows_total) {
+    DemoPlan p;
+    const char *why = nullptr;
+    if (!demo_plan(lengths, n_replays, frame_skip, max_transitions, n_envs, p, &why))   // a refusal writes nothing
+        return fail(nullptr, NPP_ERR_INVALID, std::string("npp_demo_plan_host: ") + why);
+    for (int r = 0; r < n_replays; r++) {
+        if (rows) rows[r] = p.rows[r];
+        if (row_base) row_base[r] = p.row_base[r];
+        if (order) order[r] = (size_t)r < p.order.size() ? p.order[r] : -1;
+        if (round_ticks) round_ticks[r] = (size_t)r < p.round_ticks.size() ? p.round_ticks[r] : 0;
+    }
+    if (counts) { counts[0] = (int32_t)p.order.size(); counts[1] = (int32_t)p.round_ticks.size(); }
+    if (rows_total) *rows_total = p.rows_total;
     return NPP_OK;
 }
 

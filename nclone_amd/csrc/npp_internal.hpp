@@ -345,6 +345,39 @@ struct RewardArgs {
 };
 hipError_t launch_reward(const RewardArgs &a, hipStream_t s);
 hipError_t launch_reward_restart(const RewardArgs &a, int init, hipStream_t s);
+// npp_demo.hip: demonstration transitions from recorded replays (see npp_demo_create in include/npp_amd.h; the plan: npp_demo.hpp)
+struct DemoOut {   // NppDemoOut of include/npp_amd.h, field by field
+    float *game_state;
+    int8_t *action_mask;
+    float *entity_positions, *spatial_context, *reachability_features, *mine_sdf_features, *switch_states;
+    double *positions;
+    uint8_t *action;
+    int32_t *frame;
+    uint8_t *done;
+    int32_t *replay, *level;
+    uint8_t *flags;
+    int32_t *status;
+};
+struct DemoArgs {
+    int n, fs, period;            // envs, frame skip, the period of the round (its ticks are period * fs ..)
+    const int32_t *slot;          // [n] the replay env e plays in this round, -1 = none
+    const uint8_t *inputs;        // the ragged input table
+    const int64_t *offsets;       // [n_replays + 1]
+    const int32_t *rows;          // [n_replays]
+    const int64_t *row_base;      // [n_replays]
+    const int32_t *rep_level;     // [n_replays]
+    uint8_t *staging;             // feed: [fs][n] input rows of the period
+    // collect: the player's observation rows, one per env (a plane that is off is null, and so is its destination)
+    const float *gs, *epos, *sc, *reach, *sdf, *sw;
+    const int8_t *mask;
+    const uint8_t *flags;
+    const double *pos;
+    const int32_t *rstatus;       // npp_reachability's status row, or null
+    int mask_ones;                // action_mask is the executor's all ones
+    DemoOut out;
+};
+hipError_t launch_demo_feed(const DemoArgs &a, hipStream_t s);
+hipError_t launch_demo_collect(const DemoArgs &a, hipStream_t s);
 hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n, const int *edge, int parts, uint8_t *phase, hipStream_t s);
 hipError_t launch_spin(long long ticks, hipStream_t s);   // a bounded idle wavefront (stream calibration)
 // order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)
