@@ -771,6 +771,52 @@ int npp_demo_destroy(npp_handle h);
 int npp_demo_rows(npp_handle h, int64_t *rows_total, int32_t *n_rounds, int64_t *ticks_total);
 int npp_demo_play(npp_handle h, const NppDemoOut *out);
 
+/* Seeding the cell index from recorded replays: what the reference's DemoCheckpointSeeder (replay/demo_checkpoint_seeder.py) does
+ * before training starts -- it plays every matching .replay file tick by tick (_extract_positions_from_demo_simple, :667-809),
+ * keeps one checkpoint per cell, the one with the highest score (extract_best_checkpoints), drops checkpoints nearer than 72 px to
+ * the exit door once the switch is on (:30, :118-153), and hands (cell, action_sequence, score) to the archive -- on the handle
+ * that owns the index, with the handle's envs as players.  Meant for the start of training.  The rule is this
+ * library's own definition; for a replay r with input bytes in[0 .. L) on level levels[r] of the loaded set:
+ *   play       as npp_demo_play with frame skip 1: per round npp_assign_levels plus a full reset, one NPlayHeadless.tick per byte
+ *              with decode_input_to_controls' controls, NO stop at a win or a death; the schedule is npp_demo_plan_host's with
+ *              frame_skip = 1 and max_transitions = max L: longest first, ties by index, round q plays entries q * n_envs .. one per env
+ *   candidate  the state after tick f (0 <= f < L) of an env that holds a replay in this round; idle envs and ticks past a replay's
+ *              end never are (a mask byte the feed kernel writes, not an accident of the state).  One npp_archive_explore per tick,
+ *              in tick order, over the candidates: eligibility, key, winner, ties and slot allocation are exactly explore's.  An
+ *              incumbent therefore wins a tie against every later tick, round or replay; inside one tick the lowest env wins
+ *   deviation  the reference appends the tick on which the ninja died before it breaks (:798-802; the cumulative-reward path
+ *              :310-312).  Here ninja states 6 to 9 are not eligible, as everywhere in the index: a dead state is no checkpoint.
+ *              The winning tick is removed on both sides by the 72 px filter.  Ticks behind the reference's break run here and
+ *              are never eligible (the ninja stays won or dead)
+ *   score      score_mode 0 "progress": (float)((double)f / (double)L), the seeder's frame_idx / max(1, total_frames) (:777-779);
+ *              1 "frames": the index's own NULL score -(float)frame (frame = f + 1), the scale of npp_archive_explore(d_score =
+ *              NULL) during training; 2 "table": d_scores[offsets[r] + f], a DEVICE f32 array ragged like the inputs (any return the
+ *              trainer computed itself); NaN = not eligible, as in explore
+ *   counts     seeding changes neither visits nor chosen: it adds cells, not visits.  n_used, cell_slot, cell_score, slot_key and
+ *              the records change as under explore
+ *   routes     with action routes on (npp_set_routes), the record of a candidate after tick f carries the route
+ *              map_input_to_action(in[0 .. f]) (bytes 6, 7 and above -> 0; the table npp_demo_play's `action` column uses):
+ *              frame_skip 1, frames f + 1, the level, the flags of the state.  Route bit 2 ("not replayable") is set from the first
+ *              byte b whose action's controls differ from decode_input_to_controls(b) -- b == 7, or b >= 8 with (b & 7) not in
+ *              {0, 6} -- and only then: npp_tick's blanket bit 2 does not reach these records.  Bit 1 when f + 1 exceeds the
+ *              capacity, as for a step.  Without routes nothing route-related is launched
+ *   afterwards the handle stays on the last round's levels, like npp_demo_play; every env's current and finished route is empty
+ * npp_archive_seed: HOST inputs u8[offsets[n]], offsets i64[n + 1] from 0, levels i32[n]; d_scores DEVICE (mode 2 only); d_counts
+ *   DEVICE i32[n_replays][4] or NULL, zeroed by the call: candidates, eligible, stored (explore status 0), archive full (status 7) per
+ *   replay -- integer atomic adds whose return value is not used.  Per tick, on the handle's stream and without synchronisation
+ *   or host read-back inside a round: the feed kernel (input byte, action, candidate mask, score, route-mismatch latch per env),
+ *   the tick, the route append when routes are on, propose (without the visit count), assign, store.  The assignment of every round
+ *   synchronises as it always does, and the call synchronises once at its end, before its tables are freed.
+ *   NPP_ERR_STATE without a cell index, for the causes npp_archive_explore names, and for the causes npp_demo_create names EXCEPT
+ *   action routes.  NPP_ERR_INVALID for a level id out of range, offsets[0] != 0, a negative length, an unknown score_mode, mode 2
+ *   without d_scores.  A refused call changes nothing: complete or not at all, as npp_demo_create is.
+ * npp_archive_seed_rows_host (host only, for tests): the per-tick rows of the rule for ONE replay -- actions u8[len], route_bits
+ *   u8[len] (2 from the first mismatching byte on; bit 1 depends on a capacity and is not included), scores f32[len] for score_mode
+ *   0 or 1 (another mode: NPP_ERR_INVALID).  Any output may be NULL. */
+int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets, const int32_t *levels, int n_replays, int score_mode,
+                     const float *d_scores, int32_t *d_counts);
+int npp_archive_seed_rows_host(const uint8_t *in, int64_t len, int score_mode, uint8_t *actions, uint8_t *route_bits, float *scores);
+
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);
 

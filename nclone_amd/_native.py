@@ -46,6 +46,7 @@ EXPORTS = [
     "npp_set_reward_mode", "npp_set_reward_params", "npp_step_reward", "npp_reward_default_params", "npp_reward_level_constants_host",
     "npp_reward_host",
     "npp_demo_plan_host", "npp_demo_create", "npp_demo_destroy", "npp_demo_rows", "npp_demo_play",
+    "npp_archive_seed", "npp_archive_seed_rows_host",
 ]
 
 
@@ -207,6 +208,8 @@ def lib():
     L.npp_demo_destroy.argtypes = [H]
     L.npp_demo_rows.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.npp_demo_play.argtypes = [H, C.POINTER(DemoOut)]
+    L.npp_archive_seed.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.npp_archive_seed_rows_host.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTS:
         if name != "npp_last_error":
             getattr(L, name).restype = C.c_int

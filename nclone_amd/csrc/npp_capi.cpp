@@ -20,6 +20,7 @@
 #include "npp_level.hpp"
 #include "npp_reach_build.hpp"
 #include "npp_reward.hpp"
+#include "npp_seed.hpp"
 
 using namespace npp;
 
@@ -1293,6 +1294,24 @@ int cells_args(npp_handle h, const char *who, CellArgs &a) {
     a.call = c.call;
     return NPP_OK;
 }
+
+// one explore (npp_archive_explore, and every tick of npp_archive_seed): propose, assign, and the winners' states by the kernel
+// that writes every record and meta row
+int explore_launch(npp_handle h, const CellArgs &a) {
+    HIP_TRY(h, launch_cells_propose(a, h->stream));
+    HIP_TRY(h, launch_cells_assign(a, h->stream));
+    const Archive &A = h->ar;
+    ArchiveArgs s = record_args(h, A.lay);
+    s.n_slots = A.n_slots;
+    s.count = h->n;
+    s.envs = h->cells.iota.get();
+    s.slots = h->cells.slot_of_env.get();
+    s.rec = A.rec.get();
+    s.meta_f64 = A.meta_f64.get();
+    s.meta_i32 = A.meta_i32.get();
+    HIP_TRY(h, launch_archive_store(s, h->stream));
+    return NPP_OK;
+}
 }  // namespace
 
 int npp_archive_cells_create(npp_handle h, int enable, uint64_t seed) {
@@ -1344,19 +1363,7 @@ int npp_archive_explore(npp_handle h, const float *d_score, const uint8_t *d_mas
     a.score = d_score;
     a.mask = d_mask;
     a.status = d_status;
-    HIP_TRY(h, launch_cells_propose(a, h->stream));
-    HIP_TRY(h, launch_cells_assign(a, h->stream));
-    const Archive &A = h->ar;   // the winners' states, by the kernel that writes every record and meta row
-    ArchiveArgs s = record_args(h, A.lay);
-    s.n_slots = A.n_slots;
-    s.count = h->n;
-    s.envs = h->cells.iota.get();
-    s.slots = h->cells.slot_of_env.get();
-    s.rec = A.rec.get();
-    s.meta_f64 = A.meta_f64.get();
-    s.meta_i32 = A.meta_i32.get();
-    HIP_TRY(h, launch_archive_store(s, h->stream));
-    return NPP_OK;
+    return explore_launch(h, a);
 }
 
 int npp_archive_select(npp_handle h, const uint8_t *d_mask, int32_t *d_slots) {
@@ -2390,14 +2397,18 @@ int npp_step_reward(npp_handle h, float *d_reward, float *d_components, int32_t 
 
 namespace {
 // the features that keep books per step, per reset or per stream part: the player ticks outside all of them
-const char *demo_refusal(npp_handle h) {
-    if (h->rt.cap) return "action routes are on (npp_set_routes(h, 0) first)";
+// (npp_archive_seed shares all but the routes, which it writes itself)
+const char *player_refusal(npp_handle h) {
     if (h->rw.mode) return "reward mode \"pbrs\" is on (npp_set_reward_mode(h, 0, NULL) first)";
     if (h->pm.mode) return "action masking is on (npp_set_action_masking(h, 0) first)";
     if (h->fs.vk || h->fs.sk) return "frame stacking is on (npp_set_frame_stack(h, 0, 0, 0) first)";
     if (h->pool.on) return "the level pool is on (npp_set_level_pool(h, NULL, 0, 0) first)";
     if (h->ov.n_cuts) return "the observation overlap is on (npp_set_obs_overlap(h, 0) first)";
     return nullptr;
+}
+const char *demo_refusal(npp_handle h) {
+    if (h->rt.cap) return "action routes are on (npp_set_routes(h, 0) first)";
+    return player_refusal(h);
 }
 }  // namespace
 
@@ -2555,6 +2566,110 @@ int npp_demo_play(npp_handle h, const NppDemoOut *out) {
             HIP_TRY(h, launch_demo_collect(a, h->stream));
         }
     }
+    return NPP_OK;
+}
+
+int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets, const int32_t *levels, int n_replays, int score_mode,
+                     const float *d_scores, int32_t *d_counts) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_archive_seed: NULL handle");
+    if (n_replays <= 0 || !offsets || !levels) return fail(h, NPP_ERR_INVALID, "npp_archive_seed: bad arguments");
+    if (score_mode != SEED_PROGRESS && score_mode != SEED_FRAMES && score_mode != SEED_TABLE)
+        return fail(h, NPP_ERR_INVALID, "npp_archive_seed: score_mode must be 0 (progress), 1 (frames) or 2 (table)");
+    if (score_mode == SEED_TABLE && !d_scores) return fail(h, NPP_ERR_INVALID, "npp_archive_seed: score_mode 2 (table) needs d_scores");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_archive_seed: no levels loaded");
+    // every refusal comes before the first change: a refused call leaves the handle and the index as they were
+    CellArgs c;
+    if (int rc = cells_args(h, "npp_archive_seed", c)) return rc;   // (no cell index; the causes npp_archive_explore names)
+    if (const char *why = player_refusal(h)) return fail(h, NPP_ERR_STATE, std::string("npp_archive_seed: ") + why);
+    if (offsets[0] != 0) return fail(h, NPP_ERR_INVALID, "npp_archive_seed: offsets[0] must be 0");
+    std::vector<int64_t> len((size_t)n_replays);
+    int64_t longest = 0;
+    for (int r = 0; r < n_replays; r++) {
+        len[r] = offsets[r + 1] - offsets[r];   // (a negative one is the plan's to refuse)
+        longest = std::max(longest, len[r]);
+        if (levels[r] < 0 || levels[r] >= (int)h->ls.levels.size())
+            return fail(h, NPP_ERR_INVALID, "npp_archive_seed: replay " + std::to_string(r) + ": level id out of range");
+    }
+    const int64_t total = offsets[n_replays];
+    if (total > 0 && !inputs) return fail(h, NPP_ERR_INVALID, "npp_archive_seed: inputs is NULL");
+    DemoPlan plan;   // npp_demo_plan_host's, with frame_skip 1 and no cap: a row per tick
+    const char *why = nullptr;
+    if (!demo_plan(len.data(), n_replays, 1, longest, h->n, plan, &why)) return fail(h, NPP_ERR_INVALID, std::string("npp_archive_seed: ") + why);
+    ON_DEVICE_JOINED(h);
+    const size_t N = (size_t)h->n, R = (size_t)n_replays, rounds = plan.round_ticks.size();
+    if (d_counts) HIP_TRY(h, hipMemsetAsync(d_counts, 0, R * 4 * sizeof(int32_t), h->stream));
+    if (rounds == 0) return NPP_OK;   // every replay is empty: nothing to play, nothing changes
+    std::vector<int32_t> slot(rounds * N, -1);
+    for (size_t i = 0; i < plan.order.size(); i++) slot[i] = plan.order[i];   // round i / N, env i % N
+    DevBuf<uint8_t> d_inputs, staging, action, mask, latch;
+    DevBuf<int64_t> d_offsets;
+    DevBuf<int32_t> d_slot, status;
+    DevBuf<float> score;
+    HIP_TRY(h, d_inputs.alloc((size_t)std::max<int64_t>(total, 1)));
+    HIP_TRY(h, d_offsets.alloc(R + 1));
+    HIP_TRY(h, d_slot.alloc(slot.size()));
+    HIP_TRY(h, staging.alloc(N));
+    HIP_TRY(h, action.alloc(N));
+    HIP_TRY(h, mask.alloc(N));
+    HIP_TRY(h, latch.alloc(N));
+    HIP_TRY(h, status.alloc(N));
+    HIP_TRY(h, score.alloc(N));
+    if (total > 0) HIP_TRY(h, hipMemcpy(d_inputs.get(), inputs, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_offsets.get(), offsets, d_offsets.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_slot.get(), slot.data(), d_slot.bytes(), hipMemcpyHostToDevice));
+    SeedArgs s{};
+    s.n = h->n;
+    s.score_mode = score_mode;
+    s.inputs = d_inputs.get();
+    s.offsets = d_offsets.get();
+    s.scores = d_scores;
+    s.staging = staging.get(); s.action = action.get(); s.mask = mask.get(); s.score = score.get(); s.latch = latch.get();
+    s.counts = d_counts;
+    s.u32 = h->env.u32.get();
+    s.ent = h->ls.ent.get();
+    s.env_level = h->env.level.get();
+    s.hdr = h->ls.hdr.get();
+    s.route_hdr = h->rt.hdr.get();
+    s.route_act = h->rt.act.get();
+    s.cap = h->rt.cap;
+    c.score = score_mode == SEED_FRAMES ? nullptr : score.get();   // (frames: the index's own NULL score, read from the state)
+    c.mask = mask.get();
+    c.status = status.get();
+    c.no_count = 1;
+    std::vector<int32_t> lv(N);
+    for (size_t q = 0; q < rounds; q++) {
+        // the round's levels and the reference's load, as npp_demo_play does them (the assignment synchronises as it always does;
+        // between here and the end of the round nothing does).  Both flip the routes: every env starts the round on an empty one
+        const size_t first = q * N;
+        for (size_t e = 0; e < N; e++) {
+            const size_t i = first + e;
+            lv[e] = levels[plan.order[i < plan.order.size() ? i : first]];
+        }
+        if (int rc = npp_assign_levels(h, nullptr, lv.data(), h->n)) return rc;
+        if (int rc = npp_reset_ex(h, nullptr, 1)) return rc;
+        s.slot = d_slot.get() + first;
+        for (int f = 0; f < plan.round_ticks[q]; f++) {
+            s.tick = f;
+            s.feed = 1;
+            s.status = f > 0 ? status.get() : nullptr;
+            HIP_TRY(h, launch_seed_feed(s, h->stream));
+            KernelArgs a = base_args(h);   // npp_tick's launch, without its "not replayable" mark on every route
+            a.inputs = staging.get();
+            a.n_ticks = 1;
+            a.mode = 1;
+            a.autoreset = 0;
+            HIP_TRY(h, launch_step(a, h->stream));
+            if (s.cap) HIP_TRY(h, launch_seed_route(s, h->stream));
+            if (int rc = explore_launch(h, c)) return rc;
+        }
+        if (d_counts && plan.round_ticks[q] > 0) {   // the verdicts of the round's last tick
+            s.feed = 0;
+            s.status = status.get();
+            HIP_TRY(h, launch_seed_feed(s, h->stream));
+        }
+    }
+    if (int rc = route_event(h, ROUTE_EV_INIT, nullptr)) return rc;   // the players' routes are nobody's episode
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the queued launches read the tables freed here
     return NPP_OK;
 }
 

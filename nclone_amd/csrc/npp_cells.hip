@@ -1,6 +1,7 @@
 // npp_cells.hip -- the cell index over the checkpoint archive (include/npp_amd.h, npp_archive_cells_create; the rule:
 // npp_cells.hpp): Go-Explore's "best state per cell" and its count-weighted pick, decided on the device.
-//   explore = propose (one thread per env: visit count + a 64-bit atomic max of (ordered score, 0xfffffffe - env) per key)
+//   explore = propose (one thread per env: visit count -- not under CellArgs::no_count, the seeding of npp_archive_seed -- + a
+//                      64-bit atomic max of (ordered score, 0xfffffffe - env) per key)
 //           + assign  (ONE workgroup walks the envs in ascending order: the winners of new keys take consecutive slots)
 //           + the archive's own store kernel over (env e -> slot_of_env[e]).
 //   select  = cdf     (one workgroup per level: inclusive prefix sums of the integer weights)
@@ -37,7 +38,8 @@ __global__ __launch_bounds__(256) void npp_cells_propose_kernel(CellArgs a) {
         if (k >= 0 && !cell_bits_nan(bits)) {
             key = level * NPP_CELLS_PER_LEVEL + k;
             st = CELL_LOST;
-            (void)__hip_atomic_fetch_add(&a.visits[key], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!a.no_count)   // (npp_archive_seed adds cells, not visits)
+                (void)__hip_atomic_fetch_add(&a.visits[key], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long prop = ((unsigned long long)cell_ordered_bits(bits) << 32) | cell_proposal_word((uint32_t)e);
             (void)__hip_atomic_fetch_max(&a.best[key], prop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }

@@ -6,6 +6,7 @@
 // The step kernels know nothing of this.
 #include <hip/hip_runtime.h>
 
+#include "npp_demo.hpp"
 #include "npp_internal.hpp"
 
 namespace npp {
@@ -62,10 +63,7 @@ __global__ __launch_bounds__(COLLECT_WAVES * WAVE) void npp_demo_collect_kernel(
     move_row(d.switch_states, a.sw, row, e, 25, lane);
     move_row(d.positions, a.pos, row, e, 6, lane);
     // the per-row columns, one lane each
-    if (lane == 0 && d.action) {
-        const uint32_t b = a.inputs[o + f];   // map_input_to_action (replay_executor.py:42-58): bytes 6, 7 and above -> NOOP
-        d.action[row] = b < 8u ? (uint8_t)((0x00415230u >> (4u * b)) & 7u) : (uint8_t)0;
-    }
+    if (lane == 0 && d.action) d.action[row] = demo_action_of_byte(a.inputs[o + f]);   // (npp_demo.hpp)
     if (lane == 1 && d.frame) d.frame[row] = (int32_t)f;
     if (lane == 2 && d.done) d.done[row] = a.period == rows - 1 ? 1 : 0;
     if (lane == 3 && d.replay) d.replay[row] = r;

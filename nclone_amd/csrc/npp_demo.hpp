@@ -7,7 +7,13 @@
 #include <numeric>
 #include <vector>
 
+#include "npp_state.hpp"   // NPP_HD
+
 namespace npp {
+
+// map_input_to_action (replay/replay_executor.py:42-58): bytes 6, 7 and above -> NOOP.  The ONE table: the collect kernel
+// (npp_demo.hip), the seed feed kernel (npp_seed.hip) and npp_archive_seed_rows_host read it here.
+NPP_HD inline uint8_t demo_action_of_byte(uint32_t b) { return b < 8u ? (uint8_t)((0x00415230u >> (4u * b)) & 7u) : (uint8_t)0; }
 
 // key_flags of npp_demo_create: the observation planes the player fills (NPP_DEMO_* of include/npp_amd.h)
 enum DemoKeys : unsigned {

@@ -14,6 +14,7 @@
 #include "npp_pool.hpp"
 #include "npp_reach_build.hpp"
 #include "npp_route.hpp"
+#include "npp_seed.hpp"
 
 using namespace npp;
 
@@ -267,6 +268,20 @@ int npp_demo_plan_host(const int64_t *lengths, int n_replays, int frame_skip, in
     }
     if (counts) { counts[0] = (int32_t)p.order.size(); counts[1] = (int32_t)p.round_ticks.size(); }
     if (rows_total) *rows_total = p.rows_total;
+    return NPP_OK;
+}
+
+int npp_archive_seed_rows_host(const uint8_t *in, int64_t len, int score_mode, uint8_t *actions, uint8_t *route_bits, float *scores) {
+    if (len < 0 || (len > 0 && !in)) return fail(nullptr, NPP_ERR_INVALID, "npp_archive_seed_rows_host: bad arguments");
+    if (score_mode != SEED_PROGRESS && score_mode != SEED_FRAMES)
+        return fail(nullptr, NPP_ERR_INVALID, "npp_archive_seed_rows_host: score_mode must be 0 (progress) or 1 (frames)");
+    bool latch = false;
+    for (int64_t f = 0; f < len; f++) {
+        latch = latch || seed_byte_mismatch(in[f]);
+        if (actions) actions[f] = demo_action_of_byte(in[f]);
+        if (route_bits) route_bits[f] = latch ? (uint8_t)ROUTE_BROKEN : (uint8_t)0;
+        if (scores) scores[f] = seed_score(score_mode, f, len);
+    }
     return NPP_OK;
 }
 

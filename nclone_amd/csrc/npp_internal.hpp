@@ -231,6 +231,7 @@ struct CellArgs {
     unsigned long long *cdf;      // [K] select: inclusive prefix sums of the weights inside each level
     uint64_t seed;
     uint32_t call;                // select call number
+    int no_count;                 // propose: 1 = leave visits alone (npp_archive_seed adds cells, not visits); 0 everywhere else
 };
 hipError_t launch_cells_propose(const CellArgs &a, hipStream_t s);
 hipError_t launch_cells_assign(const CellArgs &a, hipStream_t s);
@@ -378,6 +379,35 @@ struct DemoArgs {
 };
 hipError_t launch_demo_feed(const DemoArgs &a, hipStream_t s);
 hipError_t launch_demo_collect(const DemoArgs &a, hipStream_t s);
+// npp_seed.hip: seeding the cell index from recorded replays (see npp_archive_seed in include/npp_amd.h; the rows: npp_seed.hpp)
+struct SeedArgs {
+    int n, tick;                  // envs; the tick f of the round the rows are for
+    int score_mode;               // SeedScoreMode
+    int feed;                     // feed kernel: 1 = write the rows of tick f, 0 = only count the tick before (behind a round's last tick)
+    const int32_t *slot;          // [n] the replay env e plays in this round, -1 = none
+    const uint8_t *inputs;        // the ragged input table
+    const int64_t *offsets;       // [n_replays + 1]
+    const float *scores;          // mode 2: ragged like the inputs
+    // the rows of the coming tick, one entry per env
+    uint8_t *staging;             // the input byte npp_tick's launch reads (0 for an idle env and past a replay's end)
+    uint8_t *action;              // map_input_to_action of it
+    uint8_t *mask;                // 1 = the state after this tick is a candidate
+    float *score;
+    uint8_t *latch;               // 1 from the first byte of the round whose action does not press the byte's controls
+    // counters: the explore status of the tick before (null at a round's first tick) and where they go (null = none)
+    const int32_t *status;        // [n]
+    int32_t *counts;              // [n_replays][4] candidates | eligible | stored | full
+    // route append (routes on): the state the flags are read from and the env's route
+    const uint32_t *u32;          // [NU32][n]
+    const uint32_t *ent;          // [n_words_max][n]
+    const int32_t *env_level;     // [n]
+    const LevelHdr *hdr;          // [n_levels]
+    int32_t *route_hdr;           // [n][ROUTE_HDR_WORDS]
+    uint8_t *route_act;           // [n][2][cap]
+    int cap;
+};
+hipError_t launch_seed_feed(const SeedArgs &a, hipStream_t s);
+hipError_t launch_seed_route(const SeedArgs &a, hipStream_t s);
 hipError_t launch_phase_assign(const uint32_t *order, int blocks, int epb, int n, const int *edge, int parts, uint8_t *phase, hipStream_t s);
 hipError_t launch_spin(long long ticks, hipStream_t s);   // a bounded idle wavefront (stream calibration)
 // order <- the indices 0 .. n - 1 sorted by cost, heaviest first (128 logarithmic bins; any costs give a permutation)

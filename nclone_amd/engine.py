@@ -806,6 +806,49 @@ class NppBatch:
         self._keep_archive = (sc, m)   # the launches read them in stream order
         return st
 
+    SEED_SCORE_MODES = {"progress": 0, "frames": 1, "table": 2, 0: 0, 1: 1, 2: 2}
+
+    def archive_seed(self, inputs, offsets, levels, score_mode, scores=None, counts=False):
+        """Seed the cell index from recorded replays (include/npp_amd.h npp_archive_seed): replay r has the input
+        bytes inputs[offsets[r]:offsets[r + 1]] (u8, i64 [R + 1] from 0) and is played on level levels[r] of the loaded set with this
+        handle's envs as players; the state after every tick is offered to the index as by archive_explore, without counting
+        visits.  score_mode: "progress" (tick / length, the reference seeder's score), "frames" (archive_explore's score=None) or
+        "table" with scores: f32 [offsets[R]], ragged like the inputs (a CUDA tensor is used where it is; NaN = not eligible).
+        counts=True returns the device tensor i32 [R, 4]: candidates, eligible, stored, archive full per replay.  Leaves the handle
+        on the last round's levels with every route empty: assign_levels + reset afterwards.  Synchronises."""
+        if score_mode not in self.SEED_SCORE_MODES:
+            raise ValueError('archive_seed: score_mode must be "progress", "frames" or "table", not %r' % (score_mode,))
+        mode = self.SEED_SCORE_MODES[score_mode]
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        if off.ndim != 1 or lv.ndim != 1 or len(off) != len(lv) + 1:
+            raise ValueError("archive_seed: offsets must be [R + 1] for levels [R]")
+        inp = np.ascontiguousarray(inputs, dtype=np.uint8).ravel()
+        if len(off) and len(inp) < int(off[-1]):
+            raise ValueError("archive_seed: inputs holds %d bytes, offsets[-1] is %d" % (len(inp), int(off[-1])))
+        sc = None
+        if mode == 2:
+            if scores is None:
+                raise ValueError('archive_seed: score_mode "table" needs scores')
+            with self._ctx():
+                if isinstance(scores, torch.Tensor):
+                    if scores.dtype != torch.float32:
+                        raise TypeError("archive_seed: scores must be a float32 tensor, not %s" % scores.dtype)
+                    sc = scores.to(self.device).contiguous().view(-1)
+                else:
+                    sc = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32).ravel()).to(self.device)
+            if len(off) and sc.numel() < int(off[-1]):
+                raise ValueError("archive_seed: scores holds %d values, offsets[-1] is %d" % (sc.numel(), int(off[-1])))
+        cn = None
+        with self._ctx():
+            if counts:
+                cn = torch.zeros((len(lv), 4), dtype=torch.int32, device=self.device)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+            dev = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            nat.check(self.h, self.lib.npp_archive_seed(self.h, ptr(inp) if len(inp) else None, ptr(off), ptr(lv), len(lv), mode, dev(sc),
+                                                        dev(cn)))
+        return cn
+
     def archive_select(self, mask=None):
         """For every env (mask: u8 / bool [n], None = all) draw a slot among the occupied cells of the env's level, weighted by
         1 / sqrt(visits + chosen + 1); returns the int32 CUDA tensor [n] (-1: masked out, or the level holds no cell) -- the

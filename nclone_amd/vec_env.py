@@ -139,6 +139,8 @@ class NppVecEnvironment:
     keeps the best state per (level, switch_activated, 24 px cell) in slots the index allocates itself, and
     restart_from_archive(done_mask) restarts the masked envs from slots drawn by visit count among the cells of their own level
     (checkpoint_seed seeds the draws); archive_store is refused while the index owns the slots.
+    seed_archive_from_replays(replays) fills the index from recorded demonstrations before training starts, as the reference's
+    DemoCheckpointSeeder does, without counting visits.
 
     Action routes (the reference's `_action_sequence`, base_environment.py:186 / :517 / :1677 / :2114, and what a StateCheckpoint
     is made of, state_checkpoint.py): record_routes=True keeps, on the device, the actions that led every env from
@@ -265,6 +267,7 @@ class NppVecEnvironment:
         self._b = NppBatch(self.num_envs, device=device, autoreset=autoreset, outputs=outputs, fast_reset=fast_reset,
                            stream=stream)
         self._b.load_levels(levels)
+        self._levels, self._map_ids = levels, None   # (seed_archive_from_replays matches replays to levels by map bytes)
         if level_ids is None:
             level_ids = (np.arange(self.num_envs) // 64) % len(levels)
         self._b.assign_levels(level_ids)
@@ -274,6 +277,7 @@ class NppVecEnvironment:
             self._b.set_dynamic_truncation(True)
         else:
             self._b.set_truncation_limit(truncation_limit)
+        self._obs_overlap = bool(obs_overlap)
         if obs_overlap:   # speed knob (same bits): observation kernels of the cheap envs beside the step's expensive tail
             self._b.set_obs_overlap(int(obs_overlap))
         self._pool = level_weights is not None
@@ -667,6 +671,114 @@ class NppVecEnvironment:
         self._restart_refusal()   # (before a draw is spent)
         self.last_restart_slots = self._b.archive_select(mask)
         return self.restart(self.last_restart_slots)
+
+    def _level_of_map(self):
+        """{map bytes: level id} of the env's level set (the first level of a map that comes twice); a level whose values are
+        not bytes matches no replay."""
+        if self._map_ids is None:
+            self._map_ids = {}
+            for k, m in enumerate(self._levels):
+                if not isinstance(m, (bytes, bytearray)):
+                    a = np.asarray(m, dtype=np.float64).ravel()
+                    if not ((a >= 0) & (a <= 255) & (a == np.floor(a))).all():
+                        continue
+                    m = a.astype(np.uint8).tobytes()
+                self._map_ids.setdefault(bytes(m), k)
+        return self._map_ids
+
+    def seed_archive_from_replays(self, replays, score="progress", max_demos_per_level=10):
+        """Seed the cell index (checkpoint_cells=True) from expert demonstrations before training starts: the reference's
+        DemoCheckpointSeeder (replay/demo_checkpoint_seeder.py), played as one batch with this env's own envs as players
+        (NppBatch.archive_seed).  The state after every tick of every played replay is offered to the index as by
+        archive_explore -- best score per (level, switch_activated, 24 px cell), no checkpoint within 72 px of the exit door once the
+        switch is on -- but visits and chosen stay as they are: the seeder adds cells, not visits.  With record_routes, every seeded
+        slot carries the actions that lead to it (frame_skip 1), so restart() leaves them as the env's own route.
+
+        replays   CompactReplay objects or paths of .replay files.  Failures (success byte 0) are skipped, as load_demonstrations
+                  skips them.  A replay is matched to the env's levels by its map bytes (the reference matches by file name,
+                  demo_checkpoint_seeder.py:69-116); at most max_demos_per_level replays per level are kept, in the caller's order.
+        score     "progress": tick / length, the seeder's score without a reward calculator (:777-779); "frames": archive_explore's
+                  score=None, so that seeded cells are on the scale of cells found in training; or a list with one f32 array / tensor
+                  of length L per replay (any return the trainer computed; NaN = not eligible; entries of replays that are not
+                  played are ignored and may be None).
+        Returns {"status": i32 [R] (0 played, 1 no level of this env has the map, 2 failure skipped, 3 over max_demos_per_level),
+        "counts": i32 [R, 4] (candidates, eligible, stored, archive full per replay), "cells": n_used after the call}.
+        Reward mode "pbrs" and action masking are switched off for the seeding and on again before the closing reset.  The call ends
+        with the previous level assignment put back, whose own reset is a full reset of every env: the env is as the constructor
+        left it, and reset() must follow before the next step().  Raises NotImplementedError, naming the option, with frame
+        stacking, frame augmentation, level_weights or obs_overlap: their books advance per observation or per stream part, and a
+        reset does not put them back."""
+        self._need_cells("seed_archive_from_replays")
+        for on, name in ((self._vk, "enable_visual_frame_stacking"), (self._sk, "enable_state_stacking"), (self._aug, "enable_augmentation"),
+                         (self._pool, "level_weights"), (self._obs_overlap, "obs_overlap")):
+            if on:
+                raise NotImplementedError("seed_archive_from_replays with %s: the seeding plays outside its bookkeeping and a full "
+                                          "reset does not restore it" % name)
+        from .demos import _as_replay
+
+        b = self._b
+        reps = [_as_replay(r) for r in replays]
+        table_mode = not isinstance(score, str)
+        if table_mode and len(score) != len(reps):
+            raise ValueError("seed_archive_from_replays: score must be \"progress\", \"frames\" or one array per replay")
+        if not table_mode and score not in ("progress", "frames"):
+            raise ValueError("seed_archive_from_replays: score must be \"progress\", \"frames\" or one array per replay, not %r" % (score,))
+        status = np.zeros(len(reps), dtype=np.int32)
+        ids, per_level, played, level_ids = self._level_of_map(), {}, [], []
+        for i, r in enumerate(reps):
+            if not r.success:
+                status[i] = 2
+            elif r.map_data not in ids:
+                status[i] = 1
+            elif per_level.get(ids[r.map_data], 0) >= int(max_demos_per_level):
+                status[i] = 3
+            else:
+                per_level[ids[r.map_data]] = per_level.get(ids[r.map_data], 0) + 1
+                played.append(i)
+                level_ids.append(ids[r.map_data])
+        counts = np.zeros((len(reps), 4), dtype=np.int32)
+        if played:
+            lengths = np.array([len(reps[i].input_sequence) for i in played], dtype=np.int64)
+            offsets = np.zeros(len(played) + 1, dtype=np.int64)
+            np.cumsum(lengths, out=offsets[1:])
+            table = np.zeros(max(int(offsets[-1]), 1), dtype=np.uint8)
+            for k, i in enumerate(played):
+                table[offsets[k]:offsets[k + 1]] = np.asarray(reps[i].input_sequence, dtype=np.uint8)
+            scores = None
+            if table_mode:
+                parts = []
+                with b._ctx():
+                    for k, i in enumerate(played):
+                        s = score[i]
+                        s = s.detach().to(device=b.device, dtype=torch.float32) if isinstance(s, torch.Tensor) else \
+                            torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).to(b.device)
+                        if s.dim() != 1 or s.numel() != int(lengths[k]):
+                            raise ValueError("seed_archive_from_replays: score[%d] must hold one value per tick (%d)" % (i, int(lengths[k])))
+                        parts.append(s)
+                    scores = torch.cat(parts) if int(offsets[-1]) else torch.zeros(1, dtype=torch.float32, device=b.device)
+            before = b.env_levels()
+            mask_mode = b._masking
+            if mask_mode:
+                b.set_action_masking(0)
+            if self._pbrs:
+                b.set_reward_mode("sparse")
+            try:
+                got = b.archive_seed(table, offsets, np.array(level_ids, dtype=np.int32), "table" if table_mode else score, scores=scores,
+                                     counts=True)
+            finally:
+                if mask_mode:
+                    b.set_action_masking(mask_mode)
+                if self._pbrs:
+                    b.set_reward_mode("pbrs", self._reward_params)
+                b.assign_levels(before)   # (its own reset is Simulator.reset with fresh entities: the state the constructor left)
+            with b._ctx():
+                counts[played] = got.cpu().numpy()
+        with b._ctx():
+            cells = int(b.archive_cells()["n_used"].cpu()[0])
+            out = {"status": status, "counts": counts, "cells": cells}
+            if self.output == "torch":
+                out["status"], out["counts"] = torch.from_numpy(status).to(b.device), torch.from_numpy(counts).to(b.device)
+        return out
 
     # -- action routes (DESIGN.md 18) -------------------------------------------------------------------------------
     def _need_routes(self, what):
