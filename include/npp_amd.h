@@ -283,7 +283,9 @@ int npp_path_direction_host(const double *map, int64_t n, const double *pos, con
  * penalty x frames, distance milestones, gamma * Phi(s') - Phi(s) on the reference's potential WITH its position cache, the
  * completion-approach bonus, all times 0.1.  The rule is one function, npp_reward.hpp, compiled for the device (npp_reward.hip) and
  * for npp_reward_host; DESIGN.md 20 has the rule, the reference's quirks it reproduces, the per-env state and what the fixture
- * (tests/golden/reward.npz) pins.  Out of scope: the waypoint systems, the goal curriculum, RewardConfig's schedules (its properties
+ * (tests/golden/reward.npz) pins.  The sequential path waypoints of a fresh RewardConfig() are an option of the mode
+ * (npp_set_reward_waypoints below).  Out of scope: the goal curriculum, demo-waypoint merging, the bonuses calculate_reward has
+ * disabled (turn approach, exit direction, velocity alignment, momentum waypoints), RewardConfig's schedules (its properties
  * as functions of the success rate: set the numbers with npp_set_reward_params), the TensorBoard diagnostics.  Known deviation: a step
  * that ends by TRUNCATION under NPP_FLAG_AUTORESET gets time penalty + switch milestone only (the reference evaluates the final
  * position, which the in-kernel reset has overwritten).
@@ -328,6 +330,51 @@ int npp_reward_level_constants_host(const double *map, int64_t n, double *out, i
 int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params, const double *pos0, const double *pos, const uint8_t *flags,
                     const uint16_t *frames, int count, int end_bits, double *reward_out, double *components_out, uint8_t *kind_out,
                     int32_t *status);
+
+/* Reward mode "pbrs", sequential path waypoints: the bonus calculate_reward adds on every live step under a fresh RewardConfig()
+ * (enable_path_waypoints=True, reward_config.py:48): `_calculate_sequential_waypoint_bonus` (main_reward_calculator.py:2313-2484) with
+ * `get_waypoint_bonus` (reward_config.py:309-399), on the waypoints `extract_path_waypoints_for_level` (:1221-1398) places every
+ * progress_spacing pixels along the two optimal paths of `_compute_original_paths` (spawn -> switch, switch -> exit; find_shortest_path
+ * on the physics cost).  The rule is npp_waypoint.hpp, compiled for the device (npp_waypoint.hip, npp_waypoint_kernel, launched by
+ * npp_step_reward in front of npp_reward_kernel) and for npp_reward_host_wp; DESIGN.md 23 has the table layout, the per-env state, the
+ * reference's quirks and what tests/golden/waypoints.npz pins.  The farming penalty of the death branch is always 0 in the reference
+ * (it reads a key its observation never has) and is not computed.  Off by default: nothing is allocated or launched.
+ * npp_set_reward_waypoints(h, on, params): NPP_ERR_STATE unless reward mode 1 is on.  Switching on builds and uploads every loaded
+ *   level's table (params NULL = the defaults; progress_spacing takes effect here only), allocates the per-env state (72 bytes per env:
+ *   a 512-bit collected set, the next-expected index, the collected count) and restarts it.  NPP_ERR_UNSUPPORTED, naming the level, for
+ *   more than 512 waypoints on a level and while an entity is repositioned with npp_set_entity_pos; NPP_ERR_INVALID for a non-finite
+ *   number, a negative radius or one above 24 (the kernel walks the 3 x 3 cells of 24 px around the ninja), a spacing <= 0.  A level
+ *   without waypoints is accepted: its bonus is always 0.  npp_load_levels and npp_set_reward_mode(h, 0, ...) switch it off.
+ * npp_set_waypoint_params(h, params): radius and the two scales from the next launch on (NULL: the defaults; progress_spacing is ignored).
+ * npp_step_reward_wp: npp_step_reward plus d_wp_bonus (f32[n_envs], the UNSCALED bonus of the step) and d_wp_info (i32[n_envs][3]: the
+ *   collected sequence index or -1, the next expected index and the collected count after the step -- before the restart on a step that
+ *   ended the episode).  Either may be NULL; both are left unwritten with waypoints off.  npp_step_reward is this call with both NULL.
+ * Every episode start that restarts the reward state (above) restarts the waypoint state too; archive / snapshot records carry none.
+ * npp_reward_waypoints(h, level, out_xy, out_phase, cap, count): host copy of a level's table in sequence order (world pixels; phase 0
+ *   pre-switch, 1 post-switch); *count is the table's size, at most `cap` entries are written. */
+typedef struct NppWaypointParams {
+    double collection_radius, out_of_order_scale, progress_scale, progress_spacing;
+} NppWaypointParams;
+/* what a fresh RewardConfig() gives (recorded in tests/golden/waypoints.npz): 18, 0.3, 2.0, 12 */
+void npp_waypoint_default_params(NppWaypointParams *out);
+int npp_set_reward_waypoints(npp_handle h, int on, const NppWaypointParams *params);
+int npp_set_waypoint_params(npp_handle h, const NppWaypointParams *params);
+int npp_step_reward_wp(npp_handle h, float *d_reward /* [N] */, float *d_components /* [N,6] or NULL */, int32_t *d_status /* [N] or NULL */,
+                       float *d_wp_bonus /* [N] or NULL */, int32_t *d_wp_info /* [N,3] or NULL */);
+int npp_reward_waypoints(npp_handle h, int level, double *out_xy /* [cap][2] */, uint8_t *out_phase /* [cap] */, int cap, int32_t *count);
+/* Host-only: one level's waypoint table (out_xy f64[cap][2], out_phase u8[cap], out_node_index i32[cap], *count its size), the two node
+ * paths (path0 / path1 i32[path_cap][2] in tile-data pixels, path_len i32[2]) and the spawn, switch and exit node (nodes i32[3][2], -1 =
+ * none).  Any output but count may be NULL.  NPP_ERR_UNSUPPORTED (status 2) for a level reward mode "pbrs" or the waypoints refuse. */
+int npp_reward_waypoints_host(const double *map, int64_t n, double progress_spacing, int cap, double *out_xy, uint8_t *out_phase,
+                              int32_t *out_node_index, int32_t *count, int path_cap, int32_t *path0, int32_t *path1, int32_t *path_len,
+                              int32_t *nodes, int32_t *status);
+/* Host-only: get_waypoint_bonus(index, total, in_sequence) under the two scales */
+int npp_waypoint_bonus_host(int index, int total, int in_sequence, double progress_scale, double out_of_order_scale, double *out);
+/* Host-only: npp_reward_host with the waypoints: wp NULL = off (then exactly npp_reward_host), else the numbers.  wp_bonus_out
+ * f64[count] and wp_info_out i32[count][3] (as d_wp_bonus / d_wp_info, the bonus in fp64) may be NULL. */
+int npp_reward_host_wp(const double *map, int64_t n, const NppRewardParams *params, const NppWaypointParams *wp, const double *pos0,
+                       const double *pos, const uint8_t *flags, const uint16_t *frames, int count, int end_bits, double *reward_out,
+                       double *components_out, uint8_t *kind_out, int32_t *status, double *wp_bonus_out, int32_t *wp_info_out);
 
 /* The whole gray frame of envs [env0, env0 + count): what NPlayHeadless.render() returns in grayscale mode
  * (nplay_headless.py:144-156, nsim_renderer.py:71-134).  d_out: u8[count][600][1056]. */

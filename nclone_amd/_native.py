@@ -45,6 +45,8 @@ EXPORTS = [
     "npp_set_action_masking", "npp_path_action_mask", "npp_path_mask_stats_view", "npp_path_direction_host",
     "npp_set_reward_mode", "npp_set_reward_params", "npp_step_reward", "npp_reward_default_params", "npp_reward_level_constants_host",
     "npp_reward_host",
+    "npp_set_reward_waypoints", "npp_set_waypoint_params", "npp_step_reward_wp", "npp_reward_waypoints", "npp_waypoint_default_params",
+    "npp_reward_waypoints_host", "npp_waypoint_bonus_host", "npp_reward_host_wp",
     "npp_demo_plan_host", "npp_demo_create", "npp_demo_destroy", "npp_demo_rows", "npp_demo_play",
     "npp_archive_seed", "npp_archive_seed_rows_host",
 ]
@@ -201,6 +203,16 @@ def lib():
     L.npp_reward_level_constants_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p]
     L.npp_reward_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_set_reward_waypoints.argtypes = [H, C.c_int, C.c_void_p]
+    L.npp_set_waypoint_params.argtypes = [H, C.c_void_p]
+    L.npp_step_reward_wp.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_reward_waypoints.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    L.npp_waypoint_default_params.argtypes = [C.c_void_p]
+    L.npp_reward_waypoints_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_waypoint_bonus_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]
+    L.npp_reward_host_wp.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.npp_num_levels.argtypes = [H]
     L.npp_demo_plan_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]

@@ -87,13 +87,18 @@ class NppAsyncVecEnvironment:
     observations here): enable_augmentation is refused likewise (NppVecEnvironment(enable_augmentation=True) has it).
     No path-direction action masking: action_masking_mode other than None / "none" raises ValueError
     (NppVecEnvironment(action_masking_mode="hard") has it).
-    No reward mode "pbrs": reward_mode other than "sparse" raises ValueError (NppVecEnvironment(reward_mode="pbrs") has it).
+    No reward mode "pbrs": reward_mode other than "sparse" raises ValueError (NppVecEnvironment(reward_mode="pbrs") has it), and so
+    does reward_waypoints=True, the path waypoints of that mode.
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
-                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None, reward_mode="sparse"):
+                 enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None, reward_mode="sparse",
+                 reward_waypoints=False):
         assert output in ("torch", "numpy")
+        if reward_waypoints:
+            raise ValueError("NppAsyncVecEnvironment has no path waypoints (reward_waypoints=True): they are a term of reward mode "
+                             '"pbrs", which it does not have; NppVecEnvironment(reward_mode="pbrs", reward_waypoints=True) has them')
         if reward_mode != "sparse":
             raise ValueError("NppAsyncVecEnvironment has no reward mode %r: its sub-batches step on streams of their own and the reward "
                              'launch follows every single step; NppVecEnvironment(reward_mode="pbrs") has it' % (reward_mode,))

@@ -20,6 +20,7 @@
 #include "npp_level.hpp"
 #include "npp_reach_build.hpp"
 #include "npp_reward.hpp"
+#include "npp_waypoint.hpp"
 #include "npp_seed.hpp"
 
 using namespace npp;
@@ -300,6 +301,14 @@ struct Reward {
     size_t restore_cap = 0;
     const uint8_t *flags = nullptr;      // rows of the last npp_step not yet consumed by npp_step_reward
     const uint16_t *frames = nullptr;
+    // the sequential path waypoints (npp_set_reward_waypoints, npp_waypoint.hip): allocated when they are switched on
+    int wp_on = 0;
+    NppWaypointParams wp_params{};
+    DevBuf<WaypointHdr> wp_hdr;          // [n_levels]
+    DevBuf<unsigned char> wp_blob;
+    DevBuf<uint32_t> wp_state;           // [WP_NI][n]
+    DevBuf<double> wp_bonus;             // [n] the step's bonus, from npp_waypoint_kernel to npp_reward_kernel
+    std::vector<std::vector<uint32_t>> wp_rec;   // host copy of the levels' records (npp_reward_waypoints)
 };
 
 // demonstration player (npp_demo_create / npp_demo_play, npp_demo.hip): the ragged input table and the plan on the device, the
@@ -877,6 +886,25 @@ RewardArgs reward_args(npp_handle h) {
     a.stamp2 = w.stamp2.get();
     a.raw2 = w.raw2.get();
     a.end_bits = (h->flags & NPP_FLAG_AUTORESET) ? (int)(NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED) : 0;
+    a.wp_bonus = w.wp_on ? w.wp_bonus.get() : nullptr;
+    return a;
+}
+
+// the sequential path waypoints: what both kernels of npp_waypoint.hip read
+WaypointArgs waypoint_args(npp_handle h) {
+    const Reward &w = h->rw;
+    WaypointArgs a{};
+    a.n = h->n;
+    a.f64 = h->env.f64.get();
+    a.env_level = h->env.level.get();
+    a.wh = w.wp_hdr.get();
+    a.wblob = w.wp_blob.get();
+    a.params[0] = w.wp_params.collection_radius;
+    a.params[1] = w.wp_params.out_of_order_scale;
+    a.params[2] = w.wp_params.progress_scale;
+    a.state = w.wp_state.get();
+    a.end_bits = (h->flags & NPP_FLAG_AUTORESET) ? (int)(NPP_F_WON | NPP_F_DEAD | NPP_F_TRUNCATED) : 0;
+    a.bonus = w.wp_bonus.get();
     return a;
 }
 
@@ -891,6 +919,14 @@ int reward_restart(npp_handle h, const uint8_t *d_mask, const int32_t *d_envs = 
     a.env_status = d_status;
     a.count = count;
     HIP_TRY(h, launch_reward_restart(a, init, h->stream));
+    if (h->rw.wp_on) {   // the calculator's reset() empties the waypoint collection state too
+        WaypointArgs q = waypoint_args(h);
+        q.mask = d_mask;
+        q.envs = d_envs;
+        q.env_status = d_status;
+        q.count = count;
+        HIP_TRY(h, launch_waypoint_restart(q, h->stream));
+    }
     h->rw.flags = nullptr;
     h->rw.frames = nullptr;
     return NPP_OK;
@@ -2330,6 +2366,7 @@ int npp_set_reward_mode(npp_handle h, int mode, const NppRewardParams *params) {
     Reward &w = h->rw;
     if (!mode) {
         w.mode = 0;
+        w.wp_on = 0;
         w.flags = nullptr; w.frames = nullptr;
         return NPP_OK;
     }
@@ -2373,7 +2410,100 @@ int npp_set_reward_mode(npp_handle h, int mode, const NppRewardParams *params) {
     return reward_restart(h, nullptr, nullptr, nullptr, 0, 1);   // switching on resets all reward state
 }
 
+namespace {
+int waypoint_params_check(npp_handle h, const char *who, const NppWaypointParams &q) {
+    const double v[4] = {q.collection_radius, q.out_of_order_scale, q.progress_scale, q.progress_spacing};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(h, NPP_ERR_INVALID, std::string(who) + ": non-finite value");
+    if (!(q.collection_radius >= 0.0) || q.collection_radius > WP_MAX_RADIUS)
+        return fail(h, NPP_ERR_INVALID, std::string(who) + ": collection_radius must lie in [0, 24] (the kernel walks the 3 x 3 cells of 24 px around the ninja)");
+    if (!(q.progress_spacing > 0.0)) return fail(h, NPP_ERR_INVALID, std::string(who) + ": progress_spacing must be positive");
+    return NPP_OK;
+}
+}  // namespace
+
+int npp_set_waypoint_params(npp_handle h, const NppWaypointParams *params) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_waypoint_params: NULL handle");
+    NppWaypointParams q;
+    if (params) q = *params; else npp_waypoint_default_params(&q);
+    q.progress_spacing = h->rw.wp_hdr ? h->rw.wp_params.progress_spacing : 12.0;   // takes effect in npp_set_reward_waypoints only
+    if (int rc = waypoint_params_check(h, "npp_set_waypoint_params", q)) return rc;
+    h->rw.wp_params = q;
+    return NPP_OK;
+}
+
+int npp_set_reward_waypoints(npp_handle h, int on, const NppWaypointParams *params) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_reward_waypoints: NULL handle");
+    Reward &w = h->rw;
+    if (!w.mode) return fail(h, NPP_ERR_STATE, "npp_set_reward_waypoints: reward mode \"pbrs\" is off (npp_set_reward_mode)");
+    if (!on) {
+        w.wp_on = 0;
+        return NPP_OK;
+    }
+    if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_set_reward_waypoints: exit switch / door repositioned with npp_set_entity_pos");
+    NppWaypointParams q;
+    if (params) q = *params; else npp_waypoint_default_params(&q);
+    if (int rc = waypoint_params_check(h, "npp_set_reward_waypoints", q)) return rc;
+    ON_DEVICE_JOINED(h);
+    const size_t N = (size_t)h->n, nl = h->ls.levels.size();
+    std::vector<WaypointHdr> hdr(nl);
+    std::vector<unsigned char> blob;
+    std::vector<std::vector<uint32_t>> recs(nl);
+    ReachBuilt R;
+    for (size_t i = 0; i < nl; i++) {
+        build_reach(h->ls.levels[i], R);
+        WaypointBuilt W;
+        std::string note;
+        if (!build_waypoints(h->ls.levels[i], R, q.progress_spacing, W, note))
+            return fail(h, NPP_ERR_UNSUPPORTED, "npp_set_reward_waypoints: level " + std::to_string(i) + ": " + note + " (DESIGN.md 23)");
+        pack_waypoints(W, hdr[i], blob);
+        recs[i] = W.rec;
+    }
+    if (blob.empty()) blob.resize(4, 0);
+    // complete or not at all
+    DevBuf<WaypointHdr> d_hdr;
+    DevBuf<unsigned char> d_blob;
+    HIP_TRY(h, d_hdr.alloc(nl));
+    HIP_TRY(h, d_blob.alloc(blob.size()));
+    if (!w.wp_state) {
+        DevBuf<uint32_t> st;
+        DevBuf<double> bonus;
+        HIP_TRY(h, st.alloc((size_t)WP_NI * N));
+        HIP_TRY(h, bonus.alloc(N));
+        w.wp_state = std::move(st);
+        w.wp_bonus = std::move(bonus);
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a launch in flight may still read the old tables)
+    HIP_TRY(h, hipMemcpy(d_hdr.get(), hdr.data(), d_hdr.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_blob.get(), blob.data(), d_blob.bytes(), hipMemcpyHostToDevice));
+    w.wp_hdr = std::move(d_hdr);
+    w.wp_blob = std::move(d_blob);
+    w.wp_rec = std::move(recs);
+    w.wp_params = q;
+    w.wp_on = 1;
+    HIP_TRY(h, launch_waypoint_restart(waypoint_args(h), h->stream));   // switching on empties every env's collection state
+    return NPP_OK;
+}
+
+int npp_reward_waypoints(npp_handle h, int level, double *out_xy, uint8_t *out_phase, int cap, int32_t *count) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_reward_waypoints: NULL handle");
+    const Reward &w = h->rw;
+    if (!w.wp_on) return fail(h, NPP_ERR_STATE, "npp_reward_waypoints: the path waypoints are off (npp_set_reward_waypoints)");
+    if (level < 0 || (size_t)level >= w.wp_rec.size() || cap < 0 || !count) return fail(h, NPP_ERR_INVALID, "npp_reward_waypoints: bad level, cap or count");
+    const std::vector<uint32_t> &r = w.wp_rec[(size_t)level];
+    *count = (int32_t)r.size();
+    for (size_t i = 0; i < r.size() && i < (size_t)cap; i++) {
+        if (out_xy) { out_xy[2 * i] = (double)(r[i] & 0xfffu); out_xy[2 * i + 1] = (double)((r[i] >> 12) & 0xfffu); }
+        if (out_phase) out_phase[i] = (uint8_t)((r[i] >> 24) & 1u);
+    }
+    return NPP_OK;
+}
+
 int npp_step_reward(npp_handle h, float *d_reward, float *d_components, int32_t *d_status) {
+    return npp_step_reward_wp(h, d_reward, d_components, d_status, nullptr, nullptr);
+}
+
+int npp_step_reward_wp(npp_handle h, float *d_reward, float *d_components, int32_t *d_status, float *d_wp_bonus, int32_t *d_wp_info) {
     if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_step_reward: NULL handle");
     Reward &w = h->rw;
     if (!w.mode) return fail(h, NPP_ERR_STATE, "npp_step_reward: reward mode \"pbrs\" is off (npp_set_reward_mode)");
@@ -2381,6 +2511,13 @@ int npp_step_reward(npp_handle h, float *d_reward, float *d_components, int32_t 
     if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_step_reward: exit switch / door repositioned with npp_set_entity_pos");
     if (!w.flags || !w.frames) return fail(h, NPP_ERR_STATE, "npp_step_reward: no npp_step since the last call (one call per step)");
     ON_DEVICE_JOINED(h);
+    if (w.wp_on) {   // the step's waypoint bonus, in front of the reward launch that adds it
+        WaypointArgs q = waypoint_args(h);
+        q.flags = w.flags;
+        q.bonus_out = d_wp_bonus;
+        q.info_out = d_wp_info;
+        HIP_TRY(h, launch_waypoint(q, h->stream));
+    }
     RewardArgs a = reward_args(h);
     a.flags = w.flags;
     a.frames = w.frames;

@@ -343,9 +343,33 @@ struct RewardArgs {
     float *reward;                // [n]
     float *comps;                 // [n][6] or null
     int32_t *status;              // [n] or null
+    const double *wp_bonus;       // [n] the step's waypoint bonus (npp_waypoint_kernel), or null: waypoints off
 };
 hipError_t launch_reward(const RewardArgs &a, hipStream_t s);
 hipError_t launch_reward_restart(const RewardArgs &a, int init, hipStream_t s);
+// npp_waypoint.hip: the sequential path waypoints of reward mode "pbrs" (see npp_set_reward_waypoints in include/npp_amd.h; the rule:
+// npp_waypoint.hpp)
+struct WaypointHdr;
+struct WaypointArgs {
+    int n;
+    const double *f64;            // [NF64][n]
+    const int32_t *env_level;     // [n]
+    const WaypointHdr *wh;        // [n_levels] the levels' waypoint tables
+    const unsigned char *wblob;
+    double params[3];             // collection radius, out-of-order scale, progress scale
+    uint32_t *state;              // [WP_NI][n] the per-env collected set, next expected index, collected count
+    const uint8_t *flags;         // [n] flags row of the step
+    int end_bits;                 // flags bits after which the step kernel auto-reset the env (0 without auto-reset)
+    const uint8_t *mask;          // restart: the envs, as RewardArgs selects them
+    const int32_t *envs;
+    const int32_t *env_status;
+    int count;
+    double *bonus;                // [n] the step's unscaled bonus, read by npp_reward_kernel
+    float *bonus_out;             // [n] or null
+    int32_t *info_out;            // [n][3] or null
+};
+hipError_t launch_waypoint(const WaypointArgs &a, hipStream_t s);
+hipError_t launch_waypoint_restart(const WaypointArgs &a, hipStream_t s);
 // npp_demo.hip: demonstration transitions from recorded replays (see npp_demo_create in include/npp_amd.h; the plan: npp_demo.hpp)
 struct DemoOut {   // NppDemoOut of include/npp_amd.h, field by field
     float *game_state;

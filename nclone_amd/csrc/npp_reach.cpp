@@ -22,6 +22,7 @@
 #include "npp_reach_build.hpp"
 #include "npp_reach_features.hpp"
 #include "npp_reward.hpp"
+#include "npp_waypoint.hpp"
 
 namespace npp {
 namespace {
@@ -908,6 +909,152 @@ bool reward_level_constants(const CompiledLevel &L, const ReachBuilt &R, RewardL
     return true;
 }
 
+// ---- reward mode "pbrs", sequential path waypoints: RewardCalculator._compute_original_paths (main_reward_calculator.py:1400-1549)
+//      and PathWaypointExtractor.extract_waypoints_from_paths (path_waypoint_extractor.py:214-407)
+namespace {
+
+// find_goal_node_closest_to_start (pathfinding_utils.py:1223-1328) as _compute_original_paths calls it: ONE search radius (ninja +
+// entity), no ladder.  The graph's spatial hash has no `query` method, so the reference always takes its linear search over the
+// adjacency in dict order (:1289-1294)
+int goal_node_once(const std::vector<int> &order, int qx, int qy, int entity_r, int start) {
+    const double R = 10.0 + (double)entity_r;
+    const long sx = reach_node_x(start), sy = reach_node_y(start);
+    int best = -1, best_o = -1;
+    long bd = 0, bdo = 0;
+    for (int id : order) {
+        const long ex = reach_node_x(id) - qx, ey = reach_node_y(id) - qy, d2 = ex * ex + ey * ey;
+        if ((double)d2 > R * R) continue;
+        const long tx = reach_node_x(id) - sx, ty = reach_node_y(id) - sy, ds = tx * tx + ty * ty;
+        if (d2 <= (long)entity_r * entity_r) {
+            if (best_o < 0 || ds < bdo) { best_o = id; bdo = ds; }
+        } else if (best < 0 || ds < bd) { best = id; bd = ds; }
+    }
+    return best_o >= 0 ? best_o : best;
+}
+
+// find_shortest_path (pathfinding_utils.py:1962-2147): Dijkstra on (cost, node) tuples with the physics cost, the horizontal rule,
+// the aerial chain of the NEIGHBOUR (:2091-2099), infinite edges skipped, no mine SDF; the path rebuilt from `parents`.  It is the
+// search of geometric_path_distance above without the soft early stop.  false = unreachable.
+bool shortest_path(const AStarCtx &C, const std::vector<uint8_t> &ph, int start, int goal, std::vector<int> &path) {
+    path.clear();
+    if (start == goal) { path.push_back(start); return true; }
+    const Graph &A = *C.adj;
+    std::vector<double> dist(RNODES, 0.0);
+    std::vector<uint8_t> has(RNODES, 0), visited(RNODES, 0);
+    std::vector<int16_t> parent(RNODES, -1), grand(RNODES, -1), chain(RNODES, 0);
+    std::priority_queue<PQ> pq;
+    pq.push({0.0, reach_node_x(start), reach_node_y(start), start});
+    has[start] = 1;
+    while (!pq.empty()) {
+        const PQ cur = pq.top();
+        pq.pop();
+        if (visited[cur.id]) continue;
+        visited[cur.id] = 1;
+        if (cur.id == goal) {
+            for (int n = goal; n >= 0; n = parent[n]) path.push_back(n);
+            std::reverse(path.begin(), path.end());
+            return true;
+        }
+        if (!A.in[cur.id]) continue;   // adjacency.get(current, [])
+        const bool grounded = (ph[cur.id] & 1) != 0;
+        const int cpar = parent[cur.id], cgrand = grand[cur.id];
+        const int nchain = grounded ? 0 : chain[cur.id] + 1;
+        const int i = cur.id / RH, j = cur.id % RH;
+        for (int d = 0; d < 8; d++) {
+            if (!A.edge(cur.id, d)) continue;
+            const int nb = nid(i + DX[d], j + DY[d]);
+            if (visited[nb]) continue;
+            if (DY[d] == 0 && !(grounded && (ph[nb] & 1)) && cpar >= 0 && reach_node_y(cpar) == reach_node_y(cur.id) &&
+                reach_node_x(cpar) != reach_node_x(cur.id))
+                continue;   // _violates_horizontal_rule
+            const double cost = physics_cost(C, cur.id, nb, cpar, cgrand, nchain);
+            if (cost == INFINITY) continue;
+            const double nd = cur.d + cost;
+            if (!has[nb] || nd < dist[nb]) {
+                dist[nb] = nd; has[nb] = 1;
+                parent[nb] = (int16_t)cur.id; grand[nb] = (int16_t)cpar; chain[nb] = (int16_t)nchain;
+                pq.push({nd, reach_node_x(nb), reach_node_y(nb), nb});
+            }
+        }
+    }
+    return false;
+}
+
+}  // namespace
+
+bool build_waypoints(const CompiledLevel &L, const ReachBuilt &R, double progress_spacing, WaypointBuilt &W, std::string &note) {
+    W = WaypointBuilt();
+    const ReachHdr &H = R.hdr;
+    if (!H.sw_valid || !H.ex_valid) return true;   // no exit switch / door: no paths, no waypoints
+    Graph fin;
+    fin.in = R.in; fin.adj = R.adj;
+    std::vector<int> order;
+    for (int id = 0; id < RNODES; id++)
+        if (fin.in[id]) order.push_back(id);
+    if (order.empty()) return true;
+    std::sort(order.begin(), order.end(), [](int a, int b) { return reach_order_key(a) < reach_order_key(b); });
+    const std::vector<float> no_sdf;   // find_shortest_path hands the cost function no mine SDF (:2119)
+    const AStarCtx C{&fin, &R.phys, &R.mine_mult, &no_sdf};
+    W.nodes[0] = graph_ninja_node(fin, L.spawn_x, L.spawn_y);
+    if (W.nodes[0] < 0) return true;
+    W.nodes[1] = goal_node_once(order, H.goal_x[0] - 24, H.goal_y[0] - 24, 6, W.nodes[0]);
+    if (W.nodes[1] < 0) return true;
+    W.nodes[2] = goal_node_once(order, H.goal_x[1] - 24, H.goal_y[1] - 24, 12, W.nodes[1]);
+    if (W.nodes[2] < 0) return true;
+    if (!shortest_path(C, R.phys, W.nodes[0], W.nodes[1], W.path[0])) return true;
+    if (!shortest_path(C, R.phys, W.nodes[1], W.nodes[2], W.path[1])) { W.path[0].clear(); return true; }
+    // _extract_waypoints_from_path per phase, then the spawn filter on the pre-switch ones
+    const double swx = (double)(reach_node_x(W.path[0][0]) + 24), swy = (double)(reach_node_y(W.path[0][0]) + 24);
+    for (int phase = 0; phase < 2; phase++) {
+        const std::vector<int> &p = W.path[phase];
+        if (p.size() < 2) continue;
+        double cumulative = 0.0, last = 0.0;
+        for (size_t i = 0; i < p.size(); i++) {
+            if (i > 0) {
+                const double dx = (double)(reach_node_x(p[i]) - reach_node_x(p[i - 1])), dy = (double)(reach_node_y(p[i]) - reach_node_y(p[i - 1]));
+                cumulative += std::sqrt(dx * dx + dy * dy);
+            }
+            if (!(cumulative - last >= progress_spacing)) continue;
+            last = cumulative;
+            const int wx = reach_node_x(p[i]) + 24, wy = reach_node_y(p[i]) + 24;
+            if (phase == 0) {
+                const double dx = (double)wx - swx, dy = (double)wy - swy;
+                if (!(std::sqrt(dx * dx + dy * dy) >= WP_MIN_SPAWN_DISTANCE)) continue;
+            }
+            W.rec.push_back((uint32_t)wx | ((uint32_t)wy << 12) | ((uint32_t)phase << 24));
+            W.node_index.push_back((int)i);
+            if (phase == 0) W.n_pre++;
+        }
+    }
+    if (W.rec.size() > (size_t)WP_MAX) {
+        note = std::to_string(W.rec.size()) + " waypoints along the optimal paths (at most " + std::to_string(WP_MAX) + ")";
+        return false;
+    }
+    return true;
+}
+
+void pack_waypoints(const WaypointBuilt &W, WaypointHdr &hdr, std::vector<unsigned char> &blob) {
+    std::memset(&hdr, 0, sizeof(hdr));
+    hdr.count = (uint32_t)W.rec.size();
+    hdr.n_pre = W.n_pre;
+    auto append = [&](const void *p, size_t bytes) -> uint32_t {
+        const size_t off = (blob.size() + 3) / 4 * 4;
+        blob.resize(off + bytes);
+        if (bytes) std::memcpy(blob.data() + off, p, bytes);
+        return (uint32_t)off;
+    };
+    std::vector<uint16_t> start(WP_CELLS + 1, 0), list(W.rec.size());
+    auto cell_of = [](uint32_t r) { return (int)((r & 0xfffu) / 24u) * WP_CH + (int)(((r >> 12) & 0xfffu) / 24u); };
+    for (uint32_t r : W.rec) start[cell_of(r) + 1]++;
+    for (int c = 0; c < WP_CELLS; c++) start[c + 1] = (uint16_t)(start[c + 1] + start[c]);
+    std::vector<uint16_t> fill(start.begin(), start.end() - 1);
+    for (size_t i = 0; i < W.rec.size(); i++) list[fill[cell_of(W.rec[i])]++] = (uint16_t)i;   // ascending within a cell
+    hdr.off_rec = append(W.rec.data(), 4 * W.rec.size());
+    hdr.off_start = append(start.data(), 2 * start.size());
+    hdr.off_list = append(list.data(), 2 * list.size());
+    blob.resize((blob.size() + 3) / 4 * 4);
+}
+
 }  // namespace npp
 
 using namespace npp;
@@ -1035,9 +1182,74 @@ int npp_reward_level_constants_host(const double *map, int64_t n, double *out, i
     return ok ? NPP_OK : NPP_ERR_UNSUPPORTED;
 }
 
+void npp_waypoint_default_params(NppWaypointParams *out) {
+    if (!out) return;
+    // a fresh RewardConfig(): waypoint_collection_radius, waypoint_out_of_order_scale, waypoint_progress_scale at success rate 0,
+    // path_waypoint_progress_spacing, as tests/golden/waypoints.npz records them
+    *out = NppWaypointParams{18.0, 0.3, 2.0, 12.0};
+}
+
+int npp_waypoint_bonus_host(int index, int total, int in_sequence, double progress_scale, double out_of_order_scale, double *out) {
+    if (!out || total < 1 || index < 0 || index >= total) return NPP_ERR_INVALID;
+    *out = waypoint_bonus(index, total, in_sequence != 0, progress_scale, out_of_order_scale);
+    return NPP_OK;
+}
+
+int npp_reward_waypoints_host(const double *map, int64_t n, double progress_spacing, int cap, double *out_xy, uint8_t *out_phase,
+                              int32_t *out_node_index, int32_t *count, int path_cap, int32_t *path0, int32_t *path1, int32_t *path_len,
+                              int32_t *nodes, int32_t *status) {
+    if (!map || !count || cap < 0 || path_cap < 0 || !(progress_spacing > 0.0)) return NPP_ERR_INVALID;
+    *count = 0;
+    CompiledLevel L;
+    std::string err;
+    if (!compile_level(map, n, L, err)) return NPP_ERR_INVALID;
+    ReachBuilt R;
+    build_reach(L, R);
+    RewardLevel RL;
+    std::string note;
+    WaypointBuilt W;
+    if (!reward_level_constants(L, R, RL, note) || !build_waypoints(L, R, progress_spacing, W, note)) {
+        if (status) *status = 2;
+        return NPP_ERR_UNSUPPORTED;
+    }
+    if (status) *status = 0;
+    *count = (int32_t)W.rec.size();
+    for (size_t i = 0; i < W.rec.size() && i < (size_t)cap; i++) {
+        if (out_xy) { out_xy[2 * i] = (double)(W.rec[i] & 0xfffu); out_xy[2 * i + 1] = (double)((W.rec[i] >> 12) & 0xfffu); }
+        if (out_phase) out_phase[i] = (uint8_t)((W.rec[i] >> 24) & 1u);
+        if (out_node_index) out_node_index[i] = W.node_index[i];
+    }
+    for (int k = 0; k < 2; k++) {
+        int32_t *dst = k ? path1 : path0;
+        if (path_len) path_len[k] = (int32_t)W.path[k].size();
+        for (size_t i = 0; dst && i < W.path[k].size() && i < (size_t)path_cap; i++) {
+            dst[2 * i] = reach_node_x(W.path[k][i]);
+            dst[2 * i + 1] = reach_node_y(W.path[k][i]);
+        }
+    }
+    for (int k = 0; nodes && k < 3; k++) {
+        nodes[2 * k] = W.nodes[k] >= 0 ? reach_node_x(W.nodes[k]) : -1;
+        nodes[2 * k + 1] = W.nodes[k] >= 0 ? reach_node_y(W.nodes[k]) : -1;
+    }
+    return NPP_OK;
+}
+
 int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params, const double *pos0, const double *pos, const uint8_t *flags,
                     const uint16_t *frames, int count, int end_bits, double *reward_out, double *components_out, uint8_t *kind_out,
                     int32_t *status) {
+    return npp_reward_host_wp(map, n, params, nullptr, pos0, pos, flags, frames, count, end_bits, reward_out, components_out, kind_out, status,
+                              nullptr, nullptr);
+}
+
+int npp_reward_host_wp(const double *map, int64_t n, const NppRewardParams *params, const NppWaypointParams *wp, const double *pos0,
+                       const double *pos, const uint8_t *flags, const uint16_t *frames, int count, int end_bits, double *reward_out,
+                       double *components_out, uint8_t *kind_out, int32_t *status, double *wp_bonus_out, int32_t *wp_info_out) {
+    if (wp) {
+        const double v[4] = {wp->collection_radius, wp->out_of_order_scale, wp->progress_scale, wp->progress_spacing};
+        for (double x : v)
+            if (!std::isfinite(x)) return NPP_ERR_INVALID;
+        if (!(wp->collection_radius >= 0.0) || wp->collection_radius > WP_MAX_RADIUS || !(wp->progress_spacing > 0.0)) return NPP_ERR_INVALID;
+    }
     if (!map || !pos0 || count < 0 || (count > 0 && (!pos || !flags || !frames || !reward_out))) return NPP_ERR_INVALID;
     CompiledLevel L;
     std::string err;
@@ -1064,14 +1276,39 @@ int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params,
     std::vector<uint32_t> stamp(REACH_CELLS, 0u), stamp2(REACH_CELLS, 0u);
     std::vector<double> raw(REACH_CELLS, 0.0), raw2(REACH_CELLS, 0.0);
     ReachMiss M{stamp.data(), raw.data(), 1u}, M2{stamp2.data(), raw2.data(), 1u};
+    // the sequential path waypoints (npp_waypoint.hpp): the level's table and the calculator's per-episode collection state
+    WaypointHdr WH;
+    std::vector<unsigned char> wblob;
+    WaypointParams WP{};
+    uint32_t wbits[WP_WORDS], wnext = 0u, wcount = 0u;
+    if (wp) {
+        WaypointBuilt W;
+        if (!build_waypoints(L, R, wp->progress_spacing, W, note)) {
+            if (status) *status = 2;
+            return NPP_ERR_UNSUPPORTED;
+        }
+        pack_waypoints(W, WH, wblob);
+        WP = WaypointParams{wp->collection_radius, wp->out_of_order_scale, wp->progress_scale, wp->progress_spacing};
+        waypoint_restart(wbits, 1, wnext, wcount);
+    }
+    const WaypointTabs WT{&WH, wblob.data()};
     RewardState S;
     reward_state_init(S);
     reward_observe(T, S, pos0[0], pos0[1], 0, &M);   // the observation of the reset state
     for (int k = 0; k < count; k++) {
         const bool ended = (flags[k] & (unsigned)end_bits) != 0;
         if (ended) M.epoch++;   // clear_cache() of the path calculator (reachability_mixin.py:67-70) before the reset state is observed
+        double bonus = 0.0;
+        if (wp) {   // what npp_waypoint_kernel does in front of the reward kernel
+            WaypointOut wo{0.0, -1};
+            if (!(flags[k] & 3u) && !ended) wo = waypoint_step(WT, WP, wbits, 1, wnext, wcount, pos[2 * k], pos[2 * k + 1], (flags[k] >> 2) & 1);
+            bonus = wo.bonus;
+            if (wp_bonus_out) wp_bonus_out[k] = wo.bonus;
+            if (wp_info_out) { wp_info_out[3 * k] = wo.index; wp_info_out[3 * k + 1] = (int32_t)wnext; wp_info_out[3 * k + 2] = (int32_t)wcount; }
+            if (ended) waypoint_restart(wbits, 1, wnext, wcount);
+        }
         const RewardOut o = reward_step(T, RL, P, S, pos[2 * k], pos[2 * k + 1], ended ? 0 : (flags[k] >> 2) & 1, flags[k], frames[k], (unsigned)end_bits,
-                                        &M, &M2);
+                                        &M, &M2, wp != nullptr, bonus);
         reward_out[k] = o.reward;
         if (components_out) {
             double *c = components_out + 6 * (size_t)k;

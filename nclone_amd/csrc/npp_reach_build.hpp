@@ -40,6 +40,19 @@ void build_reach(const CompiledLevel &level, ReachBuilt &out);
 // reward mode "pbrs" (npp_reward.hpp): the level's constants; false + note when the level is refused (out.supported = 0)
 struct RewardLevel;
 bool reward_level_constants(const CompiledLevel &level, const ReachBuilt &R, RewardLevel &out, std::string &note);
+// reward mode "pbrs", sequential path waypoints (npp_waypoint.hpp): the two optimal paths of `_compute_original_paths` and the
+// waypoints extracted from them, in sequence order.  false + note when the level is refused (more than WP_MAX waypoints).
+struct WaypointHdr;
+struct WaypointBuilt {
+    std::vector<int> path[2];        // node ids: spawn -> switch, switch -> exit (empty = the reference found none)
+    int nodes[3] = {-1, -1, -1};     // spawn, switch and exit node
+    std::vector<uint32_t> rec;       // x | y << 12 | phase << 24, world pixels
+    std::vector<int> node_index;     // index of the waypoint's node in its path
+    uint32_t n_pre = 0;
+};
+bool build_waypoints(const CompiledLevel &level, const ReachBuilt &R, double progress_spacing, WaypointBuilt &out, std::string &note);
+// appends the level's waypoint table to `blob` (offsets in `hdr` from the blob start)
+void pack_waypoints(const WaypointBuilt &W, WaypointHdr &hdr, std::vector<unsigned char> &blob);
 // appends the level's tables to `blob` (offsets in `hdr` relative to hdr.base)
 void pack_reach(const ReachBuilt &R, ReachHdr &hdr, std::vector<unsigned char> &blob);
 

@@ -77,7 +77,10 @@ __global__ __launch_bounds__(256) void npp_reward_kernel(RewardArgs a) {
     const int sw_now = exit_switch_activated(exit_switch_state(a.ent_bits, N, e, obs_switch)) ? 1 : 0;
     ReachMiss M = reward_shared_dictionary(a, e, word_e);
     ReachMiss M2{a.stamp2 ? a.stamp2 + e * REACH_CELLS : nullptr, a.raw2 ? a.raw2 + e * REACH_CELLS : nullptr, 1u};
-    const RewardOut o = reward_step(T, RL, P, S, px, py, sw_now, flags, frames, (unsigned)a.end_bits, &M, &M2);
+    // (waypoints on: the bonus npp_waypoint_kernel wrote for this step; off: the rule takes the path it took without the option)
+    double wp_bonus = 0.0;
+    if (a.wp_bonus) wp_bonus = a.wp_bonus[e];
+    const RewardOut o = reward_step(T, RL, P, S, px, py, sw_now, flags, frames, (unsigned)a.end_bits, &M, &M2, a.wp_bonus != nullptr, wp_bonus);
     reward_state_store(a, N, e, S);
     a.reward[e] = (float)o.reward;
     if (a.comps) {

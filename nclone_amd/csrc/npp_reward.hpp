@@ -170,9 +170,11 @@ NPP_HD inline double reward_hop_len(double pdx, double pdy) { return (pdx != 0.0
 // state the step ended in) and which ran `frames` ticks; (px, py, sw_now) is the env's state NOW: the state the step ended in, or,
 // when (flags & end_bits) -- the step kernel auto-reset the env -- the state after that reset.  M: the dictionary shared with
 // npp_reachability, already on the env's current episode; M2: the arrays of the fallback query's own (its epoch is the state's).  Neither
-// pointer is null; a null `stamp` inside means "no dictionary" (no level of the set takes the miss branch).
+// pointer is null; a null `stamp` inside means "no dictionary" (no level of the set takes the miss branch).  wp_on: the path
+// waypoints are on and wp_bonus is the step's sequential waypoint bonus (npp_waypoint.hpp), added on a live step where the reference adds it.
 NPP_HD inline __attribute__((always_inline)) RewardOut reward_step(const ReachTabs &T, const RewardLevel &RL, const RewardParams &P, RewardState &S, double px, double py,
-                                                               int sw_now, unsigned flags, int frames, unsigned end_bits, ReachMiss *M, ReachMiss *M2) {
+                                                               int sw_now, unsigned flags, int frames, unsigned end_bits, ReachMiss *M, ReachMiss *M2,
+                                                               bool wp_on = false, double wp_bonus = 0.0) {
     const ReachHdr &H = *T.H;
     RewardOut o;
     o.reward = o.pbrs = o.dist_milestone = o.switch_milestone = o.approach = o.terminal = o.potential = 0.0;
@@ -274,6 +276,7 @@ NPP_HD inline __attribute__((always_inline)) RewardOut reward_step(const ReachTa
         if (S.bits & RW_PREV_POT) o.pbrs = P.pbrs_gamma * potential - S.prev_potential;   // :548-585
         S.prev_potential = potential; S.bits |= RW_PREV_POT;
         reward += o.pbrs;   // (the sequential waypoint bonus of :662-667 is 0.0 with waypoints off)
+        if (wp_on) reward += wp_bonus;         // waypoints on: what npp_waypoint.hpp computed for this step (:667)
         {   // distance_to_goal: the fallback of :689-715, get_distance from the integer position with its own cache key
             const ReachNear NI = reach_near(T, ipx, ipy);
             bool miss = false;

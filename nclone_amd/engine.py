@@ -76,6 +76,7 @@ _OPTIONAL = ("spatial_context", "positions", "work", "switch_states", "player_fr
 REWARD_COMPONENTS = ("pbrs", "distance_milestone", "switch_milestone", "approach_bonus", "terminal", "potential")
 REWARD_PARAMS = ("death_penalty", "level_completion_reward", "switch_activation_reward", "time_penalty_per_step", "pbrs_objective_weight",
                  "pbrs_gamma")
+WAYPOINT_PARAMS = ("collection_radius", "out_of_order_scale", "progress_scale", "progress_spacing")
 
 
 AUG_SCALES = {"light": 0.7, "medium": 1.0, "strong": 1.3}   # frame_augmentation.py:57
@@ -225,6 +226,7 @@ class NppBatch:
         self._mask_stats = None   # views of the handle's counters (path_mask_stats): the handle's own buffers, alive as long as it is
         self._reward_mode = 0     # 0 sparse, 1 pbrs (set_reward_mode)
         self._reward_pending = False   # a step() ran whose step_reward() has not: the handle holds that step's flags / frames rows
+        self._reward_waypoints = False   # set_reward_waypoints
         for k in outputs:
             if k not in _OPTIONAL:
                 raise ValueError("unknown output %r (optional outputs: %s)" % (k, ", ".join(_OPTIONAL)))
@@ -294,6 +296,7 @@ class NppBatch:
         self.n_levels = len(offsets) - 1
         self._archive_meta = self._archive_cells = self._archive_route_views = None   # (the checkpoint archive and its cell index go with the level set)
         self._reward_mode, self._reward_pending = 0, False   # (so does reward mode "pbrs": its constants are per level)
+        self._reward_waypoints = False
 
     def assign_levels(self, level_ids, env_ids=None):
         lv = np.ascontiguousarray(level_ids, dtype=np.int32)
@@ -544,6 +547,8 @@ class NppBatch:
         code = self.REWARD_MODES[mode]
         self._reward_mode = 0
         self._reward_pending = False
+        if not code:
+            self._reward_waypoints = False   # (the path waypoints go with the mode)
         nat.check(self.h, self.lib.npp_set_reward_mode(self.h, code, self._reward_params_struct(params) if code else None))
         self._reward_mode = code
 
@@ -551,11 +556,55 @@ class NppBatch:
         """New RewardConfig numbers (REWARD_PARAMS) from the next step_reward() on; None: the reference's defaults."""
         nat.check(self.h, self.lib.npp_set_reward_params(self.h, self._reward_params_struct(params)))
 
-    def step_reward(self, status_out=None):
+    def _waypoint_params_struct(self, params):
+        """None, a dict with some of WAYPOINT_PARAMS (the others keep the reference's defaults) or a sequence of all four -> the four
+        doubles of NppWaypointParams"""
+        q = (C.c_double * 4)()
+        self.lib.npp_waypoint_default_params(q)
+        if params is None:
+            return q
+        if isinstance(params, dict):
+            for k, v in params.items():
+                if k not in WAYPOINT_PARAMS:
+                    raise ValueError("unknown waypoint parameter %r (parameters: %s)" % (k, ", ".join(WAYPOINT_PARAMS)))
+                q[WAYPOINT_PARAMS.index(k)] = float(v)
+            return q
+        if len(params) != 4:
+            raise ValueError("waypoint parameters: a dict or the four values %s" % (WAYPOINT_PARAMS,))
+        for i, v in enumerate(params):
+            q[i] = float(v)
+        return q
+
+    def set_reward_waypoints(self, on, params=None):
+        """Reward mode "pbrs" only: the sequential path waypoints of a fresh RewardConfig().  On: every loaded level's
+        waypoint table is built (progress_spacing takes effect here only) and step_reward() adds the bonus of collecting the next
+        waypoint along the optimal path; every env's collection state restarts.  Raises NppError: NPP_ERR_STATE with the mode off,
+        NPP_ERR_UNSUPPORTED for a level with more than 512 waypoints, NPP_ERR_INVALID for a collection radius above 24."""
+        self._reward_waypoints = False
+        nat.check(self.h, self.lib.npp_set_reward_waypoints(self.h, 1 if on else 0, self._waypoint_params_struct(params) if on else None))
+        self._reward_waypoints = bool(on)
+
+    def set_waypoint_params(self, params=None):
+        """New collection radius and scales (WAYPOINT_PARAMS; progress_spacing is ignored) from the next step_reward() on; None: the
+        reference's defaults."""
+        nat.check(self.h, self.lib.npp_set_waypoint_params(self.h, self._waypoint_params_struct(params)))
+
+    def level_waypoints(self, level):
+        """(xy f64 [count, 2] world pixels, phase u8 [count]: 0 pre-switch, 1 post-switch) of a loaded level, in sequence order."""
+        count = C.c_int32(0)
+        nat.check(self.h, self.lib.npp_reward_waypoints(self.h, int(level), None, None, 0, C.byref(count)))
+        xy, ph = np.zeros((count.value, 2), dtype=np.float64), np.zeros(count.value, dtype=np.uint8)
+        nat.check(self.h, self.lib.npp_reward_waypoints(self.h, int(level), xy.ctypes.data_as(C.c_void_p), ph.ctypes.data_as(C.c_void_p),
+                                                        count.value, C.byref(count)))
+        return xy, ph
+
+    def step_reward(self, status_out=None, wp_bonus_out=None, wp_info_out=None):
         """One call per step(), after it: the reference's step reward of every env into the block's reward, and its unscaled
         components (REWARD_COMPONENTS) into reward_components when that output is enabled.  status_out: optional int32 CUDA tensor
         [N]: 0 the potential was evaluated in full, 1 from the position cache, 2 from it without next hop, 3 not at all (terminal
-        step).  Enqueued on the handle's stream, so to_host() after it stages the new reward."""
+        step).  With the path waypoints on: wp_bonus_out (optional float32 CUDA tensor [N]) the step's UNSCALED waypoint bonus,
+        wp_info_out (optional int32 CUDA tensor [N, 3]) the collected sequence index or -1, the next expected index, the collected
+        count; with them off neither is written.  Enqueued on the handle's stream, so to_host() after it stages the new reward."""
         if not self._reward_mode:
             raise ValueError('step_reward: reward mode "pbrs" is off (set_reward_mode("pbrs"))')
         if not self._reward_pending:
@@ -566,7 +615,14 @@ class NppBatch:
         if status_out is not None:
             assert status_out.dtype == torch.int32 and status_out.is_cuda and status_out.numel() == self.n and status_out.is_contiguous()
             st = C.c_void_p(status_out.data_ptr())
-        nat.check(self.h, self.lib.npp_step_reward(self.h, C.c_void_p(self.reward.data_ptr()), comp, st))
+        wb = wi = None
+        if wp_bonus_out is not None:
+            assert wp_bonus_out.dtype == torch.float32 and wp_bonus_out.is_cuda and wp_bonus_out.numel() == self.n and wp_bonus_out.is_contiguous()
+            wb = C.c_void_p(wp_bonus_out.data_ptr())
+        if wp_info_out is not None:
+            assert wp_info_out.dtype == torch.int32 and wp_info_out.is_cuda and wp_info_out.numel() == self.n * 3 and wp_info_out.is_contiguous()
+            wi = C.c_void_p(wp_info_out.data_ptr())
+        nat.check(self.h, self.lib.npp_step_reward_wp(self.h, C.c_void_p(self.reward.data_ptr()), comp, st, wb, wi))
         self._reward_pending = False
 
     # ---- path-direction action masking (include/npp_amd.h npp_set_action_masking) ---------------------

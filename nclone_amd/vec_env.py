@@ -196,6 +196,13 @@ class NppVecEnvironment:
     in-kernel reset has overwritten).  The reward launch follows the observation kernels, so obs_overlap keeps its effect.  Levels the mode refuses (those npp_reachability
     refuses, and those on which the reference itself raises "Combined geometric path distance is infinite") raise NppError in
     the constructor.
+    reward_waypoints=True (needs reward_mode="pbrs"): the sequential path waypoints of a fresh RewardConfig()
+    (enable_path_waypoints=True, the reference's default) -- waypoints every 12 px along the two optimal paths, a bonus for
+    collecting the next one, less out of sequence -- added to `reward` where the reference adds it.  info["waypoints"] holds the
+    step's unscaled bonus, the collected sequence index (-1: none), the next expected index and the collected count.
+    waypoint_params: a dict with some of collection_radius (at most 24), out_of_order_scale, progress_scale, progress_spacing
+    (defaults: 18, 0.3, 2.0, 12); set_waypoint_params(**kw) changes the first three between steps; level_waypoints(level) returns a
+    level's table.  Levels whose paths carry more than 512 waypoints raise NppError in the constructor.
     """
 
     metadata = {"render_modes": []}
@@ -207,12 +214,17 @@ class NppVecEnvironment:
                  frame_stack_padding_type="zero", level_weights=None, level_seed=None, enable_graph_observations=False,
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
                  augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False,
-                 route_capacity=None, action_masking_mode=None, reward_mode="sparse", reward_params=None):
+                 route_capacity=None, action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False,
+                 waypoint_params=None):
         assert output in ("torch", "numpy")
         if reward_mode not in ("sparse", "pbrs"):
             raise ValueError('reward_mode must be "sparse" or "pbrs", not %r' % (reward_mode,))
         self._pbrs = reward_mode == "pbrs"
         self._reward_params = dict(reward_params) if reward_params else {}
+        if reward_waypoints and not self._pbrs:
+            raise ValueError('reward_waypoints=True needs reward_mode="pbrs": the waypoint bonus is a term of that reward')
+        self._waypoints = bool(reward_waypoints)
+        self._waypoint_params = dict(waypoint_params) if waypoint_params else {}
         if action_masking_mode not in (None, "none", "hard", "soft"):
             raise ValueError('action_masking_mode must be None, "none", "hard" or "soft", not %r' % (action_masking_mode,))
         self._mask_on = action_masking_mode in ("hard", "soft")
@@ -300,8 +312,11 @@ class NppVecEnvironment:
         self._autoreset = bool(autoreset)
         if self._mask_on:
             self._b.set_action_masking(action_masking_mode)
-        if self._pbrs:
-            self._b.set_reward_mode("pbrs", self._reward_params)
+        if self._waypoints:
+            with self._b._ctx():
+                self._wp_bonus = torch.zeros(self.num_envs, dtype=torch.float32, device=self._b.device)
+                self._wp_info = torch.full((self.num_envs, 3), -1, dtype=torch.int32, device=self._b.device)
+        self._pbrs_on()
         self._term_stack = None
         if self._vk or self._sk:
             self._b.set_frame_stack(self._vk, self._sk, frame_stack_padding_type)
@@ -488,8 +503,7 @@ class NppVecEnvironment:
                     finally:
                         if mode:
                             self._b.set_action_masking(mode)
-                        if self._pbrs:
-                            self._b.set_reward_mode("pbrs", self._reward_params)
+                        self._pbrs_on()
                     info = {"checkpoint_replay": True, "replay_frames": frames.to(torch.int64).sum(dim=0),
                             "replay_terminated": (flags & 3).ne(0).any(dim=0)}
                 else:
@@ -506,6 +520,33 @@ class NppVecEnvironment:
         if self._mask_on:
             info["path_direction"] = src["path_direction"]
         return self._with_graph(self._obs(src)), info
+
+    def _pbrs_on(self):
+        """reward_mode="pbrs": the mode, and with reward_waypoints the path waypoints, switched on (again): every env's reward and
+        waypoint state restarts on the state it is in"""
+        if self._pbrs:
+            self._b.set_reward_mode("pbrs", self._reward_params)
+            if self._waypoints:
+                self._b.set_reward_waypoints(True, self._waypoint_params)
+
+    def set_waypoint_params(self, **kw):
+        """reward_waypoints=True: new values for collection_radius, out_of_order_scale or progress_scale (the constructor's
+        waypoint_params), from the next step on.  progress_spacing belongs to the levels' tables and cannot change here."""
+        if not self._waypoints:
+            raise RuntimeError("set_waypoint_params: this env was created with reward_waypoints=False")
+        if "progress_spacing" in kw:
+            raise ValueError("set_waypoint_params: progress_spacing is fixed when the waypoint tables are built (the constructor's waypoint_params)")
+        p = dict(self._waypoint_params)
+        p.update(kw)
+        self._b.set_waypoint_params(p)   # (raises ValueError for an unknown name)
+        self._waypoint_params = p
+
+    def level_waypoints(self, level):
+        """reward_waypoints=True: (xy f64 [count, 2] world pixels, phase u8 [count]: 0 pre-switch, 1 post-switch) of a level, in the
+        order the bonus counts them."""
+        if not self._waypoints:
+            raise RuntimeError("level_waypoints: this env was created with reward_waypoints=False")
+        return self._b.level_waypoints(level)
 
     def set_reward_params(self, **kw):
         """reward_mode="pbrs": new values for some of the six reward parameters (the constructor's reward_params), from the next
@@ -768,8 +809,7 @@ class NppVecEnvironment:
             finally:
                 if mask_mode:
                     b.set_action_masking(mask_mode)
-                if self._pbrs:
-                    b.set_reward_mode("pbrs", self._reward_params)
+                self._pbrs_on()
                 b.assign_levels(before)   # (its own reset is Simulator.reset with fresh entities: the state the constructor left)
             with b._ctx():
                 counts[played] = got.cpu().numpy()
@@ -883,7 +923,10 @@ class NppVecEnvironment:
         if self._pbrs:
             # the reference's reward, into the block's reward.  Behind the observation kernels: the launch joins an observation
             # overlap, which has then done its work
-            b.step_reward()
+            if self._waypoints:
+                b.step_reward(wp_bonus_out=self._wp_bonus, wp_info_out=self._wp_info)
+            else:
+                b.step_reward()
 
     def step_wait(self):
         """Results of the step enqueued by step_async: (obs, reward, terminated, truncated, info) with batch dims.
@@ -913,6 +956,12 @@ class NppVecEnvironment:
             info.update(self._mask_info(src, (flags & 11) != 0))
         if self._pbrs:
             info["pbrs_components"] = src["reward_components"]
+        if self._waypoints:   # the step's unscaled bonus, the collected sequence index or -1, the next expected index, the collected count
+            wb, wi = self._wp_bonus, self._wp_info
+            if self.output == "numpy":
+                with b._ctx():   # (to_host above has synchronised the stream the reward launches ran on)
+                    wb, wi = wb.cpu().numpy(), wi.cpu().numpy()
+            info["waypoints"] = {"bonus": wb, "index": wi[:, 0], "next_expected": wi[:, 1], "collected": wi[:, 2]}
         return self._with_graph(self._obs(src), info["level_id"]), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
@@ -986,7 +1035,7 @@ class NppEnvironment:
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
                  checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None,
-                 action_masking_mode=None, reward_mode="sparse", reward_params=None):
+                 action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False, waypoint_params=None):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -1012,7 +1061,8 @@ class NppEnvironment:
                                     augmentation_intensity=augmentation_intensity, augmentation_seed=augmentation_seed,
                                     checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
                                     checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity,
-                                    action_masking_mode=action_masking_mode, reward_mode=reward_mode, reward_params=reward_params)
+                                    action_masking_mode=action_masking_mode, reward_mode=reward_mode, reward_params=reward_params,
+                                    reward_waypoints=reward_waypoints, waypoint_params=waypoint_params)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -1040,6 +1090,12 @@ class NppEnvironment:
 
     def set_reward_params(self, **kw):
         self._v.set_reward_params(**kw)
+
+    def set_waypoint_params(self, **kw):
+        self._v.set_waypoint_params(**kw)
+
+    def level_waypoints(self, level):
+        return self._v.level_waypoints(level)
 
     def archive_store(self, slot):
         """Store the current state in slot `slot` of the checkpoint archive (checkpoint_slots > 0); returns the status (0 =
@@ -1071,6 +1127,10 @@ class NppEnvironment:
                 out_info["deterministic_mask_rate"] = float(info["deterministic_mask_rate"][0])
         if "pbrs_components" in info:
             out_info["pbrs_components"] = np.array(info["pbrs_components"][0], dtype=np.float32)
+        if "waypoints" in info:
+            w = info["waypoints"]
+            out_info["waypoints"] = {"bonus": float(w["bonus"][0]), "index": int(w["index"][0]), "next_expected": int(w["next_expected"][0]),
+                                     "collected": int(w["collected"][0])}
         return self._unbatch(obs), float(rew[0]), bool(term[0]), bool(trunc[0]), out_info
 
     def close(self):
