@@ -626,6 +626,68 @@ int npp_archive_route_view(npp_handle h, const uint32_t **d_records, int64_t *hd
 int npp_route_apply_host(int32_t *hdr, uint8_t *actions, int capacity, int autoreset, const int32_t *events, int count,
                          const uint8_t *restore_bytes);
 
+/* Episode statistics: what a trainer reads at every episode end, kept on the device.  The reference puts it into `info`
+ * (base_environment.py:1163-1242): "r" = current_ep_reward (created at :156, += reward at :676, zeroed at npp_environment.py:587
+ * and :688), "l" = sim.frame, "is_success" / "switch_activated" / "switch_activation_frame" (:546-552), "level_id",
+ * "from_checkpoint", and episode_pbrs_metrics' pbrs_total and terminal_reward (main_reward_calculator.py:2825-2914).  Off by
+ * default: nothing is allocated, nothing is launched.  The rule (csrc/npp_episode.hpp):
+ *   record    per env NPP_EP_NI i32 words and NPP_EP_ND doubles, as planes i32[NPP_EP_NI][n_envs] / f64[NPP_EP_ND][n_envs]: the
+ *             CURRENT episode (words NPP_EP_STEPS .. NPP_EP_BITS, doubles NPP_EP_RET, NPP_EP_COMP + 0..5), the FINISHED episode (the
+ *             same at + NPP_EP_FIN / + NPP_EP_DFIN), the flags byte of its ending step (NPP_EP_FIN_FLAGS) and the u32 count of
+ *             episodes the env finished (NPP_EP_N_FINISHED).  switch_step: the 1-based step at which NPP_F_SWITCH was first seen, 0 =
+ *             never; switch_frames: the episode's frames after that step.  bits: 1 closed (ended without auto-reset), 2 begun by a
+ *             restore, 4 npp_tick ran inside it.
+ *   step row  flags f, frames x, reward r, optionally six components: nothing when x == 0 or the episode is closed; otherwise the
+ *             episode takes the env's level if this is its first row, steps += 1, frames += x, ret += (double)r, comp[k] +=
+ *             (double)c[k], the switch latch; and with WON, DEAD or TRUNCATED in f the episode is copied to FINISHED, n_finished += 1,
+ *             its deltas go to the table, and the current episode restarts empty (NPP_FLAG_AUTORESET) or is closed (without: a
+ *             truncated env keeps stepping and is not counted twice).
+ *   table     u64[n_levels][16], columns NPP_EPC_*: episodes | won | dead | truncated | dead by mine | dead by impact | switch
+ *             activated | steps | frames | frames of won episodes | return_fix = the two's-complement sum of
+ *             floor(clamp(ret, +-2^42) * 2^20 + 0.5) | restored | abandoned | 0 0 0.  An episode begun by a restore adds 1 to `restored`
+ *             and nothing else.  Integer atomics only: the table does not depend on the order in which envs end.
+ *   events    RESET -- npp_reset / npp_reset_ex (masked envs), npp_assign_levels (listed envs), npp_draw_levels (envs that changed
+ *             level): a current episode with steps that is neither closed nor begun by a restore adds 1 to `abandoned` of its
+ *             level, then the current episode is empty on the env's level.  RESTORE -- npp_restore (masked envs),
+ *             npp_archive_restore (entries of status 0): the same, and the new episode carries bit 2.  npp_tick sets bit 4.
+ *             npp_demo_play and npp_archive_seed empty every current episode without counting.  FINISHED and n_finished stay.
+ *             npp_load_levels switches the feature off (the table has a row per level).  With the level pool on, npp_step has
+ *             already drawn the next level when the ending row is accumulated: the ended episode is charged to the level it was
+ *             played on and the new one starts on the drawn level.
+ * npp_set_episode_stats(h, enable): allocates the planes and the table for the loaded levels (NPP_ERR_STATE without), zeroes them
+ *   and sets both levels of every record to -1; 0 frees them.  A failed allocation is NPP_ERR_HIP and leaves the previous state.
+ * npp_episode_accumulate: n_steps rows [n_steps][n_envs] of flags, frames and reward, and, when not NULL, components
+ *   f32[n_steps][n_envs][6] (8-byte aligned; NULL: the component doubles are neither read nor written).  Call it once per npp_step /
+ *   npp_step_many, after npp_step_reward when the reward comes from there.  Every row is passed in: the handle remembers no
+ *   pointer.  It joins a split step (npp_set_obs_overlap) first.  d_ended (u8[n_envs] or NULL): 1 where this call finished an episode.
+ * npp_episode_restart: the RESET (from_restore == 0) or RESTORE event for the envs of a device mask (NULL = all), for callers
+ *   that start episodes by other means.
+ * npp_episode_view: the plane bases and the table, valid until the next npp_set_episode_stats / npp_load_levels, rewritten in
+ *   stream order.  npp_episode_table_reset zeroes the table.
+ * Each of these is NPP_ERR_INVALID on a NULL handle and NPP_ERR_STATE while the feature is off.
+ * npp_episode_apply_host: the same rule without a GPU or a handle, for tests, on ONE env: rec_i32[NPP_EP_NI], rec_f64[NPP_EP_ND] and
+ *   table u64[n_levels][16] (NULL with n_levels == 0) are updated in place by `count` events of 8 words each: {0, flags, frames,
+ *   level_now, has_components} a step row whose reward and six components are rows[8 * i + 0 .. 6]; {1, level_now} RESET;
+ *   {2, level_now} RESTORE; {3} npp_tick; {4} INIT; {5, level_now} the players' clearing.  *ended (may be NULL): 1 when a row
+ *   finished an episode.  NPP_ERR_INVALID for a NULL record, flags outside 0..255, frames outside 0..65535 or an unknown kind. */
+enum {
+    NPP_EP_STEPS = 0, NPP_EP_FRAMES = 1, NPP_EP_SWITCH_STEP = 2, NPP_EP_SWITCH_FRAMES = 3, NPP_EP_LEVEL = 4, NPP_EP_BITS = 5,
+    NPP_EP_FIN = 6, NPP_EP_FIN_FLAGS = 12, NPP_EP_N_FINISHED = 13, NPP_EP_NI = 14,
+    NPP_EP_RET = 0, NPP_EP_COMP = 1, NPP_EP_DFIN = 7, NPP_EP_ND = 14
+};
+enum {
+    NPP_EPC_EPISODES = 0, NPP_EPC_WON, NPP_EPC_DEAD, NPP_EPC_TRUNCATED, NPP_EPC_DEAD_MINE, NPP_EPC_DEAD_IMPACT, NPP_EPC_SWITCH,
+    NPP_EPC_STEPS, NPP_EPC_FRAMES, NPP_EPC_WON_FRAMES, NPP_EPC_RETURN_FIX, NPP_EPC_RESTORED, NPP_EPC_ABANDONED, NPP_EP_COLS = 16
+};
+int npp_set_episode_stats(npp_handle h, int enable);
+int npp_episode_accumulate(npp_handle h, const uint8_t *d_flags, const uint16_t *d_frames, const float *d_reward,
+                           const float *d_components /* or NULL */, int n_steps, uint8_t *d_ended /* [N] or NULL */);
+int npp_episode_restart(npp_handle h, const uint8_t *d_mask /* NULL = all */, int from_restore);
+int npp_episode_view(npp_handle h, const int32_t **d_i32, const double **d_f64, const uint64_t **d_table);
+int npp_episode_table_reset(npp_handle h);
+int npp_episode_apply_host(int32_t *rec_i32, double *rec_f64, uint64_t *table, int n_levels, int autoreset, const int32_t *events,
+                           const float *rows, int count, uint8_t *ended);
+
 /* Launch geometry: lanes_per_env wavefront lanes cooperate on one environment (power of two, 1..64; 0 = choose from
  * n_envs so that the grid fills the chip), waves_per_block wavefronts share one LDS copy of a level (1..4, 0 = auto).
  * Results are bit-identical for every geometry; only speed changes. */

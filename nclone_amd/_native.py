@@ -49,6 +49,8 @@ EXPORTS = [
     "npp_reward_waypoints_host", "npp_waypoint_bonus_host", "npp_reward_host_wp",
     "npp_demo_plan_host", "npp_demo_create", "npp_demo_destroy", "npp_demo_rows", "npp_demo_play",
     "npp_archive_seed", "npp_archive_seed_rows_host",
+    "npp_set_episode_stats", "npp_episode_accumulate", "npp_episode_restart", "npp_episode_view", "npp_episode_table_reset",
+    "npp_episode_apply_host",
 ]
 
 
@@ -222,6 +224,12 @@ def lib():
     L.npp_demo_play.argtypes = [H, C.POINTER(DemoOut)]
     L.npp_archive_seed.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.npp_archive_seed_rows_host.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_set_episode_stats.argtypes = [H, C.c_int]
+    L.npp_episode_accumulate.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_episode_restart.argtypes = [H, C.c_void_p, C.c_int]
+    L.npp_episode_view.argtypes = [H] + [C.POINTER(C.c_void_p)] * 3
+    L.npp_episode_table_reset.argtypes = [H]
+    L.npp_episode_apply_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     for name in EXPORTS:
         if name != "npp_last_error":
             getattr(L, name).restype = C.c_int

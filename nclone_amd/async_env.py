@@ -89,16 +89,20 @@ class NppAsyncVecEnvironment:
     (NppVecEnvironment(action_masking_mode="hard") has it).
     No reward mode "pbrs": reward_mode other than "sparse" raises ValueError (NppVecEnvironment(reward_mode="pbrs") has it), and so
     does reward_waypoints=True, the path waypoints of that mode.
+    No episode statistics: episode_stats=True raises ValueError (NppVecEnvironment(episode_stats=True) has them).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
                  enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None, reward_mode="sparse",
-                 reward_waypoints=False):
+                 reward_waypoints=False, episode_stats=False):
         assert output in ("torch", "numpy")
         if reward_waypoints:
             raise ValueError("NppAsyncVecEnvironment has no path waypoints (reward_waypoints=True): they are a term of reward mode "
                              '"pbrs", which it does not have; NppVecEnvironment(reward_mode="pbrs", reward_waypoints=True) has them')
+        if episode_stats:
+            raise ValueError("NppAsyncVecEnvironment has no episode statistics (episode_stats=True): the records and the level table "
+                             "belong to one handle and its sub-batches are handles of their own; NppVecEnvironment(episode_stats=True) has them")
         if reward_mode != "sparse":
             raise ValueError("NppAsyncVecEnvironment has no reward mode %r: its sub-batches step on streams of their own and the reward "
                              'launch follows every single step; NppVecEnvironment(reward_mode="pbrs") has it' % (reward_mode,))

@@ -14,6 +14,7 @@
 #include "npp_augment.hpp"
 #include "npp_cells.hpp"
 #include "npp_demo.hpp"
+#include "npp_episode.hpp"
 #include "npp_graph.hpp"
 #include "npp_host.hpp"
 #include "npp_internal.hpp"
@@ -274,6 +275,18 @@ struct Routes {
     int rows = 0;
 };
 
+// episode statistics (npp_set_episode_stats / npp_episode_accumulate, npp_episode.hip): per-env record planes and the per-level table.
+// Allocated when switched on; dropped by npp_load_levels (the table has a row per level of the set).
+struct Episode {
+    bool on = false;
+    int n_levels = 0;
+    DevBuf<int32_t> i32;                 // [EP_NI][n]
+    DevBuf<double> f64;                  // [EP_ND][n]
+    DevBuf<unsigned long long> table;    // [n_levels][EP_COLS]
+    DevBuf<int32_t> restore_status;      // status row of an npp_archive_restore whose caller asked for none (only restored envs restart)
+    size_t restore_cap = 0;
+};
+
 // path-direction action masking (npp_set_action_masking / npp_path_action_mask, npp_pathmask.hip): the mode, the per-env counters
 // and where the last step wrote its flags row.  Allocated by the first call that switches a mode on, kept for the handle's life.
 struct PathMask {
@@ -370,6 +383,7 @@ struct npp_handle_s {
     PathMask pm;
     Reward rw;
     Demo demo;
+    Episode ep;
 };
 
 
@@ -940,6 +954,34 @@ int reward_restart_range(npp_handle h, int env0, int count) {
     return reward_restart(h, h->env.mask.get());
 }
 
+// ---- episode statistics (npp_set_episode_stats; the rule: npp_episode.hpp, the kernels: npp_episode.hip).  Nothing below launches
+// or allocates while they are off.
+EpisodeArgs episode_args(npp_handle h) {
+    const Episode &E = h->ep;
+    EpisodeArgs a{};
+    a.n = h->n;
+    a.n_levels = E.n_levels;
+    a.i32 = E.i32.get();
+    a.f64 = E.f64.get();
+    a.table = E.table.get();
+    a.env_level = h->env.level.get();
+    a.autoreset = (h->flags & NPP_FLAG_AUTORESET) ? 1 : 0;
+    return a;
+}
+
+// an EP_EV_* event for the envs under the device mask (null = all), or for the `count` envs listed in d_envs (those whose d_status
+// entry, when given, is 0), on the caller's stream; the caller has joined the streams
+int episode_event(npp_handle h, int event, const uint8_t *d_mask, const int32_t *d_envs = nullptr, const int32_t *d_status = nullptr, int count = 0) {
+    if (!h->ep.on) return NPP_OK;
+    EpisodeArgs a = episode_args(h);
+    a.mask = d_mask;
+    a.envs = d_envs;
+    a.env_status = d_status;
+    a.count = count;
+    HIP_TRY(h, launch_episode_event(a, event, h->stream));
+    return NPP_OK;
+}
+
 // `fresh` = the entities are created for the first time since the level was assigned (the state a replay starts from);
 // any later reset is a Simulator.reset(), after which Entity.index no longer starts at 0 (see ZOO_HEAD in npp_internal.hpp)
 int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, int automatic = 0) {
@@ -961,6 +1003,7 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
         h->pm.flags = nullptr;
     }
     if (int rc = reward_restart(h, a.reset_mask)) return rc;   // (reward mode "pbrs") an episode start
+    if (int rc = episode_event(h, EP_EV_RESET, a.reset_mask)) return rc;   // (episode statistics) a running episode is abandoned
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));  // env_mask is caller memory: finish the copy
     return NPP_OK;
 }
@@ -1006,8 +1049,12 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     }
     // (reward mode "pbrs") after a step the reward launch restarts the envs whose episode ended, on their new level, from the step's
     // flags; an explicit draw (npp_draw_levels) is an episode start of its own
-    if (!out)
+    // (episode statistics) likewise: after a step the ending row has not been accumulated yet, and the accumulation itself starts the
+    // new episode on the level drawn here
+    if (!out) {
         if (int rc = reward_restart(h, h->pool.changed.get())) return rc;
+        if (int rc = episode_event(h, EP_EV_RESET, h->pool.changed.get())) return rc;
+    }
     return NPP_OK;
 }
 
@@ -1143,6 +1190,7 @@ int npp_restore(npp_handle h, const uint8_t *env_mask) {
     }
     HIP_TRY(h, launch_archive_restore(a, h->stream));
     if (int rc = reward_restart(h, a.mask)) return rc;   // (reward mode "pbrs") records carry no reward state: it restarts on the restored one
+    if (int rc = episode_event(h, EP_EV_RESTORE, a.mask)) return rc;   // (episode statistics) an episode begun by a restore
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));
     // the restored zoo blocks carry the repositioning flags / coordinates of the snapshot (head words 3..7): the host's
     // view of them (which decides whether the zoo kernels run) is restored with them
@@ -1191,6 +1239,17 @@ int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_env
         }
         a.status = w.restore_status.get();
     }
+    if (!store && h->ep.on && !a.status && count > 0) {   // (episode statistics) likewise
+        Episode &E = h->ep;
+        if (E.restore_cap < (size_t)count) {
+            DevBuf<int32_t> t;
+            HIP_TRY(h, t.alloc((size_t)count));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));   // a queued event may still read the old row
+            E.restore_status = std::move(t);
+            E.restore_cap = (size_t)count;
+        }
+        a.status = E.restore_status.get();
+    }
     a.rec = A.rec.get();
     a.meta_f64 = A.meta_f64.get();
     a.meta_i32 = A.meta_i32.get();
@@ -1198,6 +1257,8 @@ int archive_move(npp_handle h, const char *who, bool store, const int32_t *d_env
     HIP_TRY(h, store ? launch_archive_store(a, h->stream) : launch_archive_restore(a, h->stream));
     if (!store && count > 0)   // (reward mode "pbrs") records carry no reward state: it restarts on the restored one
         if (int rc = reward_restart(h, nullptr, d_envs, a.status, count)) return rc;
+    if (!store && count > 0)   // (episode statistics) the entries that restored begin an episode there
+        if (int rc = episode_event(h, EP_EV_RESTORE, nullptr, d_envs, a.status, count)) return rc;
     // a restored env takes the record's truncation limit on the device: the host mirror is read back where a host path needs it
     if (!store && count > 0) h->pool.dirty = true;
     return NPP_OK;
@@ -1296,6 +1357,74 @@ int npp_archive_route_view(npp_handle h, const uint32_t **d_records, int64_t *hd
     if (d_records) *d_records = h->ar.rec.get();
     if (hdr_offset_words) *hdr_offset_words = h->ar.lay.off_route;
     if (stride_words) *stride_words = h->ar.lay.words;
+    return NPP_OK;
+}
+
+int npp_set_episode_stats(npp_handle h, int enable) {
+    if (!h) return NPP_ERR_INVALID;
+    if (enable && h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_episode_stats: no levels loaded");
+    ON_DEVICE_JOINED(h);
+    Episode e;   // complete or not at all: a failed allocation leaves the previous state in place
+    if (enable) {
+        e.n_levels = (int)h->ls.levels.size();
+        if (e.i32.alloc((size_t)EP_NI * h->n) != hipSuccess || e.f64.alloc((size_t)EP_ND * h->n) != hipSuccess ||
+            e.table.alloc((size_t)e.n_levels * EP_COLS) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, NPP_ERR_HIP, "npp_set_episode_stats: hipMalloc of the records of " + std::to_string(h->n) + " envs and the table of " +
+                                            std::to_string(e.n_levels) + " levels failed");
+        }
+        e.on = true;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // queued accumulations / events still use the old planes
+    h->ep = std::move(e);
+    if (h->ep.on) {
+        HIP_TRY(h, hipMemsetAsync(h->ep.table.get(), 0, h->ep.table.bytes(), h->stream));
+        if (int rc = episode_event(h, EP_EV_INIT, nullptr)) return rc;
+    }
+    return NPP_OK;
+}
+
+int npp_episode_accumulate(npp_handle h, const uint8_t *d_flags, const uint16_t *d_frames, const float *d_reward, const float *d_components,
+                           int n_steps, uint8_t *d_ended) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->ep.on) return fail(h, NPP_ERR_STATE, "npp_episode_accumulate: episode statistics are off (npp_set_episode_stats)");
+    if (!d_flags || !d_frames || !d_reward || n_steps <= 0)
+        return fail(h, NPP_ERR_INVALID, "npp_episode_accumulate: flags, frames and reward rows and n_steps > 0 are required");
+    if (d_components && ((uintptr_t)d_components & 7))
+        return fail(h, NPP_ERR_INVALID, "npp_episode_accumulate: d_components must be 8-byte aligned");
+    ON_DEVICE_JOINED(h);
+    EpisodeArgs a = episode_args(h);
+    a.n_steps = n_steps;
+    a.flags = d_flags;
+    a.frames = d_frames;
+    a.reward = d_reward;
+    a.comps = d_components;
+    a.ended = d_ended;
+    HIP_TRY(h, launch_episode(a, h->stream));
+    return NPP_OK;
+}
+
+int npp_episode_restart(npp_handle h, const uint8_t *d_mask, int from_restore) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->ep.on) return fail(h, NPP_ERR_STATE, "npp_episode_restart: episode statistics are off (npp_set_episode_stats)");
+    ON_DEVICE_JOINED(h);
+    return episode_event(h, from_restore ? EP_EV_RESTORE : EP_EV_RESET, d_mask);
+}
+
+int npp_episode_view(npp_handle h, const int32_t **d_i32, const double **d_f64, const uint64_t **d_table) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->ep.on) return fail(h, NPP_ERR_STATE, "npp_episode_view: episode statistics are off (npp_set_episode_stats)");
+    if (d_i32) *d_i32 = h->ep.i32.get();
+    if (d_f64) *d_f64 = h->ep.f64.get();
+    if (d_table) *d_table = reinterpret_cast<const uint64_t *>(h->ep.table.get());
+    return NPP_OK;
+}
+
+int npp_episode_table_reset(npp_handle h) {
+    if (!h) return NPP_ERR_INVALID;
+    if (!h->ep.on) return fail(h, NPP_ERR_STATE, "npp_episode_table_reset: episode statistics are off (npp_set_episode_stats)");
+    ON_DEVICE_JOINED(h);
+    HIP_TRY(h, hipMemsetAsync(h->ep.table.get(), 0, h->ep.table.bytes(), h->stream));
     return NPP_OK;
 }
 
@@ -1565,6 +1694,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     h->ar = Archive();   // the checkpoint archive's records were laid out for the old set
     h->cells = Cells();  // (the cell index goes with the archive)
     h->demo = Demo();    // (demonstration player) its level ids named levels of the old set
+    h->ep = Episode();   // (episode statistics) the table had a row per level of the old set: the feature is off
     h->rw = Reward();    // (reward mode "pbrs") the levels' constants and every env's reward state belonged to the old set: the mode is off
     h->snap = Snapshot();   // likewise
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
@@ -1988,6 +2118,7 @@ int npp_tick(npp_handle h, const uint8_t *d_inputs, int n_ticks) {
     a.mode = 1;
     a.autoreset = 0;
     HIP_TRY(h, launch_step(a, h->stream));
+    if (int rc = episode_event(h, EP_EV_TICK, nullptr)) return rc;   // (episode statistics) the current episodes hold frames no row counted
     return route_event(h, ROUTE_EV_TICK, nullptr);   // (action routes) raw input bytes: the current routes no longer lead here
 }
 
@@ -2677,6 +2808,7 @@ int npp_demo_play(npp_handle h, const NppDemoOut *out) {
     so.d_spatial_context = d.sc.get();
     so.d_positions = d.pos.get();
     std::vector<int32_t> lv((size_t)N);
+    if (int rc = episode_event(h, EP_EV_CLEAR, nullptr)) return rc;   // (episode statistics) the player's ticks are nobody's episode
     for (size_t q = 0; q < d.plan.round_ticks.size(); q++) {
         // the round's levels (an env without a replay plays the level of the round's first) and the reference's load: a level
         // assignment plus Simulator.reset.  The assignment is npp_assign_levels' and synchronises as it always does; between
@@ -2703,7 +2835,7 @@ int npp_demo_play(npp_handle h, const NppDemoOut *out) {
             HIP_TRY(h, launch_demo_collect(a, h->stream));
         }
     }
-    return NPP_OK;
+    return episode_event(h, EP_EV_CLEAR, nullptr);
 }
 
 int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets, const int32_t *levels, int n_replays, int score_mode,
@@ -2774,6 +2906,7 @@ int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets
     c.status = status.get();
     c.no_count = 1;
     std::vector<int32_t> lv(N);
+    if (int rc = episode_event(h, EP_EV_CLEAR, nullptr)) return rc;   // (episode statistics) the player's ticks are nobody's episode
     for (size_t q = 0; q < rounds; q++) {
         // the round's levels and the reference's load, as npp_demo_play does them (the assignment synchronises as it always does;
         // between here and the end of the round nothing does).  Both flip the routes: every env starts the round on an empty one
@@ -2806,6 +2939,7 @@ int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets
         }
     }
     if (int rc = route_event(h, ROUTE_EV_INIT, nullptr)) return rc;   // the players' routes are nobody's episode
+    if (int rc = episode_event(h, EP_EV_CLEAR, nullptr)) return rc;   // ... and so are the current episode records
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the queued launches read the tables freed here
     return NPP_OK;
 }

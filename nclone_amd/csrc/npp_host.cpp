@@ -9,6 +9,7 @@
 #include "npp_augment.hpp"
 #include "npp_cells.hpp"
 #include "npp_demo.hpp"
+#include "npp_episode.hpp"
 #include "npp_minimal.hpp"
 #include "npp_pathmask.hpp"
 #include "npp_pool.hpp"
@@ -268,6 +269,49 @@ int npp_demo_plan_host(const int64_t *lengths, int n_replays, int frame_skip, in
     }
     if (counts) { counts[0] = (int32_t)p.order.size(); counts[1] = (int32_t)p.round_ticks.size(); }
     if (rows_total) *rows_total = p.rows_total;
+    return NPP_OK;
+}
+
+int npp_episode_apply_host(int32_t *rec_i32, double *rec_f64, uint64_t *table, int n_levels, int autoreset, const int32_t *events,
+                           const float *rows, int count, uint8_t *ended) {
+    static_assert(EP_NI == NPP_EP_NI && EP_ND == NPP_EP_ND && EP_FIN == NPP_EP_FIN && EP_DFIN == NPP_EP_DFIN && EP_COLS == NPP_EP_COLS &&
+                      EP_FIN_FLAGS == NPP_EP_FIN_FLAGS && EP_N_FINISHED == NPP_EP_N_FINISHED && EP_COMP == NPP_EP_COMP &&
+                      (int)EPC_ABANDONED == (int)NPP_EPC_ABANDONED && (int)EP_BITS == (int)NPP_EP_BITS,
+                  "the planes and columns include/npp_amd.h documents");
+    if (!rec_i32 || !rec_f64 || n_levels < 0 || (n_levels > 0 && !table) || count < 0 || (count > 0 && !events))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_episode_apply_host: bad arguments");
+    EpRecord r;
+    for (int k = 0; k < EP_NI; k++) r.i[k] = rec_i32[k];
+    for (int k = 0; k < EP_ND; k++) r.d[k] = rec_f64[k];
+    bool any = false;
+    for (int i = 0; i < count; i++) {
+        const int32_t *ev = events + (size_t)i * 8;
+        if (ev[0] == 0) {
+            if (ev[1] < 0 || ev[1] > 255 || ev[2] < 0 || ev[2] > 65535 || !rows)
+                return fail(nullptr, NPP_ERR_INVALID, "npp_episode_apply_host: event " + std::to_string(i) + ": bad step row");
+            const float *row = rows + (size_t)i * 8;
+            const bool end = ev[4] ? ep_row<true>(r, ev[1], ev[2], row[0], row + 1, ev[3], autoreset != 0)
+                                   : ep_row<false>(r, ev[1], ev[2], row[0], nullptr, ev[3], autoreset != 0);
+            if (end) {
+                any = true;
+                const int level = r.i[EP_FIN + EP_LEVEL];
+                if (level >= 0 && level < n_levels) {
+                    uint64_t d[EP_COLS];
+                    ep_deltas(r, d);
+                    for (int k = 0; k < EP_COLS; k++) table[(size_t)level * EP_COLS + k] += d[k];
+                }
+            }
+        } else if (ev[0] >= 1 && ev[0] <= 5) {
+            static const int kind[6] = {0, EP_EV_RESET, EP_EV_RESTORE, EP_EV_TICK, EP_EV_INIT, EP_EV_CLEAR};
+            const int charged = ep_event(r, kind[ev[0]], ev[1]);
+            if (charged >= 0 && charged < n_levels) table[(size_t)charged * EP_COLS + EPC_ABANDONED] += 1;
+        } else {
+            return fail(nullptr, NPP_ERR_INVALID, "npp_episode_apply_host: event " + std::to_string(i) + ": unknown kind");
+        }
+    }
+    for (int k = 0; k < EP_NI; k++) rec_i32[k] = r.i[k];
+    for (int k = 0; k < EP_ND; k++) rec_f64[k] = r.d[k];
+    if (ended) *ended = any ? 1 : 0;
     return NPP_OK;
 }
 

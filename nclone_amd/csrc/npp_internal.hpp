@@ -256,6 +256,28 @@ struct RouteArgs {
 enum RouteEvent { ROUTE_EV_FLIP = 0, ROUTE_EV_TICK = 1, ROUTE_EV_INIT = 2 };
 hipError_t launch_route_append(const RouteArgs &a, hipStream_t s);
 hipError_t launch_route_event(const RouteArgs &a, int event, hipStream_t s);
+// npp_episode.hip: episode statistics (see npp_set_episode_stats in include/npp_amd.h; the rule: npp_episode.hpp)
+struct EpisodeArgs {
+    int n, n_levels;
+    int32_t *i32;                 // [EP_NI][n]
+    double *f64;                  // [EP_ND][n]
+    unsigned long long *table;    // [n_levels][EP_COLS]
+    const int32_t *env_level;     // [n]
+    // accumulate: the rows of one step launch
+    int n_steps, autoreset;
+    const uint8_t *flags;         // [n_steps][n]
+    const uint16_t *frames;       // [n_steps][n]
+    const float *reward;          // [n_steps][n]
+    const float *comps;           // [n_steps][n][6] or null: the component planes are then neither loaded nor stored
+    uint8_t *ended;               // [n] or null: 1 = the call finished an episode of the env
+    // event: the envs, as RewardArgs selects them
+    const uint8_t *mask;
+    const int32_t *envs;
+    const int32_t *env_status;
+    int count;
+};
+hipError_t launch_episode(const EpisodeArgs &a, hipStream_t s);
+hipError_t launch_episode_event(const EpisodeArgs &a, int event, hipStream_t s);
 // npp_graph.hip: graph observation rows (see npp_graph_observation in include/npp_amd.h; tables: npp_graph.hpp)
 struct GraphHdr;
 struct GraphArgs {

@@ -131,7 +131,7 @@ def check_cell_arg(v, dtype, n, what):
 
 def _device_tensor(ptr, numel, dtype, device):
     """A torch tensor over `numel` elements of device memory that the native handle owns (no copy, no ownership)."""
-    typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4", torch.float64: "<f8"}[dtype]
+    typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4", torch.float64: "<f8", torch.int64: "<i8"}[dtype]
 
     class _Holder:
         __cuda_array_interface__ = {"shape": (int(numel),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
@@ -295,6 +295,7 @@ class NppBatch:
             self.h, blob.ctypes.data_as(C.POINTER(C.c_double)), offsets.ctypes.data_as(C.POINTER(C.c_int64)), len(offsets) - 1))
         self.n_levels = len(offsets) - 1
         self._archive_meta = self._archive_cells = self._archive_route_views = None   # (the checkpoint archive and its cell index go with the level set)
+        self._episode_views = None   # (so do the episode statistics: the table has a row per level)
         self._reward_mode, self._reward_pending = 0, False   # (so does reward mode "pbrs": its constants are per level)
         self._reward_waypoints = False
 
@@ -825,6 +826,78 @@ class NppBatch:
             self._archive_route_views = (torch.as_strided(raw, (ns, cap), (stride * 4, 1), (off + 8) * 4),
                                          torch.as_strided(words, (ns, 8), (stride, 1), off))
         return self._archive_route_views
+
+    # ---- episode statistics (include/npp_amd.h npp_set_episode_stats) ------------------------------------
+    EPISODE_COLUMNS = ("episodes", "won", "dead", "truncated", "dead_mine", "dead_impact", "switch", "steps", "frames", "won_frames",
+                       "return_fix", "restored", "abandoned")
+    _EPISODE_I32 = ("steps", "frames", "switch_step", "switch_frames", "level", "bits")
+
+    def set_episode_stats(self, on=True):
+        """Keep per-env episode records (return, length, switch latch, level) and a per-level outcome table on the device; off
+        frees them.  After load_levels: the table has a row per loaded level, and load_levels switches the feature off."""
+        nat.check(self.h, self.lib.npp_set_episode_stats(self.h, 1 if on else 0))
+        self._episode_views = None
+
+    def episode_accumulate(self, flags=None, frames=None, reward=None, components=None, n_steps=1, ended=None):
+        """One call per step() / step_many(), after step_reward() when the reward comes from there: the rows' steps, frames and
+        rewards go into the current episode of every env, and an ending row moves it to the finished one and into the level
+        table.  flags u8 / frames i16 / reward f32 CUDA tensors of n_steps * N elements (default: the block's own, one row);
+        components: f32 [n_steps * N, 6] or None; ended: optional u8 CUDA tensor [N], 1 where this call finished an episode."""
+        flags = self.flags if flags is None else flags
+        frames = self.frames if frames is None else frames
+        reward = self.reward if reward is None else reward
+        n_steps = int(n_steps)
+        want = n_steps * self.n
+        for name, t, dts, per in (("flags", flags, (torch.uint8,), 1), ("frames", frames, (torch.int16, torch.uint16), 1),
+                                  ("reward", reward, (torch.float32,), 1), ("components", components, (torch.float32,), 6),
+                                  ("ended", ended, (torch.uint8,), 0)):
+            if t is None:
+                continue
+            if n_steps < 1 or t.dtype not in dts or not t.is_cuda or not t.is_contiguous() or t.numel() != (want * per if per else self.n):
+                raise ValueError("episode_accumulate: %s must be a contiguous %s CUDA tensor of %s elements and n_steps >= 1"
+                                 % (name, str(dts[0]).replace("torch.", ""), "N" if not per else "n_steps * N * %d" % per))
+        nat.check(self.h, self.lib.npp_episode_accumulate(
+            self.h, C.c_void_p(flags.data_ptr()), C.c_void_p(frames.data_ptr()), C.c_void_p(reward.data_ptr()),
+            C.c_void_p(components.data_ptr()) if components is not None else None, n_steps,
+            C.c_void_p(ended.data_ptr()) if ended is not None else None))
+        self._keep_episode = (flags, frames, reward, components)
+
+    def episode_restart(self, mask=None, from_restore=False):
+        """The current episode of the envs under `mask` (u8 CUDA tensor [N], None = all) starts over: a running one counts as
+        abandoned.  from_restore: the new episode does not start at the spawn -- it will add to `restored` only."""
+        m = None
+        if mask is not None:
+            if mask.dtype != torch.uint8 or not mask.is_cuda or mask.numel() != self.n or not mask.is_contiguous():
+                raise ValueError("episode_restart: mask must be a contiguous uint8 CUDA tensor [N]")
+            m = C.c_void_p(mask.data_ptr())
+            self._keep_episode_mask = mask
+        nat.check(self.h, self.lib.npp_episode_restart(self.h, m, 1 if from_restore else 0))
+
+    def episode_views(self):
+        """Named CUDA views (no copy) of the records, rewritten in stream order: for the current episode steps, frames,
+        switch_step, switch_frames, level, bits (int32 [N]), ret (float64 [N]) and comp (float64 [6, N]); the same with the
+        prefix "fin_" for the finished one, plus fin_flags and n_finished; "table" int64 [L, 16]."""
+        if getattr(self, "_episode_views", None) is None:
+            a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            nat.check(self.h, self.lib.npp_episode_view(self.h, C.byref(a), C.byref(b), C.byref(c)))
+            i32 = _device_tensor(a.value, 14 * self.n, torch.int32, self.device).view(14, self.n)
+            f64 = _device_tensor(b.value, 14 * self.n, torch.float64, self.device).view(14, self.n)
+            v = {"i32": i32, "f64": f64,
+                 "table": _device_tensor(c.value, self.n_levels * 16, torch.int64, self.device).view(self.n_levels, 16)}
+            for k, name in enumerate(self._EPISODE_I32):
+                v[name], v["fin_" + name] = i32[k], i32[6 + k]
+            v["fin_flags"], v["n_finished"] = i32[12], i32[13]
+            v["ret"], v["comp"], v["fin_ret"], v["fin_comp"] = f64[0], f64[1:7], f64[7], f64[8:14]
+            self._episode_views = v
+        return self._episode_views
+
+    def episode_level_table(self):
+        """int64 [L, 16] view of the level table (columns EPISODE_COLUMNS, then zeros); return_fix is the sum of the returns in
+        units of 2^-20."""
+        return self.episode_views()["table"]
+
+    def episode_table_reset(self):
+        nat.check(self.h, self.lib.npp_episode_table_reset(self.h))
 
     # ---- cell index over the archive (include/npp_amd.h npp_archive_cells_create; DESIGN.md 17) ------------------------
     def archive_cells_create(self, seed=0, enable=True):

@@ -203,6 +203,15 @@ class NppVecEnvironment:
     waypoint_params: a dict with some of collection_radius (at most 24), out_of_order_scale, progress_scale, progress_spacing
     (defaults: 18, 0.3, 2.0, 12); set_waypoint_params(**kw) changes the first three between steps; level_waypoints(level) returns a
     level's table.  Levels whose paths carry more than 512 waypoints raise NppError in the constructor.
+    episode_stats=True: per-env episode records and a per-level outcome table, kept by a device kernel behind every
+    step.  info["_episode"] is a bool [N], true where an episode ended in this step, and info["episode"] holds, per env, the episode
+    that ended last (rows outside the mask: the env's previous one; before its first: zeros, level_id -1): "r" the return (float64,
+    the sum of the step rewards in step order), "l" its frames (the reference's sim.frame), "steps", "is_success",
+    "switch_activated", "switch_activation_frame" (the episode's frame count after the step that activated the switch, -1 = never:
+    step granularity, where the reference has the exact tick -- the one deviation), "level_id", "from_checkpoint" (begun by a
+    checkpoint restore or replay), and with reward_mode="pbrs" "pbrs_total" and "terminal_reward".  output="torch": views of the
+    handle's planes, rewritten by the next step.  episode_level_stats() returns the table by column with success_rate and
+    mean_return per level -- a curriculum's input for set_level_weights(); reset_episode_level_stats() zeroes it.
     """
 
     metadata = {"render_modes": []}
@@ -215,8 +224,9 @@ class NppVecEnvironment:
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
                  augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False,
                  route_capacity=None, action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False,
-                 waypoint_params=None):
+                 waypoint_params=None, episode_stats=False):
         assert output in ("torch", "numpy")
+        self._episode = bool(episode_stats)
         if reward_mode not in ("sparse", "pbrs"):
             raise ValueError('reward_mode must be "sparse" or "pbrs", not %r' % (reward_mode,))
         self._pbrs = reward_mode == "pbrs"
@@ -348,6 +358,10 @@ class NppVecEnvironment:
         self.last_restart_slots = None
         if self.checkpoint_cells:
             self._b.archive_cells_create(seed=checkpoint_seed)
+        if self._episode:
+            self._b.set_episode_stats(True)
+            with self._b._ctx():
+                self._ep_ended = torch.zeros(self.num_envs, dtype=torch.uint8, device=self._b.device)
 
     # -- helpers ------------------------------------------------------------------------------------------------
     def _produce(self, reset_all=False):
@@ -506,6 +520,8 @@ class NppVecEnvironment:
                         self._pbrs_on()
                     info = {"checkpoint_replay": True, "replay_frames": frames.to(torch.int64).sum(dim=0),
                             "replay_terminated": (flags & 3).ne(0).any(dim=0)}
+                    if self._episode:   # the replay's steps are not accumulated: the episode begins where it ends
+                        self._b.episode_restart(None, from_restore=True)
                 else:
                     info = {"checkpoint_replay": False, "replay_frames": 0}
         self._b.observe()
@@ -927,6 +943,49 @@ class NppVecEnvironment:
                 b.step_reward(wp_bonus_out=self._wp_bonus, wp_info_out=self._wp_info)
             else:
                 b.step_reward()
+        if self._episode:   # behind the reward launch: the block's flags, frames and reward rows, and in pbrs mode the components
+            b.episode_accumulate(components=b.out.t["reward_components"] if self._pbrs else None, ended=self._ep_ended)
+
+    def _episode_info(self):
+        """info["_episode"] and info["episode"] of the step just accumulated"""
+        v = self._b.episode_views()
+        i32, f64, ended = v["i32"][6:14], v["f64"][7:14], self._ep_ended
+        if self.output == "numpy":
+            with self._b._ctx():   # (to_host has synchronised the stream the accumulation ran on)
+                i32, f64, ended = i32.cpu().numpy(), f64.cpu().numpy(), ended.cpu().numpy()
+        steps, frames, sw_step, sw_frames, level, bits, flags = (i32[k] for k in range(7))
+        where = torch.where if self.output == "torch" else np.where
+        ep = {"r": f64[0], "l": frames, "steps": steps, "is_success": (flags & 1) != 0, "switch_activated": sw_step != 0,
+              "switch_activation_frame": where(sw_step != 0, sw_frames, -1 if self.output == "numpy" else torch.full_like(sw_frames, -1)),
+              "level_id": level, "from_checkpoint": (bits & 2) != 0}
+        if self._pbrs:
+            ep["pbrs_total"], ep["terminal_reward"] = f64[1], f64[5]
+        return ended != 0, ep
+
+    def episode_level_stats(self):
+        """episode_stats=True: {column: [L]} of the level table -- episodes, won, dead, truncated, dead_mine, dead_impact, switch,
+        steps, frames, won_frames, return_fix (the returns' sum in units of 2^-20), restored, abandoned (int64) -- plus success_rate =
+        won / episodes and mean_return (float64), both 0 where a level has no episode yet.  Episodes begun by a checkpoint count in
+        `restored` alone."""
+        if not self._episode:
+            raise RuntimeError("episode_level_stats: this env was created without episode_stats")
+        b = self._b
+        with b._ctx():
+            t = b.episode_level_table().clone()
+            out = {name: t[:, k] for k, name in enumerate(b.EPISODE_COLUMNS)}
+            n = out["episodes"].to(torch.float64)
+            some = n > 0
+            div = torch.where(some, n, torch.ones_like(n))
+            out["success_rate"] = torch.where(some, out["won"].to(torch.float64) / div, torch.zeros_like(n))
+            out["mean_return"] = torch.where(some, out["return_fix"].to(torch.float64) / 1048576.0 / div, torch.zeros_like(n))
+            if self.output == "numpy":
+                out = {k: v.cpu().numpy() for k, v in out.items()}
+        return out
+
+    def reset_episode_level_stats(self):
+        if not self._episode:
+            raise RuntimeError("reset_episode_level_stats: this env was created without episode_stats")
+        self._b.episode_table_reset()
 
     def step_wait(self):
         """Results of the step enqueued by step_async: (obs, reward, terminated, truncated, info) with batch dims.
@@ -962,6 +1021,8 @@ class NppVecEnvironment:
                 with b._ctx():   # (to_host above has synchronised the stream the reward launches ran on)
                     wb, wi = wb.cpu().numpy(), wi.cpu().numpy()
             info["waypoints"] = {"bonus": wb, "index": wi[:, 0], "next_expected": wi[:, 1], "collected": wi[:, 2]}
+        if self._episode:
+            info["_episode"], info["episode"] = self._episode_info()
         return self._with_graph(self._obs(src), info["level_id"]), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
@@ -1027,7 +1088,9 @@ class NppEnvironment:
     checkpoint_cells / checkpoint_seed are passed through to it.
     action_masking_mode / set_action_masking_mode(mode): NppVecEnvironment's path-direction action masking; info["path_direction"] is
     an int, and the step that ends the episode adds info["deterministic_mask_applied_count"] / info["deterministic_mask_rate"].
-    reward_mode / reward_params / set_reward_params(**kw): NppVecEnvironment's reward mode "pbrs"; info["pbrs_components"] is (6,)."""
+    reward_mode / reward_params / set_reward_params(**kw): NppVecEnvironment's reward mode "pbrs"; info["pbrs_components"] is (6,).
+    episode_stats=True: the step that ends the episode adds the reference's info["r"] (the return), info["l"] (frames),
+    info["is_success"] and info["switch_activation_frame"] (base_environment.py:1163-1242; NppVecEnvironment's episode statistics)."""
 
     def __init__(self, map_data=None, custom_map_path=None, frame_skip=4, device=0, enable_visual_observations=False,
                  truncation_limit="dynamic", fast_reset=True, enable_spatial_context=False, enable_switch_states=False,
@@ -1035,7 +1098,8 @@ class NppEnvironment:
                  state_stack_size=4, frame_stack_padding_type="zero", enable_graph_observations=False, observation_mode="full",
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
                  checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None,
-                 action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False, waypoint_params=None):
+                 action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False, waypoint_params=None,
+                 episode_stats=False):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -1062,7 +1126,7 @@ class NppEnvironment:
                                     checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
                                     checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity,
                                     action_masking_mode=action_masking_mode, reward_mode=reward_mode, reward_params=reward_params,
-                                    reward_waypoints=reward_waypoints, waypoint_params=waypoint_params)
+                                    reward_waypoints=reward_waypoints, waypoint_params=waypoint_params, episode_stats=episode_stats)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
@@ -1131,6 +1195,10 @@ class NppEnvironment:
             w = info["waypoints"]
             out_info["waypoints"] = {"bonus": float(w["bonus"][0]), "index": int(w["index"][0]), "next_expected": int(w["next_expected"][0]),
                                      "collected": int(w["collected"][0])}
+        if "_episode" in info and bool(info["_episode"][0]):
+            ep = info["episode"]
+            out_info.update({"r": float(ep["r"][0]), "l": int(ep["l"][0]), "is_success": bool(ep["is_success"][0]),
+                             "switch_activation_frame": int(ep["switch_activation_frame"][0])})
         return self._unbatch(obs), float(rew[0]), bool(term[0]), bool(trunc[0]), out_info
 
     def close(self):
