@@ -926,6 +926,83 @@ int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets
                      const float *d_scores, int32_t *d_counts);
 int npp_archive_seed_rows_host(const uint8_t *in, int64_t len, int score_mode, uint8_t *actions, uint8_t *route_bits, float *scores);
 
+/* Goal curriculum: the exit switch and the exit door slide along the level's optimal path in stages (IntermediateGoalManager,
+ * gym_environment/reward_calculation/intermediate_goal_manager.py; GoalCurriculumConfig, reward_config.py:953-983; the env side at
+ * npp_environment.py:703-1000 and base_environment.py:404-481).  DESIGN.md 25 has the scope, the reference's quirks and the rule.
+ * A (level, stage) pair is a VARIANT LEVEL: the level compiled with the two positions overridden, appended to the handle's level set
+ * behind the base levels, so the step, the observations of the entity tables, the pool, the archive and the episode table serve it
+ * and no kernel of the step changes.
+ * NppGoalCurriculumParams: stage_distance_interval (pixels, > 0), advancement_threshold (completion rate in [0, 1]), rolling_window
+ *   (outcomes per level, 1..8192), auto_advance (the device advances a level's stage; 0 = only npp_goal_set_stage does).
+ * npp_set_goal_curriculum(h, enable, params): enable != 0 builds the stage table of every loaded level (build_paths_for_level,
+ *   :158-336, and the two getters, :570-696, from the ORIGINAL positions), compiles the variants (apply_to_simulator, :698-1012,
+ *   carried statically in the cell lists) and RELOADS the level set as base levels + variants: like npp_load_levels it switches the
+ *   level pool, the archive, the reward mode, episode statistics, the demonstration player and snapshots off, so call it first.
+ *   Every env restarts on the stage-0 variant of the base level it played.  enable == 0 reloads the base levels alone.
+ *   npp_load_levels switches the mode off.  NPP_ERR_STATE without levels; NPP_ERR_INVALID for numbers outside the ranges above or a
+ *   level with more than 1024 stages.  While the mode is on, level ids an entry point TAKES (npp_assign_levels, npp_set_level_pool's
+ *   weights) are base ids; level ids it REPORTS (npp_get_env_levels, the episode table, archive records) are ids of the whole set,
+ *   and npp_goal_tables maps them back.  A level without both paths has no stages and stays on its base level.
+ * The rule, once per npp_step under NPP_FLAG_AUTORESET, behind the step kernel (two launches, npp_goal.hip): (1) every env whose
+ *   episode ended counts into its own three counters (update_from_episode, :1014-1038) and, when it played its level's CURRENT stage,
+ *   appends its `won` bit to the level's ring, in env-index order; (2) with auto_advance a level whose ring is full with at least
+ *   `need` wins (the smallest w with (double)w / window >= threshold) and that is not at its last stage advances by one and clears its
+ *   ring; (3) a pending stage (npp_goal_set_stage) replaces the stage, and every env that ended is put on the variant of its level's
+ *   stage -- with the level pool on, of the level the pool drew -- exactly as the pool assigns a level.  npp_reset and
+ *   npp_draw_levels run (3) alone for the envs they restart; npp_assign_levels takes base ids and maps them.
+ * npp_goal_set_stage(h, level, stage): level -1 = all base levels; deferred to the env's next episode start as in the reference
+ *   (set_curriculum_stage, base_environment.py:404-481), clamped to num_stages - 1.
+ * npp_goal_view: device views, valid until the mode is switched: level words i32[NPP_GOAL_LEVEL_WORDS][n_base] (stage, pending,
+ *   num_stages, first variant id, ring fill, ring head, wins, advances, appended, stale), ring u32[n_base][ring_words], env words
+ *   i32[NPP_GOAL_ENV_WORDS][n_envs] (episode_count, switch_activation_count, completion_count, switch latch, level at the last end).
+ * npp_goal_tables (host): base_of i32[n_levels], stage_of i32[n_levels] (-1 = a base level); either may be NULL; *n_base.
+ * npp_goal_stage_positions(h, level, ...): num_stages, the three distances, the original positions f64[4] and per stage the switch
+ *   and door position f64[cap][4] of a base level.
+ * Served on variants and pinned against the reference there: npp_reachability[_ex], npp_minimal_observation,
+ *   npp_path_action_mask, reward mode "pbrs" without the waypoints (a variant's level constants take the manager's fractional
+ *   positions, pbrs_potentials.py:952-955).  npp_graph_observation is NPP_ERR_UNSUPPORTED while the mode is on: nothing pins the
+ *   graph rows of a moved level.
+ * Refused while the mode is on (NPP_ERR_STATE, each with its own text): npp_set_reward_waypoints (the reference recomputes the paths
+ *   to the moved goals, main_reward_calculator.py:1254-1297), npp_demo_create and npp_archive_seed (the replays belong to the base
+ *   levels), npp_step_many (its inner steps have no episode boundary the rule could see).
+ * Host-only: npp_goal_stages_host -- the stage table of one level; npp_goal_apply_host -- one application of the rule on host
+ *   arrays laid out as the views (drawn: the pool's draw per env or NULL; count 0 = step (3) alone);
+ *   npp_compile_level_segments_goal / _entities_goal -- the dumps of a variant (goal_xy f64[4] switch x, y, door x, y; NULL = the
+ *   level itself); order i32[rows][4] = CSR slot, list-order number after Simulator.reset, after fast_reset, place in the fast walk. */
+typedef struct NppGoalCurriculumParams {
+    double stage_distance_interval;
+    double advancement_threshold;
+    int32_t rolling_window;
+    int32_t auto_advance;
+} NppGoalCurriculumParams;
+#define NPP_GOAL_LEVEL_WORDS 10
+#define NPP_GOAL_ENV_WORDS 5
+void npp_goal_default_params(NppGoalCurriculumParams *out);
+int npp_set_goal_curriculum(npp_handle h, int enable, const NppGoalCurriculumParams *params);
+int npp_goal_set_stage(npp_handle h, int level, int stage);
+int npp_goal_view(npp_handle h, const int32_t **d_level_words, const uint32_t **d_ring, const int32_t **d_env_words, int *n_base,
+                  int *ring_words, int *need);
+int npp_goal_tables(npp_handle h, int32_t *base_of, int32_t *stage_of, int *n_base);
+int npp_goal_stage_positions(npp_handle h, int level, int32_t *num_stages, double *dist, double *orig, int stage_cap, double *pos);
+int npp_goal_stages_host(const double *map, int64_t n, double interval, int32_t *num_stages, double *dist /* [3] */, double *orig /* [4] */,
+                         int stage_cap, double *pos /* [stage_cap][4] */, int path_cap, int32_t *path0, int32_t *path1, int32_t *path_len);
+int npp_goal_apply_host(int32_t *level_words, uint32_t *ring, int32_t *env_words, const int32_t *base_of, const int32_t *stage_of, int n_base,
+                        int n_levels, int n_envs, int window, int need, int auto_advance, const uint8_t *flags, int end_bits, int count,
+                        int32_t *env_level, const int32_t *drawn, uint8_t *changed);
+/* Host-only: npp_reach_rollout_host, npp_path_direction_host, npp_reward_level_constants_host and npp_reward_host_wp on a variant (goal_xy f64[4] as above; NULL = the level itself). */
+int npp_reward_level_constants_goal_host(const double *map, int64_t n, const double *goal_xy, double *out, int32_t *status);
+int npp_reward_goal_host(const double *map, int64_t n, const double *goal_xy, const NppRewardParams *params, const NppWaypointParams *wp,
+                         const double *pos0, const double *pos, const uint8_t *flags, const uint16_t *frames, int count, int end_bits,
+                         double *reward_out, double *components_out, uint8_t *kind_out, int32_t *status, double *wp_bonus_out,
+                         int32_t *wp_info_out);   /* wp must be NULL with goal_xy */
+int npp_reach_rollout_goal_host(const double *map, int64_t n, const double *goal_xy, const double *pos, const int32_t *mines,
+                                const uint8_t *new_episode, int count, float *out, int32_t *status, double *raw_out);
+int npp_path_direction_goal_host(const double *map, int64_t n, const double *goal_xy, const double *pos, const uint8_t *switch_activated,
+                                 int count, int8_t *direction_out, uint8_t *from_graph_out, int32_t *status);
+int npp_compile_level_segments_goal(const double *map, int64_t n, const double *goal_xy, int16_t *out, int max_rows, int *n_out,
+                                    uint32_t *unsupported_mask);
+int npp_compile_level_entities_goal(const double *map, int64_t n, const double *goal_xy, double *out, int max_rows, int *n_out, int32_t *order);
+
 int npp_num_envs(npp_handle h);
 int npp_num_levels(npp_handle h);
 

@@ -51,6 +51,9 @@ EXPORTS = [
     "npp_archive_seed", "npp_archive_seed_rows_host",
     "npp_set_episode_stats", "npp_episode_accumulate", "npp_episode_restart", "npp_episode_view", "npp_episode_table_reset",
     "npp_episode_apply_host",
+    "npp_goal_default_params", "npp_set_goal_curriculum", "npp_goal_set_stage", "npp_goal_view", "npp_goal_tables", "npp_goal_stage_positions",
+    "npp_goal_stages_host", "npp_goal_apply_host", "npp_compile_level_segments_goal", "npp_compile_level_entities_goal",
+    "npp_reach_rollout_goal_host", "npp_path_direction_goal_host", "npp_reward_level_constants_goal_host", "npp_reward_goal_host",
 ]
 
 
@@ -67,6 +70,11 @@ class StepOut(C.Structure):
         ("d_positions", C.c_void_p),
         ("d_work", C.c_void_p),
     ]
+
+
+class GoalCurriculumParams(C.Structure):
+    _fields_ = [("stage_distance_interval", C.c_double), ("advancement_threshold", C.c_double), ("rolling_window", C.c_int32),
+                ("auto_advance", C.c_int32)]
 
 
 class DemoOut(C.Structure):
@@ -230,6 +238,21 @@ def lib():
     L.npp_episode_view.argtypes = [H] + [C.POINTER(C.c_void_p)] * 3
     L.npp_episode_table_reset.argtypes = [H]
     L.npp_episode_apply_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_goal_default_params.argtypes = [C.c_void_p]
+    L.npp_set_goal_curriculum.argtypes = [H, C.c_int, C.c_void_p]
+    L.npp_goal_set_stage.argtypes = [H, C.c_int, C.c_int]
+    L.npp_goal_view.argtypes = [H] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_int)] * 3
+    L.npp_goal_tables.argtypes = [H, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    L.npp_goal_stage_positions.argtypes = [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.npp_goal_stages_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_goal_apply_host.argtypes = [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_compile_level_segments_goal.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+    L.npp_compile_level_entities_goal.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+    L.npp_reward_level_constants_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.npp_reward_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 6
+    L.npp_reach_rollout_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
+    L.npp_path_direction_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
     for name in EXPORTS:
         if name != "npp_last_error":
             getattr(L, name).restype = C.c_int

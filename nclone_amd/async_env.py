@@ -90,13 +90,18 @@ class NppAsyncVecEnvironment:
     No reward mode "pbrs": reward_mode other than "sparse" raises ValueError (NppVecEnvironment(reward_mode="pbrs") has it), and so
     does reward_waypoints=True, the path waypoints of that mode.
     No episode statistics: episode_stats=True raises ValueError (NppVecEnvironment(episode_stats=True) has them).
+    No goal curriculum: goal_curriculum=True raises ValueError (NppVecEnvironment(goal_curriculum=True) has it).
     """
 
     def __init__(self, levels, num_envs, n_streams=4, level_ids=None, frame_skip=4, device=0, truncation_limit="dynamic",
                  output="numpy", autoreset=True, fast_reset=True, level_weights=None, level_seed=None, observation_mode="full",
                  enable_augmentation=False, checkpoint_slots=0, checkpoint_cells=False, action_masking_mode=None, reward_mode="sparse",
-                 reward_waypoints=False, episode_stats=False):
+                 reward_waypoints=False, episode_stats=False, goal_curriculum=False):
         assert output in ("torch", "numpy")
+        if goal_curriculum:
+            raise ValueError("NppAsyncVecEnvironment has no goal curriculum (goal_curriculum=True): a level's stage and its window of "
+                             "outcomes belong to one handle and its sub-batches are handles of their own; "
+                             "NppVecEnvironment(goal_curriculum=True) has it")
         if reward_waypoints:
             raise ValueError("NppAsyncVecEnvironment has no path waypoints (reward_waypoints=True): they are a term of reward mode "
                              '"pbrs", which it does not have; NppVecEnvironment(reward_mode="pbrs", reward_waypoints=True) has them')

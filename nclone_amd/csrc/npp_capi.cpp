@@ -15,6 +15,7 @@
 #include "npp_cells.hpp"
 #include "npp_demo.hpp"
 #include "npp_episode.hpp"
+#include "npp_goal.hpp"
 #include "npp_graph.hpp"
 #include "npp_host.hpp"
 #include "npp_internal.hpp"
@@ -112,6 +113,8 @@ struct GraphObs {
 // The loaded level set and everything derived from it: replaced whole by npp_load_levels
 struct LevelSet {
     std::vector<CompiledLevel> levels;
+    std::vector<std::vector<double>> maps;   // map_data of the base levels (the goal curriculum compiles its variants from them)
+    int n_base = 0;                          // levels [0, n_base) were loaded by the caller; the rest are goal-curriculum variants
     std::vector<LevelHdr> hdrs;
     int n_words_max = 1;
     uint32_t hot_max = 0;   // largest staged-level size over the set
@@ -213,6 +216,20 @@ struct Pool {
     std::vector<double> w;
     DevBuf<uint8_t> flags;     // [n] step flags when the caller asked for none
     DevBuf<uint8_t> changed;   // [n] envs that drew another level (device reset / observe mask)
+};
+
+// goal curriculum (npp_set_goal_curriculum; the rule: npp_goal.hpp, the kernels: npp_goal.hip): with it on, the device changes
+// env_level after a step as the level pool does, and shares the pool's changed mask and flags row
+struct Goal {
+    bool on = false;
+    NppGoalCurriculumParams params{100.0, 0.80, 500, 1};
+    int ring_words = 0, need = 0;
+    std::vector<GoalStages> stages;            // [n_base]
+    std::vector<int32_t> base_of, stage_of;    // [n_levels]
+    std::vector<int32_t> variant0;             // [n_base]
+    std::vector<double> all;                   // [n_levels] of 1.0: make_plan's "any level an env may play"
+    DevBuf<int32_t> lv, env, d_base_of, d_stage_of, list;
+    DevBuf<uint32_t> ring;
 };
 
 // minimal observation (npp_set_minimal_observation / npp_minimal_observation): its mine columns are read from the spatial_context
@@ -384,6 +401,7 @@ struct npp_handle_s {
     Reward rw;
     Demo demo;
     Episode ep;
+    Goal goal;
 };
 
 
@@ -608,7 +626,8 @@ int pull_levels(npp_handle h);
 
 void plan_geometry(npp_handle h, bool keep_tuning = false) {
     (void)pull_levels(h);   // (a failure leaves the mirror as it was and is reported by the next call that syncs)
-    const Plan p = make_plan(h->ls, h->n, h->env_level, h->lanes_per_env, h->waves_per_block, h->n_ovr > 0, h->pool.on ? &h->pool.w : nullptr);
+    const Plan p = make_plan(h->ls, h->n, h->env_level, h->lanes_per_env, h->waves_per_block, h->n_ovr > 0,
+                             h->pool.on ? &h->pool.w : (h->goal.on ? &h->goal.all : nullptr));
     // a new plan (level set, assignment, geometry, zoo kernels on / off) restarts npp_step's variant autotuner; a plan that comes
     // out the same (npp_restore of a snapshot with the same overrides) keeps the decision
     const bool same_plan = keep_tuning && p.g == h->plan.g && p.wpb == h->plan.wpb && p.zoo_active == h->plan.zoo_active;
@@ -1012,8 +1031,28 @@ int reset_impl(npp_handle h, const uint8_t *env_mask, int fresh, int fast = 0, i
 // npp_assign_levels -- fresh Simulator.reset, reachability cache row and per-episode dictionary dropped -- by the existing kernels
 // under the draw's device mask, and, when `out` is given, their observation rows are rewritten by a masked observe launch.
 // The caller has joined the streams.
-int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_out *out) {
+GoalArgs goal_args(npp_handle h, const uint8_t *d_flags, int bits, int count) {
+    Goal &G = h->goal;
+    GoalArgs a{};
+    a.g = GoalState{G.lv.get(), G.ring.get(), G.env.get(), G.d_base_of.get(), G.d_stage_of.get(), h->ls.n_base, h->n, G.ring_words,
+                    G.params.rolling_window, G.need, G.params.auto_advance};
+    a.flags = d_flags;
+    a.bits = bits;
+    a.count = count;
+    a.env_level = h->env.level.get();
+    a.trunc = h->env.trunc.get();
+    a.level_trunc = h->dyn_trunc ? h->ls.d_level_trunc.get() : nullptr;
+    a.changed = h->pool.changed.get();
+    a.list = G.list.get();
+    return a;
+}
+
+// (goal curriculum) With the mode on the same call runs its two launches around the draw: the bookkeeping of the envs that ended
+// (counted only behind a step: `out` given) in front of it, the assignment to the variant of the level's stage behind it; `draw` =
+// false leaves the pool's draw out (npp_reset: the envs restart on the level they have, at its current stage).
+int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_out *out, bool draw = true) {
     const LevelSet &L = h->ls;
+    if (h->goal.on) HIP_TRY(h, launch_goal_update(goal_args(h, d_flags, bits, out ? 1 : 0), h->stream));
     PoolArgs p;
     p.n = h->n;
     p.flags = d_flags;
@@ -1027,7 +1066,8 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     p.trunc = h->env.trunc.get();
     p.level_trunc = h->dyn_trunc ? L.d_level_trunc.get() : nullptr;
     p.changed = h->pool.changed.get();
-    HIP_TRY(h, launch_pool_draw(p, h->stream));
+    if (draw && h->pool.on) HIP_TRY(h, launch_pool_draw(p, h->stream));
+    if (h->goal.on) HIP_TRY(h, launch_goal_assign(goal_args(h, d_flags, bits, out ? 1 : 0), h->stream));
     h->pool.dirty = true;
     KernelArgs a = base_args(h);
     a.reset_mask = h->pool.changed.get();
@@ -1054,6 +1094,22 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     if (!out) {
         if (int rc = reward_restart(h, h->pool.changed.get())) return rc;
         if (int rc = episode_event(h, EP_EV_RESET, h->pool.changed.get())) return rc;
+    }
+    return NPP_OK;
+}
+
+// (goal curriculum) base level ids -> the variant of each level's current stage, read from the device
+int goal_map_levels(npp_handle h, const int32_t *base_ids, int n, std::vector<int32_t> &out) {
+    const Goal &G = h->goal;
+    const int nb = h->ls.n_base;
+    std::vector<int32_t> lv((size_t)GL_N * nb);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(lv.data(), G.lv.get(), G.lv.bytes(), hipMemcpyDeviceToHost));
+    out.resize(n);
+    for (int i = 0; i < n; i++) {
+        const int b = base_ids[i];
+        if (b < 0 || b >= nb) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: with the goal curriculum on the ids are base level ids");
+        out[i] = lv[(size_t)GL_NUM_STAGES * nb + b] > 0 ? lv[(size_t)GL_VARIANT0 * nb + b] + lv[(size_t)GL_STAGE * nb + b] : b;
     }
     return NPP_OK;
 }
@@ -1574,6 +1630,144 @@ int npp_get_launch_geometry(npp_handle h, int *lanes_per_env, int *waves_per_blo
     return NPP_OK;
 }
 
+static int install_levels(npp_handle h, LevelSet &next);
+
+int npp_set_goal_curriculum(npp_handle h, int enable, const NppGoalCurriculumParams *params) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_goal_curriculum: NULL handle");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_goal_curriculum: no levels loaded");
+    if (!enable && !h->goal.on) return NPP_OK;
+    NppGoalCurriculumParams q;
+    if (params) q = *params; else npp_goal_default_params(&q);
+    if (enable && (!(q.stage_distance_interval > 0.0) || !std::isfinite(q.stage_distance_interval) || !(q.advancement_threshold >= 0.0) ||
+                   !(q.advancement_threshold <= 1.0) || q.rolling_window < 1 || q.rolling_window > GOAL_MAX_WINDOW))
+        return fail(h, NPP_ERR_INVALID, "npp_set_goal_curriculum: interval must be > 0, threshold in [0, 1], window in 1..8192");
+    ON_DEVICE_JOINED(h);
+    if (int rc = pull_levels(h)) return rc;
+    std::vector<int32_t> base_assign((size_t)h->n);
+    for (int e = 0; e < h->n; e++) base_assign[e] = h->goal.on ? h->goal.base_of[h->env_level[e]] : h->env_level[e];
+    // the new set is built whole, as npp_load_levels builds it: a refused call leaves the handle as it was
+    LevelSet next;
+    next.n_base = h->ls.n_base;
+    next.maps = h->ls.maps;
+    const int nb = next.n_base;
+    next.levels.resize(nb);
+    Goal G;
+    G.params = q;
+    G.stages.resize(nb);
+    G.variant0.assign(nb, 0);
+    std::string err;
+    for (int i = 0; i < nb; i++) {
+        if (!compile_level(next.maps[i].data(), (int64_t)next.maps[i].size(), next.levels[i], err))
+            return fail(h, NPP_ERR_INVALID, "npp_set_goal_curriculum: level " + std::to_string(i) + ": " + err);
+        G.base_of.push_back(i);
+        G.stage_of.push_back(-1);
+    }
+    for (int i = 0; enable && i < nb; i++) {
+        ReachBuilt R;
+        build_reach(next.levels[i], R);
+        if (!goal_stage_table(next.levels[i], R, q.stage_distance_interval, G.stages[i]))
+            return fail(h, NPP_ERR_INVALID, "npp_set_goal_curriculum: level " + std::to_string(i) + " has more than 1024 stages at this interval");
+        G.variant0[i] = G.stages[i].num_stages > 0 ? (int32_t)next.levels.size() : i;
+        for (int st = 0; st < G.stages[i].num_stages; st++) {
+            next.levels.emplace_back();
+            if (!compile_level_variant(next.maps[i].data(), (int64_t)next.maps[i].size(), G.stages[i].pos.data() + 4 * (size_t)st, next.levels.back(), err))
+                return fail(h, NPP_ERR_INVALID, "npp_set_goal_curriculum: level " + std::to_string(i) + " stage " + std::to_string(st) + ": " + err);
+            G.base_of.push_back(i);
+            G.stage_of.push_back(st);
+        }
+    }
+    const size_t nl = next.levels.size(), N = (size_t)h->n;
+    if (enable) {
+        G.ring_words = (q.rolling_window + 31) / 32;
+        G.need = goal_need(q.rolling_window, q.advancement_threshold);
+        G.all.assign(nl, 1.0);
+        HIP_TRY(h, G.lv.alloc((size_t)GL_N * nb));
+        HIP_TRY(h, G.ring.alloc((size_t)nb * G.ring_words));
+        HIP_TRY(h, G.env.alloc((size_t)GE_N * N));
+        HIP_TRY(h, G.d_base_of.alloc(nl));
+        HIP_TRY(h, G.d_stage_of.alloc(nl));
+        HIP_TRY(h, G.list.alloc(2 * N));
+        if (!h->pool.changed) {
+            HIP_TRY(h, h->pool.changed.alloc(N));
+            HIP_TRY(h, h->pool.flags.alloc(N));
+            HIP_TRY(h, hipMemset(h->pool.flags.get(), 0, N));
+        }
+        std::vector<int32_t> lv((size_t)GL_N * nb, 0);
+        for (int i = 0; i < nb; i++) {
+            lv[(size_t)GL_PENDING * nb + i] = -1;
+            lv[(size_t)GL_NUM_STAGES * nb + i] = G.stages[i].num_stages;
+            lv[(size_t)GL_VARIANT0 * nb + i] = G.variant0[i];
+        }
+        HIP_TRY(h, hipMemcpy(G.lv.get(), lv.data(), G.lv.bytes(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemset(G.ring.get(), 0, G.ring.bytes()));
+        HIP_TRY(h, hipMemset(G.env.get(), 0, G.env.bytes()));
+        HIP_TRY(h, hipMemset(G.list.get(), 0, G.list.bytes()));
+        HIP_TRY(h, hipMemcpy(G.d_base_of.get(), G.base_of.data(), G.d_base_of.bytes(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(G.d_stage_of.get(), G.stage_of.data(), G.d_stage_of.bytes(), hipMemcpyHostToDevice));
+    }
+    if (int rc = install_levels(h, next)) return rc;   // (switches the mode off, as for any new set)
+    if (enable) {
+        h->goal = std::move(G);
+        h->goal.on = true;
+        h->pool.ever = true;   // levels change on the device from here on: snapshots carry them
+    }
+    plan_geometry(h);
+    return npp_assign_levels(h, nullptr, base_assign.data(), h->n);
+}
+
+int npp_goal_set_stage(npp_handle h, int level, int stage) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_goal_set_stage: NULL handle");
+    if (!h->goal.on) return fail(h, NPP_ERR_STATE, "npp_goal_set_stage: the goal curriculum is off (npp_set_goal_curriculum)");
+    const int nb = h->ls.n_base;
+    if (level < -1 || level >= nb || stage < 0) return fail(h, NPP_ERR_INVALID, "npp_goal_set_stage: level is -1 or a base level id, stage >= 0");
+    ON_DEVICE_JOINED(h);
+    std::vector<int32_t> pend(nb);
+    int32_t *d_pend = h->goal.lv.get() + (size_t)GL_PENDING * nb;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(pend.data(), d_pend, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+    for (int l = level < 0 ? 0 : level; l < (level < 0 ? nb : level + 1); l++) {
+        const int ns = h->goal.stages[l].num_stages;
+        if (ns > 0) pend[l] = stage < ns - 1 ? stage : ns - 1;
+    }
+    HIP_TRY(h, hipMemcpy(d_pend, pend.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice));
+    return NPP_OK;
+}
+
+int npp_goal_view(npp_handle h, const int32_t **d_level_words, const uint32_t **d_ring, const int32_t **d_env_words, int *n_base, int *ring_words,
+                  int *need) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_goal_view: NULL handle");
+    if (!h->goal.on) return fail(h, NPP_ERR_STATE, "npp_goal_view: the goal curriculum is off (npp_set_goal_curriculum)");
+    static_assert(GL_N == NPP_GOAL_LEVEL_WORDS && GE_N == NPP_GOAL_ENV_WORDS, "npp_amd.h describes the planes");
+    if (d_level_words) *d_level_words = h->goal.lv.get();
+    if (d_ring) *d_ring = h->goal.ring.get();
+    if (d_env_words) *d_env_words = h->goal.env.get();
+    if (n_base) *n_base = h->ls.n_base;
+    if (ring_words) *ring_words = h->goal.ring_words;
+    if (need) *need = h->goal.need;
+    return NPP_OK;
+}
+
+int npp_goal_tables(npp_handle h, int32_t *base_of, int32_t *stage_of, int *n_base) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_goal_tables: NULL handle");
+    if (!h->goal.on) return fail(h, NPP_ERR_STATE, "npp_goal_tables: the goal curriculum is off (npp_set_goal_curriculum)");
+    if (base_of) std::memcpy(base_of, h->goal.base_of.data(), sizeof(int32_t) * h->goal.base_of.size());
+    if (stage_of) std::memcpy(stage_of, h->goal.stage_of.data(), sizeof(int32_t) * h->goal.stage_of.size());
+    if (n_base) *n_base = h->ls.n_base;
+    return NPP_OK;
+}
+
+int npp_goal_stage_positions(npp_handle h, int level, int32_t *num_stages, double *dist, double *orig, int stage_cap, double *pos) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_goal_stage_positions: NULL handle");
+    if (!h->goal.on) return fail(h, NPP_ERR_STATE, "npp_goal_stage_positions: the goal curriculum is off (npp_set_goal_curriculum)");
+    if (level < 0 || level >= h->ls.n_base || stage_cap < 0) return fail(h, NPP_ERR_INVALID, "npp_goal_stage_positions: bad arguments");
+    const GoalStages &S = h->goal.stages[level];
+    if (num_stages) *num_stages = S.num_stages;
+    if (dist) { dist[0] = S.d_switch; dist[1] = S.d_exit; dist[2] = S.d_combined; }
+    if (orig) std::memcpy(orig, S.orig, sizeof(S.orig));
+    for (size_t i = 0; pos && i < S.pos.size() && i < 4 * (size_t)stage_cap; i++) pos[i] = S.pos[i];
+    return NPP_OK;
+}
+
 int npp_num_envs(npp_handle h) { return h ? h->n : 0; }
 int npp_num_levels(npp_handle h) { return h ? (int)h->ls.levels.size() : 0; }
 
@@ -1597,6 +1791,17 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
                                                     " uses entity types outside the accelerated path: " + t);
         }
     }
+    next.n_base = n_levels;
+    next.maps.resize(n_levels);
+    for (int i = 0; i < n_levels; i++) next.maps[i].assign(blob + offsets[i], blob + offsets[i + 1]);
+    return install_levels(h, next);
+}
+
+// packs and uploads a compiled level set and swaps it in (npp_load_levels; npp_set_goal_curriculum with its variants behind the base
+// levels); the caller is on the device with the streams joined
+static int install_levels(npp_handle h, LevelSet &next) {
+    std::vector<CompiledLevel> &lv = next.levels;
+    const int n_levels = (int)lv.size();
     // ---- pack the blob
     std::vector<unsigned char> host;
     std::vector<LevelHdr> &hdrs = next.hdrs;
@@ -1699,6 +1904,7 @@ int npp_load_levels(npp_handle h, const double *blob, const int64_t *offsets, in
     h->snap = Snapshot();   // likewise
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
     h->pool.w.clear();
+    h->goal = Goal();    // (goal curriculum) the variants belonged to the old set: the mode is off
     h->ovr.assign(h->n, 0);
     h->n_ovr = 0;
     h->assign_gen++;
@@ -1717,6 +1923,11 @@ int npp_assign_levels(npp_handle h, const int32_t *env_ids, const int32_t *level
     if (!env_ids && n != h->n) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: env_ids == NULL needs n == n_envs");
     ON_DEVICE_JOINED(h);
     if (int rc = pull_levels(h)) return rc;   // (level pool) the whole mirror is uploaded below
+    std::vector<int32_t> mapped;
+    if (h->goal.on) {   // (goal curriculum) base ids in, the variant of each level's current stage out
+        if (int rc = goal_map_levels(h, level_ids, n, mapped)) return rc;
+        level_ids = mapped.data();
+    }
     std::vector<uint8_t> mask(h->n, 0);
     for (int i = 0; i < n; i++) {   // validate everything before touching the assignment: an error must leave host and device in step
         int e = env_ids ? env_ids[i] : i;
@@ -1751,6 +1962,15 @@ int npp_reset(npp_handle h, const uint8_t *env_mask) { return npp_reset_ex(h, en
 int npp_reset_ex(npp_handle h, const uint8_t *env_mask, int mode) {
     if (!h) return NPP_ERR_INVALID;
     if (mode < 0 || mode > 2) return fail(h, NPP_ERR_INVALID, "npp_reset_ex: mode must be 0, 1 or 2");
+    if (h->goal.on) {   // (goal curriculum) the envs restart on the variant of their level's current stage, assigned as the pool assigns
+        if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_reset: no levels loaded");
+        ON_DEVICE_JOINED(h);
+        uint8_t *d_mask = h->env.mask.get();
+        if (env_mask) HIP_TRY(h, hipMemcpyAsync(d_mask, env_mask, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+        else HIP_TRY(h, hipMemsetAsync(d_mask, 1, (size_t)h->n, h->stream));
+        if (int rc = pool_redraw(h, d_mask, 0xff, nullptr, false)) return rc;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // env_mask is caller memory; the mask buffer is reused below
+    }
     const int fast = mode == 2 || (mode == 0 && (h->flags & NPP_FLAG_FAST_RESET));
     // mode 0 follows NppEnvironment.reset: the first reset after a level assignment reloads the map (Simulator.reset), later ones
     // are fast resets; the per-env "no reset yet" bit lives in the state planes (npp_state.hpp: S_FRESH)
@@ -1789,6 +2009,15 @@ int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64
         return NPP_OK;
     }
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: no levels loaded");
+    std::vector<double> padded;
+    if (h->goal.on && n_levels == h->ls.n_base) {   // (goal curriculum) one weight per BASE level: the variants are never drawn
+        padded.assign(weights, weights + n_levels);
+        padded.resize(h->ls.levels.size(), 0.0);
+        weights = padded.data();
+        n_levels = (int)padded.size();
+    } else if (h->goal.on) {
+        return fail(h, NPP_ERR_INVALID, "npp_set_level_pool: with the goal curriculum on the weights are per base level");
+    }
     std::vector<double> cdf;
     int last = 0;
     std::string err;
@@ -2050,7 +2279,7 @@ extern "C" {
 int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
-    const bool pool = h->pool.on && (h->flags & NPP_FLAG_AUTORESET);
+    const bool pool = (h->pool.on || h->goal.on) && (h->flags & NPP_FLAG_AUTORESET);   // (goal curriculum: the same tail)
     if (!pool && !h->rt.cap && !h->pm.mode && !h->rw.mode) return step_impl(h, d_actions, frame_skip, out);
     npp_step_out o;
     std::memset(&o, 0, sizeof(o));
@@ -2084,6 +2313,9 @@ int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_s
 int npp_step_many(npp_handle h, const uint8_t *d_actions, int n_steps, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0 || n_steps <= 0) return fail(h, NPP_ERR_INVALID, "npp_step_many: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step_many: no levels loaded");
+    if (h->goal.on)
+        return fail(h, NPP_ERR_STATE, "npp_step_many: the goal curriculum is on and the launch's inner steps have no episode boundary its "
+                                      "bookkeeping could see (npp_set_goal_curriculum(h, 0, NULL) first)");
     if (h->rw.mode)
         return fail(h, NPP_ERR_STATE, "npp_step_many: reward mode \"pbrs\" is on and the launch's inner steps have no observation "
                                       "(npp_set_reward_mode(h, 0, NULL) first)");
@@ -2566,6 +2798,9 @@ int npp_set_waypoint_params(npp_handle h, const NppWaypointParams *params) {
 int npp_set_reward_waypoints(npp_handle h, int on, const NppWaypointParams *params) {
     if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_reward_waypoints: NULL handle");
     Reward &w = h->rw;
+    if (on && h->goal.on)
+        return fail(h, NPP_ERR_STATE, "npp_set_reward_waypoints: the goal curriculum is on and the waypoints towards the moved goals are not "
+                                      "computed (npp_set_goal_curriculum(h, 0, NULL) first)");
     if (!w.mode) return fail(h, NPP_ERR_STATE, "npp_set_reward_waypoints: reward mode \"pbrs\" is off (npp_set_reward_mode)");
     if (!on) {
         w.wp_on = 0;
@@ -2671,6 +2906,7 @@ const char *player_refusal(npp_handle h) {
     if (h->pm.mode) return "action masking is on (npp_set_action_masking(h, 0) first)";
     if (h->fs.vk || h->fs.sk) return "frame stacking is on (npp_set_frame_stack(h, 0, 0, 0) first)";
     if (h->pool.on) return "the level pool is on (npp_set_level_pool(h, NULL, 0, 0) first)";
+    if (h->goal.on) return "the goal curriculum is on and the replays belong to the base levels (npp_set_goal_curriculum(h, 0, NULL) first)";
     if (h->ov.n_cuts) return "the observation overlap is on (npp_set_obs_overlap(h, 0) first)";
     return nullptr;
 }
@@ -2950,6 +3186,9 @@ int npp_graph_observation(npp_handle h, float *d_node_feats, uint16_t *d_edge_in
     if (((uintptr_t)d_node_feats | (uintptr_t)d_edge_index | (uintptr_t)d_edge_mask) & 15)
         return fail(h, NPP_ERR_INVALID, "npp_graph_observation: node features, edge index and edge mask must be 16-byte aligned");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_graph_observation: no levels loaded");
+    if (h->goal.on)
+        return fail(h, NPP_ERR_UNSUPPORTED, "npp_graph_observation: the goal curriculum is on and the graph rows on its variant levels are not pinned against the reference "
+                                            "(npp_set_goal_curriculum(h, 0, NULL) first)");
     if (h->n_ovr) return fail(h, NPP_ERR_UNSUPPORTED, "npp_graph_observation: an entity is repositioned with npp_set_entity_pos");
     ON_DEVICE_JOINED(h);
     if (int rc = ensure_graph(h)) return rc;

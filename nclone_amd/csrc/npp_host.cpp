@@ -144,11 +144,16 @@ int npp_route_apply_host(int32_t *hdr, uint8_t *actions, int capacity, int autor
 
 int npp_path_direction_host(const double *map, int64_t n, const double *pos, const uint8_t *switch_activated, int count,
                             int8_t *direction_out, uint8_t *from_graph_out, int32_t *status) {
+    return npp_path_direction_goal_host(map, n, nullptr, pos, switch_activated, count, direction_out, from_graph_out, status);
+}
+
+int npp_path_direction_goal_host(const double *map, int64_t n, const double *goal_xy, const double *pos, const uint8_t *switch_activated, int count,
+                                 int8_t *direction_out, uint8_t *from_graph_out, int32_t *status) {
     if (!map || count < 0 || (count > 0 && (!pos || !switch_activated || !direction_out)))
         return fail(nullptr, NPP_ERR_INVALID, "npp_path_direction_host: bad arguments");
     ReachBuilt R;
     std::string err;
-    if (!build_reach(map, n, R, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_path_direction_host: " + err);
+    if (!build_reach_variant(map, n, goal_xy, R, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_path_direction_host: " + err);
     ReachHdr H;
     std::vector<unsigned char> blob;
     pack_reach(R, H, blob);
@@ -163,10 +168,15 @@ int npp_path_direction_host(const double *map, int64_t n, const double *pos, con
 }
 
 int npp_compile_level_segments(const double *map, int64_t n, int16_t *out, int max_rows, int *n_out, uint32_t *unsupported_mask) {
+    return npp_compile_level_segments_goal(map, n, nullptr, out, max_rows, n_out, unsupported_mask);
+}
+
+int npp_compile_level_segments_goal(const double *map, int64_t n, const double *goal_xy, int16_t *out, int max_rows, int *n_out,
+                                    uint32_t *unsupported_mask) {
     if (!map || !out || !n_out) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_segments: bad arguments");
     CompiledLevel L;
     std::string err;
-    if (!compile_level(map, n, L, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_segments: " + err);
+    if (!compile_level_variant(map, n, goal_xy, L, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_segments: " + err);
     int r = dump_segments(L, out, max_rows);
     if (r < 0) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_segments: buffer too small");
     *n_out = r;
@@ -220,10 +230,20 @@ int npp_plan_zoo_block(const double *blob, const int64_t *offsets, int n_levels,
 }
 
 int npp_compile_level_entities(const double *map, int64_t n, double *out, int max_rows, int *n_out) {
+    return npp_compile_level_entities_goal(map, n, nullptr, out, max_rows, n_out, nullptr);
+}
+
+int npp_compile_level_entities_goal(const double *map, int64_t n, const double *goal_xy, double *out, int max_rows, int *n_out, int32_t *order) {
     if (!map || !out || !n_out) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_entities: bad arguments");
     CompiledLevel L;
     std::string err;
-    if (!compile_level(map, n, L, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_entities: " + err);
+    if (!compile_level_variant(map, n, goal_xy, L, err)) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_entities: " + err);
+    for (size_t i = 0; order && i < L.ent_map_order.size() && (int)i < max_rows; i++) {   // per entity in map order: CSR slot, list-order
+        const int s = L.ent_map_order[i];                                                   // numbers after reset / fast reset, fast walk place
+        int walk = 0;
+        while (L.ent_perm[walk] != s) walk++;
+        order[4 * i] = s; order[4 * i + 1] = L.ent_seq[s]; order[4 * i + 2] = L.ent_rank[s]; order[4 * i + 3] = walk;
+    }
     int ne = (int)L.ent_map_order.size();
     if (ne > max_rows) return fail(nullptr, NPP_ERR_INVALID, "npp_compile_level_entities: buffer too small");
     // cell of a slot from the CSR

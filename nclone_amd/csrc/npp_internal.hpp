@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "npp_goal.hpp"
 #include "npp_state.hpp"
 #include "npp_zoo_layout.hpp"
 
@@ -190,6 +191,20 @@ struct PoolArgs {
     uint8_t *changed;             // [n] out: 1 = the env drew another level than it played (every other byte 0)
 };
 hipError_t launch_pool_draw(const PoolArgs &a, hipStream_t s);
+// npp_goal.hip: the goal curriculum's bookkeeping (see npp_set_goal_curriculum in include/npp_amd.h; the rule: npp_goal.hpp)
+struct GoalArgs {
+    GoalState g;
+    const uint8_t *flags;         // [n] env e's episode ended when flags[e] & bits
+    int bits;
+    int count;                    // 1: outcomes are counted (a step); 0: only the levels at the end and pending stages (explicit restarts)
+    int32_t *env_level;           // [n]
+    int32_t *trunc;               // [n] truncation limits
+    const int32_t *level_trunc;   // [n_levels] or null, as PoolArgs
+    uint8_t *changed;             // [n] out: 1 = the env starts its next episode on another level than it ended on
+    int32_t *list;                // [2][n] scratch, the ended envs in env order: base level | stage * 2 + won (stage -1: a base level)
+};
+hipError_t launch_goal_update(const GoalArgs &a, hipStream_t s);
+hipError_t launch_goal_assign(const GoalArgs &a, hipStream_t s);
 // npp_augment.hip: one augmentation call (see npp_frame_augment in include/npp_amd.h; the draw and the pixels: npp_augment.hpp)
 struct AugArgs {
     int n, k;                     // k: player_frame entries per env (the visual stack size, or 1)

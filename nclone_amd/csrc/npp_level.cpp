@@ -115,6 +115,16 @@ void seg_bounds_units(uint16_t s, int &x0, int &y0, int &x1, int &y1) {
 }  // namespace
 
 bool compile_level(const double *map, int64_t n, CompiledLevel &L, std::string &err) {
+    return compile_level_variant(map, n, nullptr, L, err);
+}
+
+bool compile_level_variant(const double *map, int64_t n, const double *goal_xy, CompiledLevel &L, std::string &err) {
+    if (goal_xy)
+        for (int k = 0; k < 4; k++)
+            if (!(std::fabs(goal_xy[k]) <= 65535.0)) {
+                err = "goal position is not a finite value within +-65535";
+                return false;
+            }
     if (n < 1233) {
         err = "map_data shorter than 1233 values";
         return false;
@@ -299,12 +309,25 @@ bool compile_level(const double *map, int64_t n, CompiledLevel &L, std::string &
         err = "too many entities (max 4096 per level)";
         return false;
     }
+    // ---- goal-curriculum variant (intermediate_goal_manager.py:698-1012 apply_to_simulator, carried statically): the exit
+    //      switch and its door stand at goal_xy.  A switch whose 24-px cell changed was removed from its list and APPENDED to the new
+    //      cell's, so it is last among that cell's load-time entities; the door only gets the new `cell` attribute
+    int moved_switch = -1;
+    if (goal_xy && last_switch_raw >= 0) {
+        L.goal_variant = true;
+        RawEnt &sw = raw[last_switch_raw], &door = raw[sw.link_raw];
+        const int sw_cell = cell_of(goal_xy[0], goal_xy[1]);
+        if (sw_cell != sw.cell) moved_switch = last_switch_raw;
+        sw.x = goal_xy[0]; sw.y = goal_xy[1]; sw.cell = sw_cell;
+        door.x = goal_xy[2]; door.y = goal_xy[3]; door.cell = cell_of(goal_xy[2], goal_xy[3]);
+    }
     // CSR by cell: map order inside a cell, exit doors after everything else of that cell (they are appended to
     // the cell's list only when their switch is hit, entity_exit_switch.py:120)
     std::vector<int> order(raw.size());
     for (size_t i = 0; i < raw.size(); i++) order[i] = (int)i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        int ka = raw[a].cell * 2 + (raw[a].kind == EK_EXIT), kb = raw[b].cell * 2 + (raw[b].kind == EK_EXIT);
+        int ka = raw[a].cell * 3 + (raw[a].kind == EK_EXIT ? 2 : (a == moved_switch ? 1 : 0));
+        int kb = raw[b].cell * 3 + (raw[b].kind == EK_EXIT ? 2 : (b == moved_switch ? 1 : 0));
         return ka < kb;
     });
     std::vector<int> slot_of(raw.size());
@@ -321,7 +344,8 @@ bool compile_level(const double *map, int64_t n, CompiledLevel &L, std::string &
         L.ent_y[s] = r.y;
         uint32_t link = r.link_raw >= 0 ? (uint32_t)slot_of[r.link_raw] : (r.extra >= 0 ? (uint32_t)r.extra : 0xffffu);
         L.ent_meta[s] = r.kind | (r.init << 4) | (link << 8) | (r.type << 24);
-        L.ent_seq[s] = (uint16_t)r.seq;
+        // an appended switch takes the first number behind the load-time ones (movers count from n_created + 1 on, npp_zoo.hpp)
+        L.ent_seq[s] = (uint16_t)(order[s] == moved_switch ? next_seq : r.seq);
         L.ent_cell[s] = (uint16_t)r.cell;
         L.ent_init_words[ent_word(s)] |= ent_bits_at(r.init, s);
         count[r.cell]++;
@@ -422,6 +446,8 @@ bool compile_level(const double *map, int64_t n, CompiledLevel &L, std::string &
             if (ref & 0x80000000u) L.mov_rank[ref & 0x7fffffffu] = (uint16_t)k;
             else L.ent_rank[ref] = (uint16_t)k;
         }
+        // fast_reset puts the switch back into its map cell and apply_to_simulator appends it to the new one again
+        if (moved_switch >= 0) L.ent_rank[slot_of[moved_switch]] = (uint16_t)next_seq;
         // walk order of the CSR under that rule: inside a cell by rank, exit doors still last (they join their cell's
         // list only when their switch is hit)
         L.ent_perm.resize(ne);

@@ -69,11 +69,17 @@ struct CompiledLevel {
     int n_created = 0;                 // entities created at load (first free list-order number)
     int n_balls = 0;
     double db_count = 0;               // map_data[1200]
+    bool goal_variant = false;         // compiled by compile_level_variant with positions (npp_goal.hpp): a goal-curriculum variant
     bool has_zoo = false;              // any kind beyond mines / gold / exit / locked doors
 };
 
 // Returns false (and fills err) on malformed input.
 bool compile_level(const double *map, int64_t n, CompiledLevel &out, std::string &err);
+
+// A goal-curriculum variant (npp_goal.hpp): the same level with its exit switch at goal_xy[0..1] and its exit door at goal_xy[2..3]
+// (world pixels, any fp64 value: map_data's `coord * 6` cannot carry them), the cell lists as apply_to_simulator leaves them.
+// goal_xy == nullptr is compile_level.  A level without an exit pair compiles to itself.
+bool compile_level_variant(const double *map, int64_t n, const double *goal_xy, CompiledLevel &out, std::string &err);
 
 // rows of 8 int16, see npp_dump_level_segments in npp_amd.h
 int dump_segments(const CompiledLevel &lv, int16_t *out, int max_rows);

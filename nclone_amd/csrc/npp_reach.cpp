@@ -22,6 +22,7 @@
 #include "npp_reach_build.hpp"
 #include "npp_reach_features.hpp"
 #include "npp_reward.hpp"
+#include "npp_goal.hpp"
 #include "npp_waypoint.hpp"
 
 namespace npp {
@@ -504,9 +505,11 @@ void build_adjacency(const CompiledLevel &L, ReachAdjacency &A) {
     A.in = fin.in; A.adj = fin.adj;
 }
 
-bool build_reach(const double *map, int64_t n, ReachBuilt &R, std::string &err) {
+bool build_reach(const double *map, int64_t n, ReachBuilt &R, std::string &err) { return build_reach_variant(map, n, nullptr, R, err); }
+
+bool build_reach_variant(const double *map, int64_t n, const double *goal_xy, ReachBuilt &R, std::string &err) {
     CompiledLevel L;
-    if (!compile_level(map, n, L, err)) return false;
+    if (!compile_level_variant(map, n, goal_xy, L, err)) return false;
     build_reach(L, R);
     return true;
 }
@@ -794,10 +797,10 @@ int graph_ninja_node(const Graph &g, double px, double py) {
 // Dijkstra on the physics cost that carries the pixel length of its paths -- then the sub-node projection tail.  It differs from
 // the A* above in what it hands the cost function as the aerial chain (:1693-1701: the chain of the NEIGHBOUR, counted for every
 // move off an ungrounded node) and in its soft early stop (:1644-1655).
-double geometric_path_distance(const AStarCtx &C, const std::vector<uint8_t> &ph, int sx, int sy, int gx, int gy, double entity_radius) {
+double geometric_path_distance(const AStarCtx &C, const std::vector<uint8_t> &ph, double sx, double sy, double gx, double gy, double entity_radius) {
     const Graph &A = *C.adj;
-    const int start = graph_ninja_node(A, (double)sx, (double)sy);
-    const int goal = find_closest_node(A, ph, (double)gx, (double)gy, 10.0 + entity_radius, false);
+    const int start = graph_ninja_node(A, sx, sy);
+    const int goal = find_closest_node(A, ph, gx, gy, 10.0 + entity_radius, false);
     if (start < 0 || goal < 0) return INFINITY;
     if (start == goal) return 0.0;
     std::vector<double> dist(RNODES, 0.0), geo(RNODES, 0.0);
@@ -849,7 +852,7 @@ double geometric_path_distance(const AStarCtx &C, const std::vector<uint8_t> &ph
         const double plen = py_pow(pdx * pdx + pdy * pdy, 0.5);
         if (plen > 0.001) {
             const double dirx = pdx / plen, diry = pdy / plen;
-            const double projection = ((double)sx - (reach_node_x(start) + 24)) * dirx + ((double)sy - (reach_node_y(start) + 24)) * diry;
+            const double projection = (sx - (reach_node_x(start) + 24)) * dirx + (sy - (reach_node_y(start) + 24)) * diry;
             const double t = target - projection - combined;
             return t > 0.0 ? t : 0.0;
         }
@@ -870,8 +873,13 @@ bool reward_level_constants(const CompiledLevel &L, const ReachBuilt &R, RewardL
     base.in = R.base_in; base.adj = R.base_adj;
     const AStarCtx C{&base, &R.phys, &R.mine_mult, &R.grad};
     const int spx = (int)(long)L.spawn_x, spy = (int)(long)L.spawn_y;
-    const double a = geometric_path_distance(C, R.phys, spx, spy, H.goal_x[0], H.goal_y[0], 6.0);
-    const double b = geometric_path_distance(C, R.phys, H.goal_x[0], H.goal_y[0], H.goal_x[1], H.goal_y[1], 12.0);
+    // the positions of a level are int(entity position) (pbrs_potentials.py:962-996); under the goal curriculum they are the manager's
+    // getters as they come, fractions included (:952-955)
+    const bool gv = L.goal_variant && L.obs_switch >= 0;
+    const double swx = gv ? L.ent_x[L.obs_switch] : (double)H.goal_x[0], swy = gv ? L.ent_y[L.obs_switch] : (double)H.goal_y[0];
+    const double exx = gv ? L.ent_x[L.obs_door] : (double)H.goal_x[1], exy = gv ? L.ent_y[L.obs_door] : (double)H.goal_y[1];
+    const double a = geometric_path_distance(C, R.phys, (double)spx, (double)spy, swx, swy, 6.0);
+    const double b = geometric_path_distance(C, R.phys, swx, swy, exx, exy, 12.0);
     out.spawn_to_switch = a; out.switch_to_exit = b; out.combined = a + b;
     if (a == INFINITY || b == INFINITY) {
         out.spawn_to_switch = out.switch_to_exit = out.combined = INFINITY;
@@ -1033,6 +1041,47 @@ bool build_waypoints(const CompiledLevel &L, const ReachBuilt &R, double progres
     return true;
 }
 
+// build_paths_for_level (intermediate_goal_manager.py:158-336) on the ORIGINAL positions: find_ninja_node at the spawn,
+// find_closest_node_to_position(threshold=50) for the switch and the door (not section 23's find_goal_node_closest_to_start),
+// find_shortest_path with a fresh MineProximityCostCache.  An early return leaves what was set before it: a level whose second
+// path is missing keeps its first one, has no combined path and no stages.
+bool goal_stage_table(const CompiledLevel &L, const ReachBuilt &R, double interval, GoalStages &G) {
+    G = GoalStages();
+    if (!(interval > 0.0) || !std::isfinite(interval)) return false;
+    if (L.obs_switch >= 0) {   // exit_switch_position / exit_door_position (nplay_headless.py:578-616); (0, 0) without an exit
+        G.orig[0] = L.ent_x[L.obs_switch]; G.orig[1] = L.ent_y[L.obs_switch];
+        G.orig[2] = L.ent_x[L.obs_door]; G.orig[3] = L.ent_y[L.obs_door];
+    }
+    Graph fin;
+    fin.in = R.in; fin.adj = R.adj;
+    const std::vector<float> no_sdf;
+    const AStarCtx C{&fin, &R.phys, &R.mine_mult, &no_sdf};
+    auto to_path = [](const std::vector<int> &ids, GoalPath &p) {
+        for (int id : ids) { p.x.push_back(reach_node_x(id)); p.y.push_back(reach_node_y(id)); }
+    };
+    [&] {
+        if (R.hdr.n_adj == 0) return;
+        const int spawn = graph_ninja_node(fin, L.spawn_x, L.spawn_y);
+        if (spawn < 0) return;
+        const int sw = find_closest_node(fin, R.phys, G.orig[0], G.orig[1], 50.0, false);
+        if (sw < 0) return;
+        std::vector<int> p0, p1;
+        if (!shortest_path(C, R.phys, spawn, sw, p0)) return;
+        to_path(p0, G.path[0]);
+        const int ex = find_closest_node(fin, R.phys, G.orig[2], G.orig[3], 50.0, false);
+        if (ex < 0) return;
+        if (!shortest_path(C, R.phys, sw, ex, p1)) return;
+        to_path(p1, G.path[1]);
+        G.combined = true;
+    }();
+    if (G.combined) {
+        const double d = goal_path_distance(G.path[0]) + goal_path_distance(G.path[1]);
+        if (d / interval >= (double)GOAL_MAX_STAGES) return false;
+    }
+    goal_finish_stages(G, interval);
+    return true;
+}
+
 void pack_waypoints(const WaypointBuilt &W, WaypointHdr &hdr, std::vector<unsigned char> &blob) {
     std::memset(&hdr, 0, sizeof(hdr));
     hdr.count = (uint32_t)W.rec.size();
@@ -1134,10 +1183,15 @@ int npp_reach_compile_miss(const double *map, int64_t n, int32_t *info, uint8_t 
 
 int npp_reach_rollout_host(const double *map, int64_t n, const double *pos, const int32_t *mines, const uint8_t *new_episode, int count,
                            float *out, int32_t *status, double *raw_out) {
+    return npp_reach_rollout_goal_host(map, n, nullptr, pos, mines, new_episode, count, out, status, raw_out);
+}
+
+int npp_reach_rollout_goal_host(const double *map, int64_t n, const double *goal_xy, const double *pos, const int32_t *mines,
+                                const uint8_t *new_episode, int count, float *out, int32_t *status, double *raw_out) {
     if (!map || !pos || !out || count < 0) return NPP_ERR_INVALID;
     ReachBuilt R;
     std::string err;
-    if (!build_reach(map, n, R, err)) return NPP_ERR_INVALID;
+    if (!build_reach_variant(map, n, goal_xy, R, err)) return NPP_ERR_INVALID;
     ReachHdr H;
     std::vector<unsigned char> blob;
     pack_reach(R, H, blob);
@@ -1168,10 +1222,14 @@ void npp_reward_default_params(NppRewardParams *out) {
 }
 
 int npp_reward_level_constants_host(const double *map, int64_t n, double *out, int32_t *status) {
+    return npp_reward_level_constants_goal_host(map, n, nullptr, out, status);
+}
+
+int npp_reward_level_constants_goal_host(const double *map, int64_t n, const double *goal_xy, double *out, int32_t *status) {
     if (!map || !out) return NPP_ERR_INVALID;
     CompiledLevel L;
     std::string err;
-    if (!compile_level(map, n, L, err)) return NPP_ERR_INVALID;
+    if (!compile_level_variant(map, n, goal_xy, L, err)) return NPP_ERR_INVALID;
     ReachBuilt R;
     build_reach(L, R);
     RewardLevel RL;
@@ -1234,6 +1292,69 @@ int npp_reward_waypoints_host(const double *map, int64_t n, double progress_spac
     return NPP_OK;
 }
 
+void npp_goal_default_params(NppGoalCurriculumParams *out) {
+    if (!out) return;
+    // GoalCurriculumConfig (reward_config.py:953-983): stage_distance_interval, advancement_threshold, rolling_window; the advance
+    // itself is the training callback's there, here the device's when auto_advance is set
+    *out = NppGoalCurriculumParams{100.0, 0.80, 500, 1};
+}
+
+int npp_goal_stages_host(const double *map, int64_t n, double interval, int32_t *num_stages, double *dist, double *orig, int stage_cap,
+                         double *pos, int path_cap, int32_t *path0, int32_t *path1, int32_t *path_len) {
+    if (!map || !num_stages || stage_cap < 0 || path_cap < 0) return NPP_ERR_INVALID;
+    CompiledLevel L;
+    std::string err;
+    if (!compile_level(map, n, L, err)) return NPP_ERR_INVALID;
+    ReachBuilt R;
+    build_reach(L, R);
+    GoalStages G;
+    if (!goal_stage_table(L, R, interval, G)) return NPP_ERR_INVALID;
+    *num_stages = G.num_stages;
+    if (dist) { dist[0] = G.d_switch; dist[1] = G.d_exit; dist[2] = G.d_combined; }
+    if (orig) std::memcpy(orig, G.orig, sizeof(G.orig));
+    for (size_t i = 0; pos && i < G.pos.size() && i < 4 * (size_t)stage_cap; i++) pos[i] = G.pos[i];
+    for (int k = 0; k < 2; k++) {
+        int32_t *dst = k ? path1 : path0;
+        if (path_len) path_len[k] = (int32_t)G.path[k].size();
+        for (size_t i = 0; dst && i < G.path[k].size() && i < (size_t)path_cap; i++) { dst[2 * i] = G.path[k].x[i]; dst[2 * i + 1] = G.path[k].y[i]; }
+    }
+    return NPP_OK;
+}
+
+int npp_goal_apply_host(int32_t *level_words, uint32_t *ring, int32_t *env_words, const int32_t *base_of, const int32_t *stage_of, int n_base,
+                        int n_levels, int n_envs, int window, int need, int auto_advance, const uint8_t *flags, int end_bits, int count,
+                        int32_t *env_level, const int32_t *drawn, uint8_t *changed) {
+    if (!level_words || !ring || !env_words || !base_of || !stage_of || !flags || !env_level || n_base <= 0 || n_levels < n_base || n_envs <= 0 ||
+        window < 1 || window > GOAL_MAX_WINDOW || need < 0)
+        return NPP_ERR_INVALID;
+    for (int l = 0; l < n_levels; l++)
+        if (base_of[l] < 0 || base_of[l] >= n_base || stage_of[l] < -1) return NPP_ERR_INVALID;
+    for (int e = 0; e < n_envs; e++)
+        if (env_level[e] < 0 || env_level[e] >= n_levels || (drawn && (drawn[e] < 0 || drawn[e] >= n_levels))) return NPP_ERR_INVALID;
+    const GoalState g{level_words, ring, env_words, base_of, stage_of, n_base, n_envs, (window + 31) / 32, window, need, auto_advance};
+    // what npp_goal_update_kernel does: the envs in index order, then every level
+    for (int e = 0; e < n_envs; e++) {
+        const bool ended = (flags[e] & end_bits) != 0;
+        if (count) goal_env_row(g, e, flags[e], ended, env_level[e]);
+        else if (ended) goal_env_restart(g, e, env_level[e]);
+        if (count && ended) {
+            const int b = base_of[env_level[e]];
+            if (goal_lv(g, GL_NUM_STAGES, b) > 0) goal_append(g, b, stage_of[env_level[e]], (flags[e] & GOAL_F_WON) != 0);
+        }
+    }
+    for (int l = 0; l < n_base; l++) goal_finish(g, l, count != 0);
+    // the level pool's draw stands between the two kernels; then npp_goal_assign_kernel
+    for (int e = 0; e < n_envs; e++) {
+        const bool ended = (flags[e] & end_bits) != 0;
+        if (ended) {
+            if (drawn) env_level[e] = drawn[e];
+            env_level[e] = goal_level_for(g, env_level[e]);
+        }
+        if (changed) changed[e] = ended && env_level[e] != goal_env(g, GE_PREV, e);
+    }
+    return NPP_OK;
+}
+
 int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params, const double *pos0, const double *pos, const uint8_t *flags,
                     const uint16_t *frames, int count, int end_bits, double *reward_out, double *components_out, uint8_t *kind_out,
                     int32_t *status) {
@@ -1244,6 +1365,15 @@ int npp_reward_host(const double *map, int64_t n, const NppRewardParams *params,
 int npp_reward_host_wp(const double *map, int64_t n, const NppRewardParams *params, const NppWaypointParams *wp, const double *pos0,
                        const double *pos, const uint8_t *flags, const uint16_t *frames, int count, int end_bits, double *reward_out,
                        double *components_out, uint8_t *kind_out, int32_t *status, double *wp_bonus_out, int32_t *wp_info_out) {
+    return npp_reward_goal_host(map, n, nullptr, params, wp, pos0, pos, flags, frames, count, end_bits, reward_out, components_out, kind_out, status,
+                                wp_bonus_out, wp_info_out);
+}
+
+int npp_reward_goal_host(const double *map, int64_t n, const double *goal_xy, const NppRewardParams *params, const NppWaypointParams *wp,
+                         const double *pos0, const double *pos, const uint8_t *flags, const uint16_t *frames, int count, int end_bits,
+                         double *reward_out, double *components_out, uint8_t *kind_out, int32_t *status, double *wp_bonus_out,
+                         int32_t *wp_info_out) {
+    if (goal_xy && wp) return NPP_ERR_UNSUPPORTED;   // the waypoints towards moved goals are not computed
     if (wp) {
         const double v[4] = {wp->collection_radius, wp->out_of_order_scale, wp->progress_scale, wp->progress_spacing};
         for (double x : v)
@@ -1253,7 +1383,7 @@ int npp_reward_host_wp(const double *map, int64_t n, const NppRewardParams *para
     if (!map || !pos0 || count < 0 || (count > 0 && (!pos || !flags || !frames || !reward_out))) return NPP_ERR_INVALID;
     CompiledLevel L;
     std::string err;
-    if (!compile_level(map, n, L, err)) return NPP_ERR_INVALID;
+    if (!compile_level_variant(map, n, goal_xy, L, err)) return NPP_ERR_INVALID;
     ReachBuilt R;
     build_reach(L, R);
     RewardLevel RL;

@@ -36,6 +36,8 @@ struct ReachBuilt : ReachAdjacency {
 struct CompiledLevel;
 void build_adjacency(const CompiledLevel &level, ReachAdjacency &out);
 bool build_reach(const double *map, int64_t n, ReachBuilt &out, std::string &err);
+// the same on a goal-curriculum variant (npp_level.hpp: compile_level_variant; goal_xy == nullptr: the level itself)
+bool build_reach_variant(const double *map, int64_t n, const double *goal_xy, ReachBuilt &out, std::string &err);
 void build_reach(const CompiledLevel &level, ReachBuilt &out);
 // reward mode "pbrs" (npp_reward.hpp): the level's constants; false + note when the level is refused (out.supported = 0)
 struct RewardLevel;

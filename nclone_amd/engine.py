@@ -298,6 +298,65 @@ class NppBatch:
         self._episode_views = None   # (so do the episode statistics: the table has a row per level)
         self._reward_mode, self._reward_pending = 0, False   # (so does reward mode "pbrs": its constants are per level)
         self._reward_waypoints = False
+        self._goal = None   # (and the goal curriculum: its variants were compiled from the old set)
+
+    # ---- goal curriculum (include/npp_amd.h npp_set_goal_curriculum; the reference's IntermediateGoalManager) -----
+    GOAL_LEVEL_WORDS = ("stage", "pending", "num_stages", "variant0", "fill", "head", "wins", "advances", "appended", "stale")
+    GOAL_ENV_WORDS = ("episode_count", "switch_activation_count", "completion_count", "switch_seen", "level_at_end")
+
+    def set_goal_curriculum(self, on=True, stage_distance_interval=100.0, advancement_threshold=0.80, rolling_window=500,
+                            auto_advance=True):
+        """Switch the goal curriculum on or off.  Switching RELOADS the level set (base levels + one variant level per stage), as
+        load_levels does: the pool, the archive, the reward mode and the episode statistics go off, so call it first.  Every env
+        restarts on the stage-0 variant of the base level it played.  Bad numbers raise ValueError with the native message."""
+        q = nat.GoalCurriculumParams(float(stage_distance_interval), float(advancement_threshold), int(rolling_window),
+                                     1 if auto_advance else 0)
+        code = self.lib.npp_set_goal_curriculum(self.h, 1 if on else 0, C.byref(q))
+        if code == nat.NPP_ERR_INVALID:
+            raise ValueError(self.lib.npp_last_error(self.h).decode())
+        nat.check(self.h, code)
+        n_base = self._goal["n_base"] if getattr(self, "_goal", None) else self.n_levels
+        self._archive_meta = self._archive_cells = self._archive_route_views = None
+        self._episode_views = None
+        self._reward_mode, self._reward_pending = 0, False
+        self._reward_waypoints = False
+        self._pool_weights = None
+        self._goal = None
+        self.n_levels = self.lib.npp_num_levels(self.h)
+        if not on:
+            return
+        base_of, stage_of = np.zeros(self.n_levels, dtype=np.int32), np.zeros(self.n_levels, dtype=np.int32)
+        nb = C.c_int()
+        nat.check(self.h, self.lib.npp_goal_tables(self.h, base_of.ctypes.data_as(C.c_void_p), stage_of.ctypes.data_as(C.c_void_p), C.byref(nb)))
+        assert nb.value == n_base
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rw, need = C.c_int(), C.c_int()
+        nat.check(self.h, self.lib.npp_goal_view(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(nb), C.byref(rw), C.byref(need)))
+        lv = _device_tensor(a.value, len(self.GOAL_LEVEL_WORDS) * n_base, torch.int32, self.device).view(-1, n_base)
+        env = _device_tensor(c.value, len(self.GOAL_ENV_WORDS) * self.n, torch.int32, self.device).view(-1, self.n)
+        ring = _device_tensor(b.value, n_base * rw.value, torch.int32, self.device).view(n_base, rw.value)
+        self._goal = {"n_base": n_base, "base_of": base_of, "stage_of": stage_of, "level_words": lv, "env_words": env, "ring": ring,
+                      "need": need.value, "window": int(rolling_window), "interval": float(stage_distance_interval),
+                      "auto_advance": bool(auto_advance)}
+
+    def goal_set_stage(self, stage, level=None):
+        """Deferred as in the reference: the stage takes effect at every env's next episode start; clamped to the last stage."""
+        nat.check(self.h, self.lib.npp_goal_set_stage(self.h, -1 if level is None else int(level), int(stage)))
+
+    def goal_views(self):
+        """The mode's tables and device views (no copy): n_base, base_of / stage_of (numpy int32 [n_levels]), level_words int32
+        [10, n_base] (rows GOAL_LEVEL_WORDS), env_words int32 [5, N] (rows GOAL_ENV_WORDS), ring int32 [n_base, words], need, window."""
+        if getattr(self, "_goal", None) is None:
+            raise ValueError("the goal curriculum is off (set_goal_curriculum)")
+        return self._goal
+
+    def goal_stage_positions(self, level):
+        """-> (num_stages, distances f64[3], original f64[4], positions f64[max(num_stages, 1), 4]) of a base level"""
+        ns = C.c_int32()
+        dist, orig, pos = np.zeros(3), np.zeros(4), np.zeros((1024, 4))
+        nat.check(self.h, self.lib.npp_goal_stage_positions(self.h, int(level), C.byref(ns), dist.ctypes.data_as(C.c_void_p),
+                                                           orig.ctypes.data_as(C.c_void_p), 1024, pos.ctypes.data_as(C.c_void_p)))
+        return ns.value, dist, orig, pos[:max(ns.value, 1)].copy()
 
     def assign_levels(self, level_ids, env_ids=None):
         lv = np.ascontiguousarray(level_ids, dtype=np.int32)

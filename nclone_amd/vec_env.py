@@ -224,9 +224,17 @@ class NppVecEnvironment:
                  observation_mode="full", enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium",
                  augmentation_seed=None, checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False,
                  route_capacity=None, action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False,
-                 waypoint_params=None, episode_stats=False):
+                 waypoint_params=None, episode_stats=False, goal_curriculum=False, goal_curriculum_params=None):
         assert output in ("torch", "numpy")
         self._episode = bool(episode_stats)
+        self._goal = bool(goal_curriculum)
+        self._goal_params = dict(goal_curriculum_params) if goal_curriculum_params else {}
+        if self._goal and reward_waypoints:
+            raise ValueError("goal_curriculum with reward_waypoints=True: the waypoints towards the moved goals are not computed "
+                             "(DESIGN.md 25); reward_mode=\"pbrs\" without them runs on the variant levels")
+        if self._goal and enable_graph_observations:   # no fixture pins the graph rows of a variant level
+            raise ValueError("goal_curriculum with enable_graph_observations: graph observations are not served on the curriculum's "
+                             "variant levels (npp_graph_observation refuses them)")
         if reward_mode not in ("sparse", "pbrs"):
             raise ValueError('reward_mode must be "sparse" or "pbrs", not %r' % (reward_mode,))
         self._pbrs = reward_mode == "pbrs"
@@ -289,6 +297,8 @@ class NppVecEnvironment:
         self._b = NppBatch(self.num_envs, device=device, autoreset=autoreset, outputs=outputs, fast_reset=fast_reset,
                            stream=stream)
         self._b.load_levels(levels)
+        if self._goal:   # first: switching it on reloads the level set with one variant level per (level, stage)
+            self._b.set_goal_curriculum(True, **self._goal_params)
         self._levels, self._map_ids = levels, None   # (seed_archive_from_replays matches replays to levels by map bytes)
         if level_ids is None:
             level_ids = (np.arange(self.num_envs) // 64) % len(levels)
@@ -307,6 +317,8 @@ class NppVecEnvironment:
         if self._pool:
             self._level_seed = int(level_seed) if level_seed is not None else int(np.random.SeedSequence().entropy) & (2**64 - 1)
             self._b.set_level_pool(level_weights, self._level_seed)
+            self._level_ids = None
+        elif self._goal:   # (levels move on the device here too)
             self._level_ids = None
         else:
             with self._b._ctx():   # the fixed assignment, for info["level_id"]
@@ -503,6 +515,9 @@ class NppVecEnvironment:
                 if seq.ndim != 2 or seq.shape[0] != self.num_envs:
                     raise ValueError("checkpoint action_sequence: [K] or [num_envs, K]")
                 K = int(seq.shape[1])
+                if K and self._goal:
+                    raise ValueError("reset(options={'checkpoint': action sequence}) with goal_curriculum: the replay is one launch of "
+                                     "several steps, which the curriculum's bookkeeping refuses (DESIGN.md 25)")
                 if K:
                     fs = self.frame_skip if fs is None else int(fs)
                     with self._b._ctx():
@@ -616,8 +631,65 @@ class NppVecEnvironment:
             raise RuntimeError("set_level_weights: this env was created without level_weights (no level pool)")
         self._b.set_level_pool(weights, self._level_seed)
 
+    # ---- goal curriculum (the reference's set_curriculum_stage, base_environment.py:404-481) -------------
+    def set_curriculum_stage(self, stage, level=None):
+        """The stage of one base level (or of all): deferred to every env's next episode start, clamped to the last stage."""
+        if not self._goal:
+            raise RuntimeError("set_curriculum_stage: this env was created without goal_curriculum")
+        self._b.goal_set_stage(stage, level)
+
+    def goal_curriculum_state(self):
+        """Per base level: stage, num_stages, window_fill, wins (int arrays [L]) and positions [L, 4], the switch x, y and door x, y of
+        the level's current stage (the original ones for a level without stages).  Synchronises."""
+        if not self._goal:
+            raise RuntimeError("goal_curriculum_state: this env was created without goal_curriculum")
+        g = self._b.goal_views()
+        with self._b._ctx():
+            lv = g["level_words"].cpu().numpy()
+        pos = np.zeros((g["n_base"], 4))
+        for l in range(g["n_base"]):
+            ns, _d, orig, p = self._goal_table(l)
+            pos[l] = p[lv[0, l]] if ns > 0 else orig
+        return {"stage": lv[0].copy(), "num_stages": lv[2].copy(), "window_fill": lv[4].copy(), "wins": lv[6].copy(), "positions": pos}
+
+    def _goal_table(self, level):
+        if not hasattr(self, "_goal_tables"):
+            self._goal_tables = {}
+        if level not in self._goal_tables:
+            self._goal_tables[level] = self._b.goal_stage_positions(level)
+        return self._goal_tables[level]
+
+    def _goal_rows(self):
+        """per row of the level set (base levels and variants): num_stages of its base level, the positions it plays, the originals"""
+        if not hasattr(self, "_goal_row_tables"):
+            g = self._b.goal_views()
+            nl = len(g["base_of"])
+            ns, cur, orig = np.zeros(nl, dtype=np.int32), np.zeros((nl, 4)), np.zeros((nl, 4))
+            for r in range(nl):
+                n, _d, o, p = self._goal_table(int(g["base_of"][r]))
+                ns[r], orig[r] = n, o
+                cur[r] = p[g["stage_of"][r]] if g["stage_of"][r] >= 0 else o
+            self._goal_row_tables = (ns, cur, orig)
+        return self._goal_row_tables
+
+    def _goal_info(self, raw_levels):
+        """info["goal_curriculum"]: the fields of get_curriculum_info (intermediate_goal_manager.py:1044-1095) kept here, per env.
+        One copy of the level row and of the counters to the host (synchronises, also under output="torch"), then table look-ups."""
+        g = self._b.goal_views()
+        with self._b._ctx():
+            raw = raw_levels.cpu().numpy() if torch.is_tensor(raw_levels) else np.asarray(raw_levels)
+            env = g["env_words"][:3].cpu().numpy()
+        ns_row, cur_row, orig_row = self._goal_rows()
+        base, stage = g["base_of"][raw], np.maximum(g["stage_of"][raw], 0)
+        ns, cur, orig = ns_row[raw], cur_row[raw], orig_row[raw]
+        return base.astype(np.int32), {
+            "unified_stage": stage.astype(np.int32), "num_stages": ns, "stage_distance_interval": g["interval"],
+            "curriculum_switch_pos": cur[:, :2], "curriculum_exit_pos": cur[:, 2:], "original_switch_pos": orig[:, :2],
+            "original_exit_pos": orig[:, 2:], "episode_count": env[0], "switch_activation_count": env[1],
+            "completion_count": env[2], "at_final_stage": (ns > 0) & (stage >= ns - 1)}
+
     def _level_id(self, numpy):
-        if self._pool:
+        if self._pool or self._goal:
             if numpy:
                 return self._b.env_levels()
             with self._b._ctx():
@@ -958,6 +1030,17 @@ class NppVecEnvironment:
         ep = {"r": f64[0], "l": frames, "steps": steps, "is_success": (flags & 1) != 0, "switch_activated": sw_step != 0,
               "switch_activation_frame": where(sw_step != 0, sw_frames, -1 if self.output == "numpy" else torch.full_like(sw_frames, -1)),
               "level_id": level, "from_checkpoint": (bits & 2) != 0}
+        if self._goal:   # the base level plus the stage the episode was played at (level -1: no episode yet)
+            g = self._b.goal_views()
+            base_of, stage_of = g["base_of"], g["stage_of"]
+            if self.output == "torch":
+                base_of, stage_of = (torch.from_numpy(t).to(self._b.device) for t in (base_of, stage_of))
+                idx = level.clamp(min=0).long()
+            else:
+                idx = np.maximum(level, 0)
+            ep["level_row"] = level
+            ep["level_id"] = where(level >= 0, base_of[idx], -1 if self.output == "numpy" else torch.full_like(level, -1))
+            ep["stage"] = where(level >= 0, stage_of[idx], -1 if self.output == "numpy" else torch.full_like(level, -1))
         if self._pbrs:
             ep["pbrs_total"], ep["terminal_reward"] = f64[1], f64[5]
         return ended != 0, ep
@@ -1010,7 +1093,11 @@ class NppVecEnvironment:
         }
         if "terminal_game_state_stack" in src:
             info["terminal_game_state_stack"] = src["terminal_game_state_stack"]
-        info["level_id"] = self._level_id(self.output == "numpy")
+        info["level_id"] = raw_levels = self._level_id(self.output == "numpy")
+        if self._goal:   # the base level plus the stage; the rows of the level set (variants included) stay in info["level_row"]
+            base, info["goal_curriculum"] = self._goal_info(raw_levels)
+            info["level_row"] = raw_levels
+            info["level_id"] = base if self.output == "numpy" else torch.from_numpy(base).to(self._b.device)
         if self._mask_on:
             info.update(self._mask_info(src, (flags & 11) != 0))
         if self._pbrs:
@@ -1023,7 +1110,7 @@ class NppVecEnvironment:
             info["waypoints"] = {"bonus": wb, "index": wi[:, 0], "next_expected": wi[:, 1], "collected": wi[:, 2]}
         if self._episode:
             info["_episode"], info["episode"] = self._episode_info()
-        return self._with_graph(self._obs(src), info["level_id"]), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
+        return self._with_graph(self._obs(src), raw_levels), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
         """actions: int array/tensor [N] in 0..5.  Returns (obs, reward, terminated, truncated, info) with batch dims."""
@@ -1089,6 +1176,9 @@ class NppEnvironment:
     action_masking_mode / set_action_masking_mode(mode): NppVecEnvironment's path-direction action masking; info["path_direction"] is
     an int, and the step that ends the episode adds info["deterministic_mask_applied_count"] / info["deterministic_mask_rate"].
     reward_mode / reward_params / set_reward_params(**kw): NppVecEnvironment's reward mode "pbrs"; info["pbrs_components"] is (6,).
+    goal_curriculum=True / goal_curriculum_params / set_curriculum_stage(stage) / goal_curriculum_state(): NppVecEnvironment's goal
+    curriculum.  This class never auto-resets and the curriculum's counters are kept behind auto-resetting steps only,
+    so info["goal_curriculum"]'s three counters stay 0 and the stage moves only through set_curriculum_stage.
     episode_stats=True: the step that ends the episode adds the reference's info["r"] (the return), info["l"] (frames),
     info["is_success"] and info["switch_activation_frame"] (base_environment.py:1163-1242; NppVecEnvironment's episode statistics)."""
 
@@ -1099,7 +1189,7 @@ class NppEnvironment:
                  enable_augmentation=False, augmentation_p=0.5, augmentation_intensity="medium", augmentation_seed=None,
                  checkpoint_slots=0, checkpoint_cells=False, checkpoint_seed=0, record_routes=False, route_capacity=None,
                  action_masking_mode=None, reward_mode="sparse", reward_params=None, reward_waypoints=False, waypoint_params=None,
-                 episode_stats=False):
+                 episode_stats=False, goal_curriculum=False, goal_curriculum_params=None):
         spaces.check_frame_augmentation(augmentation_p, augmentation_intensity)
         spaces.check_observation_mode(
             observation_mode, enable_visual_observations=enable_visual_observations,
@@ -1126,10 +1216,18 @@ class NppEnvironment:
                                     checkpoint_slots=checkpoint_slots, checkpoint_cells=checkpoint_cells,
                                     checkpoint_seed=checkpoint_seed, record_routes=record_routes, route_capacity=route_capacity,
                                     action_masking_mode=action_masking_mode, reward_mode=reward_mode, reward_params=reward_params,
-                                    reward_waypoints=reward_waypoints, waypoint_params=waypoint_params, episode_stats=episode_stats)
+                                    reward_waypoints=reward_waypoints, waypoint_params=waypoint_params, episode_stats=episode_stats,
+                                    goal_curriculum=goal_curriculum, goal_curriculum_params=goal_curriculum_params)
         self.action_space = self._v.single_action_space
         self.observation_space = self._v.single_observation_space
         self.frame_skip = frame_skip
+
+    def set_curriculum_stage(self, stage):
+        """goal_curriculum=True: the stage from the next reset on (the reference's method, base_environment.py:404-481)"""
+        self._v.set_curriculum_stage(stage, 0)
+
+    def goal_curriculum_state(self):
+        return self._v.goal_curriculum_state()
 
     @staticmethod
     def _unbatch(obs):
@@ -1195,6 +1293,10 @@ class NppEnvironment:
             w = info["waypoints"]
             out_info["waypoints"] = {"bonus": float(w["bonus"][0]), "index": int(w["index"][0]), "next_expected": int(w["next_expected"][0]),
                                      "collected": int(w["collected"][0])}
+        if "goal_curriculum" in info:   # get_curriculum_info's fields of this env (positions as (x, y) tuples)
+            gc = info["goal_curriculum"]
+            out_info["goal_curriculum"] = {k: (v if np.isscalar(v) else (tuple(float(x) for x in v[0]) if np.ndim(v) == 2 else v[0].item()))
+                                           for k, v in gc.items()}
         if "_episode" in info and bool(info["_episode"][0]):
             ep = info["episode"]
             out_info.update({"r": float(ep["r"][0]), "l": int(ep["l"][0]), "is_success": bool(ep["is_success"][0]),
