@@ -759,6 +759,48 @@ int npp_env_level_view(npp_handle h, const int32_t **d_levels);
 int npp_level_pool_draw_host(const double *weights, int n_levels, uint64_t seed, const int32_t *envs, const uint32_t *counts, int count,
                              int32_t *out);
 
+/* Evaluation sweep: a fixed list of levels, each played an exact number of times, one outcome per episode (the reference's eval_mode:
+ * EnvMapLoader walks its test suite in order, env_map_loader.py:138-162; create_evaluation_env).  A third assignment policy beside the
+ * level pool's draw and the goal curriculum's variant: take the next job from a list.  The rule (csrc/npp_sweep.hpp):
+ *   jobs      i32[n_jobs] level ids in the caller's order; job j is ONE episode on level jobs[j].
+ *   state     counters i32[3] = next (jobs handed out), done (jobs finished), n_jobs; env_job i32[n_envs], the job an env plays, -1 =
+ *             idle; one result row per job as planes i32[NPP_SWEEP_RI][n_jobs] -- the six words of the finished episode
+ *             (NPP_EP_STEPS .. NPP_EP_BITS), the flags byte of its ending step (NPP_SWEEP_R_FLAGS), the env that played it
+ *             (NPP_SWEEP_R_ENV, -1 until then) and status (NPP_SWEEP_R_STATUS: 0 pending, 1 done) -- and f64[NPP_SWEEP_RD][n_jobs], the
+ *             return and the six component sums.
+ *   start     env e < min(n_envs, n_jobs) takes job e, is put on level jobs[e] and reset as by npp_assign_levels; the other envs are
+ *             idle and keep their level; next = min(n_envs, n_jobs).
+ *   step      after every npp_step, in the place of the pool's draw: the envs whose flags show won, dead or truncated AND that hold a
+ *             job, taken in env order, get ranks 0, 1, ...; the env of rank r takes job j = next + r (next as before the step): with
+ *             j < n_jobs it is assigned level jobs[j] exactly as the pool assigns a drawn level (reset, observation rows rewritten
+ *             and the level's dynamic truncation limit when the level is another one; the step kernel's auto-reset stands when it
+ *             is the same), otherwise it goes idle: it plays on where it is and nothing it does is recorded.  next += the number
+ *             of ranked envs, so next runs past n_jobs by the envs that found the queue dry.  One workgroup ranks the row without
+ *             atomics: the same bits in every run.  npp_step_many, npp_tick and npp_reset never assign.
+ *   collect   npp_episode_accumulate with n_steps == 1 copies, for every env whose job ended in the step, the finished half of its
+ *             episode record into the job's row and adds 1 to done.  The contract is ONE npp_episode_accumulate behind EVERY npp_step
+ *             while a sweep runs; the sweep is over when done == n_jobs.
+ * npp_sweep_start(h, jobs, n_jobs): NPP_ERR_STATE, each with its own text: n_jobs <= 0; episode statistics off; a handle without
+ *   NPP_FLAG_AUTORESET; the level pool on; the goal curriculum on; a checkpoint archive exists; an entity repositioned with
+ *   npp_set_entity_pos.  NPP_ERR_INVALID for a job outside the loaded levels.  A start while a sweep runs begins a new one.
+ * While a sweep runs, NPP_ERR_STATE: npp_set_level_pool, npp_set_goal_curriculum, npp_archive_create, npp_demo_create / npp_demo_play,
+ *   npp_archive_seed, npp_assign_levels, a repositioning npp_set_entity_pos, npp_snapshot and npp_restore (a restored env's job would be
+ *   undefined).  What holds with the level pool on holds here: no LDS level staging, the zoo kernels run when any env or any job level
+ *   has zoo entities, the step-variant autotuner decides once, npp_get_env_levels reads back.
+ * npp_sweep_stop(h): the sweep ends, every env keeps the level it plays, and the handle steps with the bytes of one that never had a
+ *   sweep.  npp_load_levels and npp_set_episode_stats(h, 0) end it as well.  Without a sweep nothing is allocated or launched.
+ * npp_sweep_view: device pointers (any may be NULL), valid until the next npp_sweep_start / npp_load_levels and rewritten in stream
+ *   order; they outlive npp_sweep_stop.  NPP_ERR_STATE before the first start.
+ * npp_sweep_assign_host (host-only, for tests): one `step` of the rule on host arrays -- counters i32[3] in / out; level_trunc i32[n_levels]
+ *   or NULL (then trunc is not touched).  NPP_ERR_INVALID for a negative size, a missing array, an env_job outside -1 .. n_jobs - 1. */
+enum { NPP_SWEEP_R_FLAGS = 6, NPP_SWEEP_R_ENV = 7, NPP_SWEEP_R_STATUS = 8, NPP_SWEEP_RI = 9, NPP_SWEEP_RD = 7 };
+int npp_sweep_start(npp_handle h, const int32_t *jobs, int n_jobs);
+int npp_sweep_stop(npp_handle h);
+int npp_sweep_view(npp_handle h, const int32_t **d_env_job, const int32_t **d_results_i32, const double **d_results_f64,
+                   const int32_t **d_counters /* next | done | n_jobs */, int *n_jobs);
+int npp_sweep_assign_host(const uint8_t *flags, int end_bits, int n_envs, const int32_t *jobs, int n_jobs, int32_t *counters, int32_t *env_job,
+                          int32_t *prev_job, int32_t *env_level, int32_t *trunc, const int32_t *level_trunc, int n_levels, uint8_t *changed);
+
 /* Graph observations for the GCN encoder: graph_node_feats, graph_edge_index, graph_node_mask, graph_edge_mask of the reference's
  * training Dict (OBSERVATION_SPACE_README.md; gym_environment/npp_environment.py:245-271).  The reference builds the graph at every
  * reset from the freshly loaded level (mixins/graph_mixin.py:96-109, 340-376) and keeps it for the episode, so it is a constant per

@@ -54,6 +54,7 @@ EXPORTS = [
     "npp_goal_default_params", "npp_set_goal_curriculum", "npp_goal_set_stage", "npp_goal_view", "npp_goal_tables", "npp_goal_stage_positions",
     "npp_goal_stages_host", "npp_goal_apply_host", "npp_compile_level_segments_goal", "npp_compile_level_entities_goal",
     "npp_reach_rollout_goal_host", "npp_path_direction_goal_host", "npp_reward_level_constants_goal_host", "npp_reward_goal_host",
+    "npp_sweep_start", "npp_sweep_stop", "npp_sweep_view", "npp_sweep_assign_host",
 ]
 
 
@@ -253,6 +254,10 @@ def lib():
     L.npp_reward_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 6
     L.npp_reach_rollout_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3
     L.npp_path_direction_goal_host.argtypes = [C.POINTER(C.c_double), C.c_int64] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+    L.npp_sweep_start.argtypes = [H, C.c_void_p, C.c_int]
+    L.npp_sweep_stop.argtypes = [H]
+    L.npp_sweep_view.argtypes = [H] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int)]
+    L.npp_sweep_assign_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
     for name in EXPORTS:
         if name != "npp_last_error":
             getattr(L, name).restype = C.c_int

@@ -210,5 +210,12 @@ class NppAsyncVecEnvironment:
         self.step_async(actions)
         return self.step_wait()
 
+    def start_evaluation(self, levels=None, episodes_per_level=1):
+        raise NotImplementedError("NppAsyncVecEnvironment has no evaluation sweep (start_evaluation / evaluate): the job list belongs to "
+                                  "one handle and its sub-batches are handles of their own; NppVecEnvironment(episode_stats=True) has it")
+
+    def evaluate(self, policy, levels=None, episodes_per_level=1, max_steps=None):
+        self.start_evaluation(levels, episodes_per_level)
+
     def close(self):
         self.ab.close()

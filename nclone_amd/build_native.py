@@ -10,10 +10,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libnpp_amd.so")
-SOURCES = ["npp_kernels.hip", "npp_render.hip", "npp_stack.hip", "npp_pool.hip", "npp_augment.hip", "npp_reach_kernel.hip", "npp_graph.hip", "npp_archive.hip", "npp_cells.hip", "npp_route.hip", "npp_episode.hip", "npp_pathmask.hip", "npp_reward.hip", "npp_waypoint.hip", "npp_demo.hip", "npp_seed.hip", "npp_goal.hip", "npp_capi.cpp", "npp_level.cpp", "npp_reach.cpp",
+SOURCES = ["npp_kernels.hip", "npp_render.hip", "npp_stack.hip", "npp_pool.hip", "npp_augment.hip", "npp_reach_kernel.hip", "npp_graph.hip", "npp_archive.hip", "npp_cells.hip", "npp_route.hip", "npp_episode.hip", "npp_pathmask.hip", "npp_reward.hip", "npp_waypoint.hip", "npp_demo.hip", "npp_seed.hip", "npp_goal.hip", "npp_sweep.hip", "npp_capi.cpp", "npp_level.cpp", "npp_reach.cpp",
            "npp_graph.cpp", "npp_host.cpp"]
 HEADERS = ["npp_internal.hpp", "npp_level.hpp", "npp_tilequery.hpp", "npp_zoo.hpp", "npp_reach.hpp", "npp_reach_build.hpp", "npp_reach_features.hpp",
-           "npp_host.hpp", "npp_zoo_layout.hpp", "npp_pool.hpp", "npp_augment.hpp", "npp_graph.hpp", "npp_minimal.hpp", "npp_archive.hpp", "npp_cells.hpp", "npp_route.hpp", "npp_episode.hpp", "npp_pathmask.hpp", "npp_reward.hpp", "npp_waypoint.hpp", "npp_demo.hpp", "npp_seed.hpp", "npp_goal.hpp", "npp_state.hpp",
+           "npp_host.hpp", "npp_zoo_layout.hpp", "npp_pool.hpp", "npp_augment.hpp", "npp_graph.hpp", "npp_minimal.hpp", "npp_archive.hpp", "npp_cells.hpp", "npp_route.hpp", "npp_episode.hpp", "npp_pathmask.hpp", "npp_reward.hpp", "npp_waypoint.hpp", "npp_demo.hpp", "npp_seed.hpp", "npp_goal.hpp", "npp_sweep.hpp", "npp_state.hpp",
            "npp_reach_tables.inc", os.path.join("..", "..", "include", "npp_amd.h")]
 
 
@@ -51,7 +51,7 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
              ("npp_reach_kernel.hip", [], "npp_reach_kernel.o"), ("npp_reach.cpp", [], "npp_reach.o"), ("npp_host.cpp", [], "npp_host.o"),
              ("npp_graph.hip", [], "npp_graph_kernel.o"), ("npp_graph.cpp", [], "npp_graph.o"), ("npp_archive.hip", [], "npp_archive.o"),
              ("npp_cells.hip", [], "npp_cells.o"), ("npp_route.hip", [], "npp_route.o"), ("npp_episode.hip", [], "npp_episode.o"), ("npp_pathmask.hip", [], "npp_pathmask.o"), ("npp_reward.hip", [], "npp_reward.o"), ("npp_waypoint.hip", [], "npp_waypoint.o"), ("npp_demo.hip", [], "npp_demo.o"),
-             ("npp_seed.hip", [], "npp_seed.o"), ("npp_goal.hip", [], "npp_goal.o")]
+             ("npp_seed.hip", [], "npp_seed.o"), ("npp_goal.hip", [], "npp_goal.o"), ("npp_sweep.hip", [], "npp_sweep.o")]
     procs = []
     for src, extra, obj in jobs:
         cmd = [hipcc] + flags + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(objdir, obj)]

@@ -24,6 +24,7 @@
 #include "npp_reward.hpp"
 #include "npp_waypoint.hpp"
 #include "npp_seed.hpp"
+#include "npp_sweep.hpp"
 
 using namespace npp;
 
@@ -232,6 +233,17 @@ struct Goal {
     DevBuf<uint32_t> ring;
 };
 
+// evaluation sweep (npp_sweep_start; the rule: npp_sweep.hpp, the kernels: npp_sweep.hip): with it on, the device changes env_level /
+// trunc after a step as the level pool does, and shares the pool's changed mask and flags row.  Allocated by npp_sweep_start; the
+// result planes outlive npp_sweep_stop (npp_sweep_view) and go with the next start or level set.
+struct Sweep {
+    bool on = false;
+    int n_jobs = 0;
+    std::vector<double> w;                     // [n_levels] 1.0 for a level some job names: make_plan's "any level an env may play"
+    DevBuf<int32_t> jobs, counters, env_job, prev_job, res_i32;
+    DevBuf<double> res_f64;
+};
+
 // minimal observation (npp_set_minimal_observation / npp_minimal_observation): its mine columns are read from the spatial_context
 // rows of the step kernel, so with the mode on every step / observe launch writes them -- into the caller's d_spatial_context, or
 // into `sc` when the caller's npp_step_out has none
@@ -402,6 +414,7 @@ struct npp_handle_s {
     Demo demo;
     Episode ep;
     Goal goal;
+    Sweep sweep;
 };
 
 
@@ -627,7 +640,7 @@ int pull_levels(npp_handle h);
 void plan_geometry(npp_handle h, bool keep_tuning = false) {
     (void)pull_levels(h);   // (a failure leaves the mirror as it was and is reported by the next call that syncs)
     const Plan p = make_plan(h->ls, h->n, h->env_level, h->lanes_per_env, h->waves_per_block, h->n_ovr > 0,
-                             h->pool.on ? &h->pool.w : (h->goal.on ? &h->goal.all : nullptr));
+                             h->pool.on ? &h->pool.w : (h->goal.on ? &h->goal.all : (h->sweep.on ? &h->sweep.w : nullptr)));
     // a new plan (level set, assignment, geometry, zoo kernels on / off) restarts npp_step's variant autotuner; a plan that comes
     // out the same (npp_restore of a snapshot with the same overrides) keeps the decision
     const bool same_plan = keep_tuning && p.g == h->plan.g && p.wpb == h->plan.wpb && p.zoo_active == h->plan.zoo_active;
@@ -1047,6 +1060,28 @@ GoalArgs goal_args(npp_handle h, const uint8_t *d_flags, int bits, int count) {
     return a;
 }
 
+SweepArgs sweep_args(npp_handle h, const uint8_t *d_flags, int bits) {
+    const Sweep &S = h->sweep;
+    SweepArgs a{};
+    a.n = h->n;
+    a.n_jobs = S.n_jobs;
+    a.jobs = S.jobs.get();
+    a.counters = S.counters.get();
+    a.env_job = S.env_job.get();
+    a.prev_job = S.prev_job.get();
+    a.flags = d_flags;
+    a.bits = bits;
+    a.env_level = h->env.level.get();
+    a.trunc = h->env.trunc.get();
+    a.level_trunc = h->dyn_trunc ? h->ls.d_level_trunc.get() : nullptr;
+    a.changed = h->pool.changed.get();
+    a.ep_i32 = h->ep.i32.get();
+    a.ep_f64 = h->ep.f64.get();
+    a.res_i32 = S.res_i32.get();
+    a.res_f64 = S.res_f64.get();
+    return a;
+}
+
 // (goal curriculum) With the mode on the same call runs its two launches around the draw: the bookkeeping of the envs that ended
 // (counted only behind a step: `out` given) in front of it, the assignment to the variant of the level's stage behind it; `draw` =
 // false leaves the pool's draw out (npp_reset: the envs restart on the level they have, at its current stage).
@@ -1067,6 +1102,9 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
     p.level_trunc = h->dyn_trunc ? L.d_level_trunc.get() : nullptr;
     p.changed = h->pool.changed.get();
     if (draw && h->pool.on) HIP_TRY(h, launch_pool_draw(p, h->stream));
+    // (evaluation sweep) behind a step the next job of the list takes the place of the draw; npp_sweep_start comes here with the
+    // changed mask it wrote itself
+    if (h->sweep.on && out) HIP_TRY(h, launch_sweep_assign(sweep_args(h, d_flags, bits), h->stream));
     if (h->goal.on) HIP_TRY(h, launch_goal_assign(goal_args(h, d_flags, bits, out ? 1 : 0), h->stream));
     h->pool.dirty = true;
     KernelArgs a = base_args(h);
@@ -1095,6 +1133,16 @@ int pool_redraw(npp_handle h, const uint8_t *d_flags, int bits, const npp_step_o
         if (int rc = reward_restart(h, h->pool.changed.get())) return rc;
         if (int rc = episode_event(h, EP_EV_RESET, h->pool.changed.get())) return rc;
     }
+    return NPP_OK;
+}
+
+// (evaluation sweep) the sweep ends: every env keeps the level it plays now, the assignment is the host's again, and the result
+// planes stay for npp_sweep_view.  The caller is on the device with the streams joined.
+int sweep_end(npp_handle h) {
+    if (!h->sweep.on) return NPP_OK;
+    if (int rc = pull_levels(h)) return rc;
+    h->sweep.on = false;
+    plan_geometry(h);
     return NPP_OK;
 }
 
@@ -1209,6 +1257,7 @@ int npp_sync(npp_handle h) {
 int npp_snapshot(npp_handle h) {
     if (!h) return NPP_ERR_INVALID;
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_snapshot: no levels loaded");
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, "npp_snapshot: an evaluation sweep is running (npp_sweep_stop first)");
     ON_DEVICE_JOINED(h);
     Snapshot &s = h->snap;
     const ArchiveLayout lay = record_layout(h);
@@ -1228,6 +1277,7 @@ int npp_snapshot(npp_handle h) {
 int npp_restore(npp_handle h, const uint8_t *env_mask) {
     if (!h) return NPP_ERR_INVALID;
     const Snapshot &s = h->snap;
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, "npp_restore: an evaluation sweep is running and a restored env's job would be undefined (npp_sweep_stop first)");
     if (!s.rec || s.gen != h->assign_gen) return fail(h, NPP_ERR_STATE, "npp_restore: no snapshot for the current level assignment");
     ON_DEVICE_JOINED(h);
     ArchiveArgs a = record_args(h, s.lay);   // identity mode: env e <- record e under the mask
@@ -1267,6 +1317,7 @@ namespace {
 // know what a record's tables belong to
 int archive_refusal(npp_handle h, const char *who) {
     if (h->pool.on) return fail(h, NPP_ERR_STATE, std::string(who) + ": the level pool is on (npp_set_level_pool)");
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, std::string(who) + ": an evaluation sweep is running (npp_sweep_stop first)");
     if (h->n_ovr) return fail(h, NPP_ERR_STATE, std::string(who) + ": an exit switch / door is repositioned (npp_set_entity_pos)");
     return NPP_OK;
 }
@@ -1432,6 +1483,8 @@ int npp_set_episode_stats(npp_handle h, int enable) {
         e.on = true;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // queued accumulations / events still use the old planes
+    if (!enable && h->sweep.on)   // (evaluation sweep) its results are the episode records: without them it ends
+        if (int rc = sweep_end(h)) return rc;
     h->ep = std::move(e);
     if (h->ep.on) {
         HIP_TRY(h, hipMemsetAsync(h->ep.table.get(), 0, h->ep.table.bytes(), h->stream));
@@ -1457,6 +1510,8 @@ int npp_episode_accumulate(npp_handle h, const uint8_t *d_flags, const uint16_t 
     a.comps = d_components;
     a.ended = d_ended;
     HIP_TRY(h, launch_episode(a, h->stream));
+    // (evaluation sweep) the finished half of the records of the envs whose job ended in the step, into the jobs' result rows
+    if (h->sweep.on && n_steps == 1) HIP_TRY(h, launch_sweep_collect(sweep_args(h, d_flags, 0), h->stream));
     return NPP_OK;
 }
 
@@ -1636,6 +1691,7 @@ int npp_set_goal_curriculum(npp_handle h, int enable, const NppGoalCurriculumPar
     if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_set_goal_curriculum: NULL handle");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_goal_curriculum: no levels loaded");
     if (!enable && !h->goal.on) return NPP_OK;
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, "npp_set_goal_curriculum: an evaluation sweep is running (npp_sweep_stop first)");
     NppGoalCurriculumParams q;
     if (params) q = *params; else npp_goal_default_params(&q);
     if (enable && (!(q.stage_distance_interval > 0.0) || !std::isfinite(q.stage_distance_interval) || !(q.advancement_threshold >= 0.0) ||
@@ -1905,6 +1961,7 @@ static int install_levels(npp_handle h, LevelSet &next) {
     h->pool.on = h->pool.ever = h->pool.dirty = false;   // (its weights were per level of the old set)
     h->pool.w.clear();
     h->goal = Goal();    // (goal curriculum) the variants belonged to the old set: the mode is off
+    h->sweep = Sweep();  // (evaluation sweep) its jobs named levels of the old set: it ends, and its results go
     h->ovr.assign(h->n, 0);
     h->n_ovr = 0;
     h->assign_gen++;
@@ -1921,6 +1978,7 @@ int npp_assign_levels(npp_handle h, const int32_t *env_ids, const int32_t *level
     if (!h || !level_ids || n <= 0) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_assign_levels: no levels loaded");
     if (!env_ids && n != h->n) return fail(h, NPP_ERR_INVALID, "npp_assign_levels: env_ids == NULL needs n == n_envs");
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, "npp_assign_levels: an evaluation sweep is running and assigns the levels itself (npp_sweep_stop first)");
     ON_DEVICE_JOINED(h);
     if (int rc = pull_levels(h)) return rc;   // (level pool) the whole mirror is uploaded below
     std::vector<int32_t> mapped;
@@ -1992,7 +2050,7 @@ int npp_set_dynamic_truncation(npp_handle h, int enable) {
     h->dyn_trunc = enable != 0;
     if (!h->dyn_trunc || h->ls.levels.empty()) return NPP_OK;
     ON_DEVICE_JOINED(h);
-    if (h->pool.on)
+    if (h->pool.on || h->sweep.on)
         if (int rc = upload_level_trunc(h)) return rc;
     return apply_dynamic_truncation(h, nullptr);
 }
@@ -2009,6 +2067,7 @@ int npp_set_level_pool(npp_handle h, const double *weights, int n_levels, uint64
         return NPP_OK;
     }
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: no levels loaded");
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, "npp_set_level_pool: an evaluation sweep is running (npp_sweep_stop first)");
     std::vector<double> padded;
     if (h->goal.on && n_levels == h->ls.n_base) {   // (goal curriculum) one weight per BASE level: the variants are never drawn
         padded.assign(weights, weights + n_levels);
@@ -2057,6 +2116,93 @@ int npp_draw_levels(npp_handle h, const uint8_t *env_mask) {
     else HIP_TRY(h, hipMemsetAsync(d_mask, 1, (size_t)h->n, h->stream));
     if (int rc = pool_redraw(h, d_mask, 0xff, nullptr)) return rc;
     if (env_mask) HIP_TRY(h, hipStreamSynchronize(h->stream));   // env_mask is caller memory: finish the copy
+    return NPP_OK;
+}
+
+int npp_sweep_start(npp_handle h, const int32_t *jobs, int n_jobs) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_start: NULL handle");
+    if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_sweep_start: no levels loaded");
+    if (n_jobs <= 0) return fail(h, NPP_ERR_STATE, "npp_sweep_start: n_jobs must be > 0 (an empty job list has nothing to play)");
+    if (!jobs) return fail(h, NPP_ERR_INVALID, "npp_sweep_start: jobs is NULL");
+    const int n_levels = (int)h->ls.levels.size(), n = h->n;
+    for (int j = 0; j < n_jobs; j++)
+        if (jobs[j] < 0 || jobs[j] >= n_levels)
+            return fail(h, NPP_ERR_INVALID, "npp_sweep_start: job " + std::to_string(j) + " names level " + std::to_string(jobs[j]) +
+                                                ", outside the " + std::to_string(n_levels) + " loaded levels");
+    if (!h->ep.on) return fail(h, NPP_ERR_STATE, "npp_sweep_start: episode statistics are off and the results are their records (npp_set_episode_stats)");
+    if (!(h->flags & NPP_FLAG_AUTORESET)) return fail(h, NPP_ERR_STATE, "npp_sweep_start: the handle was created without NPP_FLAG_AUTORESET and jobs are handed out at the auto-reset");
+    if (h->pool.on) return fail(h, NPP_ERR_STATE, "npp_sweep_start: the level pool is on (npp_set_level_pool(h, NULL, 0, 0) first)");
+    if (h->goal.on) return fail(h, NPP_ERR_STATE, "npp_sweep_start: the goal curriculum is on (npp_set_goal_curriculum(h, 0, NULL) first)");
+    if (h->ar.n_slots) return fail(h, NPP_ERR_STATE, "npp_sweep_start: a checkpoint archive exists (npp_archive_create(h, 0) first)");
+    if (h->n_ovr) return fail(h, NPP_ERR_STATE, "npp_sweep_start: an exit switch / door is repositioned (npp_set_entity_pos)");
+    ON_DEVICE_JOINED(h);
+    if (int rc = sweep_end(h)) return rc;   // a second start begins clean
+    if (int rc = pull_levels(h)) return rc;
+    const size_t N = (size_t)n, J = (size_t)n_jobs;
+    Sweep S;   // complete or not at all: a failed allocation leaves the handle without a sweep and with its old results
+    if (S.jobs.alloc(J) != hipSuccess || S.counters.alloc(3) != hipSuccess || S.env_job.alloc(N) != hipSuccess || S.prev_job.alloc(N) != hipSuccess ||
+        S.res_i32.alloc((size_t)SWEEP_RI * J) != hipSuccess || S.res_f64.alloc((size_t)SWEEP_RD * J) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, NPP_ERR_HIP, "npp_sweep_start: hipMalloc of the state of " + std::to_string(n_jobs) + " jobs failed");
+    }
+    Pool &P = h->pool;
+    if (!P.changed) {   // the changed mask and the flags row the sweep shares with the level pool
+        HIP_TRY(h, P.changed.alloc(N));
+        HIP_TRY(h, P.flags.alloc(N));
+        HIP_TRY(h, hipMemset(P.flags.get(), 0, N));
+    }
+    if (h->dyn_trunc)
+        if (int rc = upload_level_trunc(h)) return rc;
+    S.n_jobs = n_jobs;
+    S.w.assign((size_t)n_levels, 0.0);
+    for (int j = 0; j < n_jobs; j++) S.w[jobs[j]] = 1.0;
+    // Start: env e < min(n, J) takes job e and is put on its level; the others are idle and keep theirs
+    std::vector<int32_t> env_job(N), prev(N, -1), res((size_t)SWEEP_RI * J, 0);
+    std::vector<uint8_t> mask(N, 0);
+    for (int e = 0; e < n; e++) {
+        const int j = env_job[e] = sweep_start_job(e, n_jobs);
+        if (j < 0) continue;
+        mask[e] = 1;
+        h->env_level[e] = jobs[j];
+        if (h->dyn_trunc) h->trunc[e] = h->ls.level_trunc[jobs[j]];
+    }
+    for (size_t j = 0; j < J; j++) res[(size_t)SWEEP_R_ENV * J + j] = -1;
+    const int32_t counters[3] = {n < n_jobs ? n : n_jobs, 0, n_jobs};
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(S.jobs.get(), jobs, S.jobs.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(S.counters.get(), counters, sizeof(counters), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(S.env_job.get(), env_job.data(), S.env_job.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(S.prev_job.get(), prev.data(), S.prev_job.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(S.res_i32.get(), res.data(), S.res_i32.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(S.res_f64.get(), 0, S.res_f64.bytes()));
+    HIP_TRY(h, hipMemcpy(h->env.level.get(), h->env_level.data(), h->env.level.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->env.trunc.get(), h->trunc.data(), h->env.trunc.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(P.changed.get(), mask.data(), N, hipMemcpyHostToDevice));
+    h->sweep = std::move(S);
+    h->sweep.on = true;
+    h->assign_gen++;   // (a snapshot of the old assignment no longer restores)
+    plan_geometry(h);
+    // every env with a job is reset as after npp_assign_levels, under the mask written above (no draw, no assignment launch)
+    return pool_redraw(h, nullptr, 0, nullptr, false);
+}
+
+int npp_sweep_stop(npp_handle h) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_stop: NULL handle");
+    if (!h->sweep.on) return NPP_OK;
+    ON_DEVICE_JOINED(h);
+    return sweep_end(h);
+}
+
+int npp_sweep_view(npp_handle h, const int32_t **d_env_job, const int32_t **d_results_i32, const double **d_results_f64,
+                   const int32_t **d_counters, int *n_jobs) {
+    if (!h) return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_view: NULL handle");
+    const Sweep &S = h->sweep;
+    if (!S.n_jobs) return fail(h, NPP_ERR_STATE, "npp_sweep_view: no evaluation sweep was started on this level set (npp_sweep_start)");
+    if (d_env_job) *d_env_job = S.env_job.get();
+    if (d_results_i32) *d_results_i32 = S.res_i32.get();
+    if (d_results_f64) *d_results_f64 = S.res_f64.get();
+    if (d_counters) *d_counters = S.counters.get();
+    if (n_jobs) *n_jobs = S.n_jobs;
     return NPP_OK;
 }
 
@@ -2279,7 +2425,7 @@ extern "C" {
 int npp_step(npp_handle h, const uint8_t *d_actions, int frame_skip, const npp_step_out *out) {
     if (!h || !d_actions || frame_skip <= 0) return fail(h, NPP_ERR_INVALID, "npp_step: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_step: no levels loaded");
-    const bool pool = (h->pool.on || h->goal.on) && (h->flags & NPP_FLAG_AUTORESET);   // (goal curriculum: the same tail)
+    const bool pool = (h->pool.on || h->goal.on || h->sweep.on) && (h->flags & NPP_FLAG_AUTORESET);   // (goal curriculum, evaluation sweep: the same tail)
     if (!pool && !h->rt.cap && !h->pm.mode && !h->rw.mode) return step_impl(h, d_actions, frame_skip, out);
     npp_step_out o;
     std::memset(&o, 0, sizeof(o));
@@ -2563,6 +2709,7 @@ int npp_set_entity_pos(npp_handle h, int env, int kind, double x, double y) {
     if (!h || env < 0 || env >= h->n || (kind != 0 && kind != 1)) return fail(h, NPP_ERR_INVALID, "npp_set_entity_pos: bad arguments");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: no levels loaded");
     if (h->pool.on) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: the level pool is on (npp_set_level_pool)");
+    if (h->sweep.on && x == x && y == y) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: an evaluation sweep is running (npp_sweep_stop first)");
     if (h->ar.n_slots && x == x && y == y) return fail(h, NPP_ERR_STATE, "npp_set_entity_pos: a checkpoint archive exists (npp_archive_create)");
     {
         ON_DEVICE_JOINED(h);
@@ -2908,6 +3055,7 @@ const char *player_refusal(npp_handle h) {
     if (h->pool.on) return "the level pool is on (npp_set_level_pool(h, NULL, 0, 0) first)";
     if (h->goal.on) return "the goal curriculum is on and the replays belong to the base levels (npp_set_goal_curriculum(h, 0, NULL) first)";
     if (h->ov.n_cuts) return "the observation overlap is on (npp_set_obs_overlap(h, 0) first)";
+    if (h->sweep.on) return "an evaluation sweep is running (npp_sweep_stop(h) first)";
     return nullptr;
 }
 const char *demo_refusal(npp_handle h) {
@@ -3083,6 +3231,7 @@ int npp_archive_seed(npp_handle h, const uint8_t *inputs, const int64_t *offsets
     if (score_mode == SEED_TABLE && !d_scores) return fail(h, NPP_ERR_INVALID, "npp_archive_seed: score_mode 2 (table) needs d_scores");
     if (h->ls.levels.empty()) return fail(h, NPP_ERR_STATE, "npp_archive_seed: no levels loaded");
     // every refusal comes before the first change: a refused call leaves the handle and the index as they were
+    if (h->sweep.on) return fail(h, NPP_ERR_STATE, "npp_archive_seed: an evaluation sweep is running (npp_sweep_stop(h) first)");
     CellArgs c;
     if (int rc = cells_args(h, "npp_archive_seed", c)) return rc;   // (no cell index; the causes npp_archive_explore names)
     if (const char *why = player_refusal(h)) return fail(h, NPP_ERR_STATE, std::string("npp_archive_seed: ") + why);

@@ -16,6 +16,7 @@
 #include "npp_reach_build.hpp"
 #include "npp_route.hpp"
 #include "npp_seed.hpp"
+#include "npp_sweep.hpp"
 
 using namespace npp;
 
@@ -332,6 +333,27 @@ int npp_episode_apply_host(int32_t *rec_i32, double *rec_f64, uint64_t *table, i
     for (int k = 0; k < EP_NI; k++) rec_i32[k] = r.i[k];
     for (int k = 0; k < EP_ND; k++) rec_f64[k] = r.d[k];
     if (ended) *ended = any ? 1 : 0;
+    return NPP_OK;
+}
+
+int npp_sweep_assign_host(const uint8_t *flags, int end_bits, int n_envs, const int32_t *jobs, int n_jobs, int32_t *counters, int32_t *env_job,
+                          int32_t *prev_job, int32_t *env_level, int32_t *trunc, const int32_t *level_trunc, int n_levels, uint8_t *changed) {
+    static_assert(SWEEP_RI == NPP_SWEEP_RI && SWEEP_RD == NPP_SWEEP_RD && SWEEP_R_FLAGS == NPP_SWEEP_R_FLAGS && SWEEP_R_ENV == NPP_SWEEP_R_ENV &&
+                      SWEEP_R_STATUS == NPP_SWEEP_R_STATUS,
+                  "the result planes include/npp_amd.h documents");
+    if (n_envs < 0 || n_jobs < 0 || n_levels < 0 || !counters || (n_jobs > 0 && !jobs) ||
+        (n_envs > 0 && (!flags || !env_job || !prev_job || !env_level || !changed || (level_trunc && !trunc))))
+        return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_assign_host: bad arguments");
+    if (counters[SWEEP_NEXT] < 0 || counters[SWEEP_NEXT] > n_jobs + n_envs)
+        return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_assign_host: next outside 0 .. n_jobs + n_envs");
+    for (int j = 0; j < n_jobs; j++)
+        if (jobs[j] < 0 || (level_trunc && jobs[j] >= n_levels))
+            return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_assign_host: job " + std::to_string(j) + ": level id out of range");
+    for (int e = 0; e < n_envs; e++)
+        if (env_job[e] < -1 || env_job[e] >= n_jobs)
+            return fail(nullptr, NPP_ERR_INVALID, "npp_sweep_assign_host: env " + std::to_string(e) + ": job out of range");
+    counters[SWEEP_NEXT] += sweep_assign_row(flags, end_bits, n_envs, jobs, n_jobs, counters[SWEEP_NEXT], env_job, prev_job, env_level, trunc,
+                                             level_trunc, changed);
     return NPP_OK;
 }
 

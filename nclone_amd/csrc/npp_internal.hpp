@@ -205,6 +205,27 @@ struct GoalArgs {
 };
 hipError_t launch_goal_update(const GoalArgs &a, hipStream_t s);
 hipError_t launch_goal_assign(const GoalArgs &a, hipStream_t s);
+// npp_sweep.hip: the evaluation sweep (see npp_sweep_start in include/npp_amd.h; the rule: npp_sweep.hpp)
+struct SweepArgs {
+    int n, n_jobs;
+    const int32_t *jobs;          // [n_jobs] level ids
+    int32_t *counters;            // [3] next | done | n_jobs
+    int32_t *env_job, *prev_job;  // [n]
+    // assign: the step's flags row and what the level pool's draw writes
+    const uint8_t *flags;         // [n] env e's episode ended when flags[e] & bits
+    int bits;
+    int32_t *env_level;           // [n]
+    int32_t *trunc;               // [n] truncation limits
+    const int32_t *level_trunc;   // [n_levels] or null, as PoolArgs
+    uint8_t *changed;             // [n] out: 1 = the env's next job is on another level than it played (every other byte 0)
+    // collect: the episode records (EpisodeArgs) and the result planes
+    const int32_t *ep_i32;        // [EP_NI][n]
+    const double *ep_f64;         // [EP_ND][n]
+    int32_t *res_i32;             // [SWEEP_RI][n_jobs]
+    double *res_f64;              // [SWEEP_RD][n_jobs]
+};
+hipError_t launch_sweep_assign(const SweepArgs &a, hipStream_t s);
+hipError_t launch_sweep_collect(const SweepArgs &a, hipStream_t s);
 // npp_augment.hip: one augmentation call (see npp_frame_augment in include/npp_amd.h; the draw and the pixels: npp_augment.hpp)
 struct AugArgs {
     int n, k;                     // k: player_frame entries per env (the visual stack size, or 1)

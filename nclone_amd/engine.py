@@ -299,6 +299,7 @@ class NppBatch:
         self._reward_mode, self._reward_pending = 0, False   # (so does reward mode "pbrs": its constants are per level)
         self._reward_waypoints = False
         self._goal = None   # (and the goal curriculum: its variants were compiled from the old set)
+        self._sweep = None  # (and an evaluation sweep with its results: the jobs named levels of the old set)
 
     # ---- goal curriculum (include/npp_amd.h npp_set_goal_curriculum; the reference's IntermediateGoalManager) -----
     GOAL_LEVEL_WORDS = ("stage", "pending", "num_stages", "variant0", "fill", "head", "wins", "advances", "appended", "stale")
@@ -322,6 +323,7 @@ class NppBatch:
         self._reward_waypoints = False
         self._pool_weights = None
         self._goal = None
+        self._sweep = None
         self.n_levels = self.lib.npp_num_levels(self.h)
         if not on:
             return
@@ -957,6 +959,44 @@ class NppBatch:
 
     def episode_table_reset(self):
         nat.check(self.h, self.lib.npp_episode_table_reset(self.h))
+
+    # ---- evaluation sweep (include/npp_amd.h npp_sweep_start) ---------------------------------------------
+    _SWEEP_I32 = _EPISODE_I32 + ("flags", "env", "status")
+
+    def sweep_start(self, jobs):
+        """Play the level ids of `jobs` once each, in list order: env e starts on job e and every env takes the next job of the list
+        when its episode ends (behind step(), in the place of the level pool's draw); an env that finds the list used up idles.
+        Needs set_episode_stats(), and one episode_accumulate() behind every step().  A bad list raises ValueError."""
+        j = np.ascontiguousarray(jobs, dtype=np.int32).ravel()
+        if len(j) == 0:
+            raise ValueError("sweep_start: the job list is empty")
+        code = self.lib.npp_sweep_start(self.h, j.ctypes.data_as(C.c_void_p), len(j))
+        if code == nat.NPP_ERR_INVALID:
+            raise ValueError(self.lib.npp_last_error(self.h).decode())
+        nat.check(self.h, code)
+        a, b, c, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nj = C.c_int()
+        nat.check(self.h, self.lib.npp_sweep_view(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(nj)))
+        J = nj.value
+        i32 = _device_tensor(b.value, len(self._SWEEP_I32) * J, torch.int32, self.device).view(-1, J)
+        f64 = _device_tensor(c.value, 7 * J, torch.float64, self.device).view(7, J)
+        v = {"jobs": j.copy(), "n_jobs": J, "env_job": _device_tensor(a.value, self.n, torch.int32, self.device),
+             "counters": _device_tensor(d.value, 3, torch.int32, self.device), "i32": i32, "f64": f64, "ret": f64[0], "comp": f64[1:7]}
+        for k, name in enumerate(self._SWEEP_I32):
+            v[name] = i32[k]
+        self._sweep = v
+
+    def sweep_stop(self):
+        """End the sweep: every env keeps the level it plays.  The result views of sweep_state() stay readable."""
+        nat.check(self.h, self.lib.npp_sweep_stop(self.h))
+
+    def sweep_state(self):
+        """Device views (no copy) of the last sweep started on this level set, rewritten in stream order: "jobs" (numpy int32 [J]),
+        "n_jobs", "env_job" int32 [N] (-1 = idle), "counters" int32 [3] = next, done, n_jobs, and per job the result planes "i32"
+        [9, J] (rows steps, frames, switch_step, switch_frames, level, bits, flags, env, status) and "f64" [7, J] (ret, comp)."""
+        if getattr(self, "_sweep", None) is None:
+            raise ValueError("no evaluation sweep was started on this level set (sweep_start)")
+        return self._sweep
 
     # ---- cell index over the archive (include/npp_amd.h npp_archive_cells_create; DESIGN.md 17) ------------------------
     def archive_cells_create(self, seed=0, enable=True):

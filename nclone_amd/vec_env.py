@@ -73,6 +73,25 @@ def controls_to_input_byte(hor, jump):
     return (1 if jump else 0) | (2 if hor > 0 else 0) | (4 if hor < 0 else 0)
 
 
+def reduce_evaluation(levels, episodes_per_level, done, is_success, returns, frames):
+    """The per-level table of an evaluation: the [J] per-job arrays (job j = episode j // L of levels[j % L]) reshaped to [K, L] and
+    summed along axis 0 in float64, episode 0 first, over the jobs that are done: {"level" [L], "episodes" int64 [L], "success_rate",
+    "mean_return", "mean_frames" float64 [L]; 0 where a level has no finished episode}."""
+    lv = np.asarray(levels, dtype=np.int32).ravel()
+    K, L = int(episodes_per_level), len(lv)
+    done = np.asarray(done, dtype=bool).reshape(K, L)
+    n = done.sum(axis=0, dtype=np.int64)
+
+    def total(v):
+        return np.where(done, np.asarray(v, dtype=np.float64).reshape(K, L), 0.0).sum(axis=0, dtype=np.float64)
+
+    div = np.where(n > 0, n, 1).astype(np.float64)
+    return {"level": lv.copy(), "episodes": n,
+            "success_rate": np.where(n > 0, total(np.asarray(is_success, dtype=bool)) / div, 0.0),
+            "mean_return": np.where(n > 0, total(returns) / div, 0.0),
+            "mean_frames": np.where(n > 0, total(frames) / div, 0.0)}
+
+
 class NppVecEnvironment:
     """N N++ environments stepped in lock-step on one MI355X.
 
@@ -227,6 +246,8 @@ class NppVecEnvironment:
                  waypoint_params=None, episode_stats=False, goal_curriculum=False, goal_curriculum_params=None):
         assert output in ("torch", "numpy")
         self._episode = bool(episode_stats)
+        self._sweep = False    # an evaluation is running (start_evaluation)
+        self._swept = False    # one has run: the levels moved on the device and the fixed assignment no longer describes them
         self._goal = bool(goal_curriculum)
         self._goal_params = dict(goal_curriculum_params) if goal_curriculum_params else {}
         if self._goal and reward_waypoints:
@@ -482,6 +503,9 @@ class NppVecEnvironment:
                  slot_ids[e]; with -1, or where the restore's status is not 0 (empty slot, another level, out of range), the env
                  does an ordinary spawn reset.  info = {"checkpoint_replay": False, "restored": bool [N], "restore_status": i32 [N]}.
                  Other keys of the reference (skip_map_load, new_level, map_name) concern its map loader and are ignored."""
+        if self._sweep:
+            raise RuntimeError("reset() in the middle of an evaluation: the sweep hands out the levels and a reset env's job would "
+                               "be played twice (start_evaluation() begins a new one, stop_evaluation() ends it)")
         if seed is not None:
             self._rng = np.random.default_rng(seed)
             if self._pool:   # the pool's draws restart from the seed (off and on again: the draw counts restart at 0)
@@ -539,6 +563,10 @@ class NppVecEnvironment:
                         self._b.episode_restart(None, from_restore=True)
                 else:
                     info = {"checkpoint_replay": False, "replay_frames": 0}
+        return self._reset_return(info)
+
+    def _reset_return(self, info):
+        """(obs, info) of the state every env is in now, every frame stack re-padded: what reset() and start_evaluation() return"""
         self._b.observe()
         self._produce(reset_all=True)
         if self.output == "torch":
@@ -689,7 +717,7 @@ class NppVecEnvironment:
             "completion_count": env[2], "at_final_stage": (ns > 0) & (stage >= ns - 1)}
 
     def _level_id(self, numpy):
-        if self._pool or self._goal:
+        if self._pool or self._goal or self._swept:
             if numpy:
                 return self._b.env_levels()
             with self._b._ctx():
@@ -1070,6 +1098,81 @@ class NppVecEnvironment:
             raise RuntimeError("reset_episode_level_stats: this env was created without episode_stats")
         self._b.episode_table_reset()
 
+    # -- evaluation sweep (the reference's eval_mode, env_map_loader.py:138-162) ------------------------------
+    def start_evaluation(self, levels=None, episodes_per_level=1):
+        """Evaluate on a fixed list of levels (default: every loaded level), each played exactly episodes_per_level times: the job
+        list is tile(levels, K), env e starts on job e and every env takes the next job when its episode ends; envs that find the
+        list used up idle.  Returns (obs, info) like reset().  Needs episode_stats=True (the results are its records).  From here
+        to stop_evaluation() step() adds info["evaluation"] = {"active": bool [N], "job": int32 [N]} and reset() is refused."""
+        if not self._episode:
+            raise RuntimeError("start_evaluation: this env was created without episode_stats=True, and an evaluation's results are "
+                               "the episode records")
+        K = int(episodes_per_level)
+        if K < 1:
+            raise ValueError("start_evaluation: episodes_per_level must be >= 1")
+        lv = np.arange(len(self._levels), dtype=np.int32) if levels is None else np.asarray(levels, dtype=np.int32).ravel()
+        if len(lv) == 0:
+            raise ValueError("start_evaluation: no levels")
+        self._b.sweep_start(np.tile(lv, K))
+        self._sweep = self._swept = True
+        self._eval = {"levels": lv.copy(), "episodes_per_level": K}
+        return self._reset_return({"evaluation": {"levels": lv.copy(), "episodes_per_level": K, "jobs": len(lv) * K}})
+
+    def stop_evaluation(self):
+        """End the evaluation (finished or not): every env keeps the level it plays; evaluation_results() stays readable."""
+        self._b.sweep_stop()
+        self._sweep = False
+
+    def _need_evaluation(self, what):
+        if getattr(self, "_eval", None) is None:
+            raise RuntimeError("%s: no evaluation was started (start_evaluation)" % what)
+        return self._b.sweep_state()
+
+    def evaluation_done(self):
+        """True once every job has finished.  One 12-byte read that synchronises: call it every few steps, not every step."""
+        s = self._need_evaluation("evaluation_done")
+        with self._b._ctx():
+            c = s["counters"].cpu().numpy()
+        return int(c[1]) == int(c[2])
+
+    def evaluation_results(self):
+        """The outcome of every job, in job order (job j = episode j // L of level levels[j % L]): {"level", "env" (-1: not
+        played yet), "done", "is_success", "dead", "truncated", "death_cause", "steps", "frames", "switch_frames" (-1: the switch was
+        never activated), "r"} (+ "pbrs_components" [J, 6] with reward_mode="pbrs"), each [J], and "per_level" = {"level",
+        "episodes", "success_rate", "mean_return", "mean_frames"} [L], reduced in float64 over the [K, L] reshape along axis 0, so
+        the same results give the same bits.  Synchronises."""
+        s = self._need_evaluation("evaluation_results")
+        with self._b._ctx():
+            i32, f64 = s["i32"].cpu().numpy(), s["f64"].cpu().numpy()
+        steps, frames, sw_step, sw_frames, _level, _bits, flags, env, status = i32
+        out = {"level": s["jobs"].copy(), "env": env, "done": status != 0, "is_success": (flags & 1) != 0, "dead": (flags & 2) != 0,
+               "truncated": (flags & 8) != 0, "death_cause": (flags >> 4) & 3, "steps": steps, "frames": frames,
+               "switch_frames": np.where(sw_step != 0, sw_frames, -1), "r": f64[0]}
+        if self._pbrs:
+            out["pbrs_components"] = np.ascontiguousarray(f64[1:7].T)
+        per = reduce_evaluation(self._eval["levels"], self._eval["episodes_per_level"], out["done"], out["is_success"], out["r"], frames)
+        if self.output == "torch":
+            with self._b._ctx():
+                out = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self._b.device) for k, v in out.items()}
+                per = {k: torch.from_numpy(v).to(self._b.device) for k, v in per.items()}
+        out["per_level"] = per
+        return out
+
+    def evaluate(self, policy, levels=None, episodes_per_level=1, max_steps=None, check_every=16):
+        """start_evaluation(), then step with actions = policy(obs) until every job has finished (looked at every check_every steps)
+        or max_steps steps have run, then stop_evaluation().  Returns evaluation_results(); jobs that did not finish have done False."""
+        obs, _ = self.start_evaluation(levels, episodes_per_level)
+        try:
+            t = 0
+            while max_steps is None or t < int(max_steps):
+                obs = self.step(policy(obs))[0]
+                t += 1
+                if t % int(check_every) == 0 and self.evaluation_done():
+                    break
+            return self.evaluation_results()
+        finally:
+            self.stop_evaluation()
+
     def step_wait(self):
         """Results of the step enqueued by step_async: (obs, reward, terminated, truncated, info) with batch dims.
         output="torch": device tensors, no synchronisation (consume them on the handle's stream);
@@ -1110,6 +1213,14 @@ class NppVecEnvironment:
             info["waypoints"] = {"bonus": wb, "index": wi[:, 0], "next_expected": wi[:, 1], "collected": wi[:, 2]}
         if self._episode:
             info["_episode"], info["episode"] = self._episode_info()
+        if self._sweep:   # the job every env plays from this observation on (-1: idle, the list is used up)
+            job = b.sweep_state()["env_job"]
+            if self.output == "numpy":
+                with b._ctx():
+                    job = job.cpu().numpy()
+            else:
+                job = job.clone()
+            info["evaluation"] = {"active": job >= 0, "job": job}
         return self._with_graph(self._obs(src), raw_levels), src["reward"], (flags & 3) != 0, (flags & 8) != 0, info
 
     def step(self, actions):
